@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the CWT hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3_paul|c3_dog]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3_paul|c3_dog] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one synthetic signal: (broadcast of the signal when N > 1) -> forward
 FFT -> all rows of W written device-resident.  Inputs are resident in HBM when the timed region starts.
@@ -16,11 +16,17 @@ default multi-GPU line) refines the grid to 256*G rows instead, 256 per GPU.
 
 Clocks: this GPU idles at sclk ~0.5 GHz and needs ~45 ms of work to reach its sustained clock (tools/clock_ramp.py), more
 than the W warm-up steps of a short run last.  bench.py therefore runs an untimed priming phase (>= 80 ms of the same
-steps) BEFORE the W warm-up steps; W and K are honoured exactly.  The same W + K steps started from the idle device are
-measured first and reported as `from_idle`; `--no-prime` makes that the headline.
+steps) BEFORE the W warm-up steps; W and K are honoured exactly.  With `--full` the same W + K steps started from the idle
+device are measured first and reported as `from_idle`; `--no-prime` makes that the headline.
 
-Rank 0 prints ONE JSON line with the driver's contract fields plus
+A plain run sets up, primes, warms up, times the K steps and prints ONE JSON line with the driver's contract fields
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  `--dump-outputs DIR` then writes what the
+last timed step computed (a seeded column sample of W, the spectrum at the same columns) as float .npy files.
+
+`--full` adds everything else, each in passes of its own after the headline's timed steps:
+  from_idle     the same W + K steps timed from the idle device
   roofline      dominant kernel, HIP-event timed inside this process in a separate pass
+  icwt, cold_grid_ms, api, weak_scaling (multi-GPU)
   parity        (1 GPU) every row of W of the timed workload against the CPU oracle: max per-row error, worst
                 row, worst row per kernel class
   cpu_baseline  (1 GPU) the oracle timed on this box's host cores on the same rows (kind "port") and the whole
@@ -57,6 +63,7 @@ PARITY_TOL = {64: 1e-8, 32: 1e-5}       # per-row max|dW|/max|W|: 1/100 of north
 # (spectral dynamic range max|xhat|/rms|xhat| ~ 4), for which these targets leave every row >= 100x inside north_star's
 # bars (parity block: all 256 rows).  `extra.c2_roundoff` times the same workload at the engine's default.
 BENCH_TOLERANCE = {64: 1e-9, 32: 3e-5}
+DUMP_BYTES = 60_000_000        # --dump-outputs: the column sample of W and the spectrum stays below this many bytes
 
 
 def scale_grid(N, dt, flambda, rows):
@@ -237,6 +244,25 @@ class Workload:
         ms = elapsed / steps * 1e3
         return {"ms_per_step": ms, "value": float(self.N) * self.rows_total / (elapsed / steps) / 1e9,
                 "host_enqueue_ms_per_step": self.host_enqueue_ms}
+
+    def dump_outputs(self, path, steps):
+        """--dump-outputs: what the last of `steps` timed steps left for a caller of the timed path -- this rank's rows of W
+        and (unsharded) the signal's spectrum -- as float arrays, complex values as trailing (re, im) pairs.  Every row is
+        kept at a fixed, seeded sample of columns (the same for W and the spectrum) so that the files stay under 64 MB."""
+        torch = self.rt.torch
+        _, _, W, xhat = self.lanes[(steps - 1) % len(self.lanes)]
+        rows = len(self.sj)
+        k = min(self.N, DUMP_BYTES // ((rows + 1) * self.csize))
+        cols = np.sort(np.random.default_rng(4321).choice(self.N, size=k, replace=False))
+        idx = torch.from_numpy(cols).to(self.rt.dev)
+        tag = f"_rank{self.rt.rank}" if self.rt.world > 1 else ""
+        os.makedirs(path, exist_ok=True)
+        arrays = {"columns": cols.astype(np.float64), "scales": self.sj.astype(np.float64),
+                  "W": torch.view_as_real(W[:rows].index_select(1, idx)).cpu().numpy()}
+        if not self.sharded:
+            arrays["fft"] = torch.view_as_real(xhat.index_select(0, idx)).cpu().numpy()
+        for name, a in arrays.items():
+            np.save(os.path.join(path, name + tag + ".npy"), a)
 
     def api_timed(self, steps, warmup):
         """The same K steps through the PUBLIC multi-GPU entry point, `pycwt_amd.parallel.cwt_sharded` (shape known to every
@@ -694,7 +720,7 @@ def live_traffic(config, logn, rows, n_poly, csize):
             out = os.path.join(tmp, counter)
             cmd = [prof, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", out, "-o", "cwt", "--",
                    sys.executable, os.path.abspath(__file__), "--config", config, "--logn", str(logn), "--rows", str(rows),
-                   "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--no-prime", "--no-live-traffic",
+                   "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra", "--no-prime", "--no-live-traffic",
                    "--opt", "overlap_narrow=0", "--opt", "ols_early=0", "--opt", "ols_side=0"]
             env = dict(os.environ, TMPDIR="/tmp")
             r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=120)
@@ -751,8 +777,9 @@ def compact_line(out, detail_path):
     if not line["config"].get("plan_options"):
         line["config"].pop("plan_options", None)
     roof = out.get("roofline") or {}
-    line["roofline"] = pick(roof, ["bound", "kernel", "achieved", "peak", "unit", "frac", "whole_path_frac", "traffic",
-                                   "avg_launch_ms", "launches_per_step", "algorithmic_bytes_per_launch", "row_split"])
+    if "roofline" in out:                  # (--full)
+        line["roofline"] = pick(roof, ["bound", "kernel", "achieved", "peak", "unit", "frac", "whole_path_frac", "traffic",
+                                       "avg_launch_ms", "launches_per_step", "algorithmic_bytes_per_launch", "row_split"])
     if roof.get("traffic_source"):
         line["roofline"]["traffic_source"] = "live rocprofv3 PMC passes" if roof["traffic_source"].startswith("measured") else "committed PMC passes"
     if "cpu_baseline" in out:
@@ -814,11 +841,12 @@ def compact_line(out, detail_path):
     return rnd(line)
 
 
-def measure(rt, config, args, rows_total, opts, want_cpu, traffic_passes=True, signal="white", auto_target=None):
+def measure(rt, config, args, rows_total, opts, want_cpu, traffic_passes=True, signal="white", auto_target=None, dump=None):
+    """The headline's timed steps (and `dump`: their outputs); with --full the passes of their own that follow them."""
     wl = Workload(rt, config, args.logn, rows_total, opts, args.partition, args.pipeline, signal=signal, auto_target=auto_target)
     if args.prime and not args.emulate:
-        # the same W + K steps first from an idle device (reported as `from_idle`), then with the clocks up (the headline)
-        idle = wl.timed(args.steps, args.warmup)
+        # (--full) the same W + K steps first from an idle device (reported as `from_idle`), then with the clocks up (the headline)
+        idle = wl.timed(args.steps, args.warmup) if args.full else None
         primed_steps = wl.prime(PRIME_MS)
         out = wl.timed(args.steps, args.warmup)
         if args.shard:
@@ -827,16 +855,27 @@ def measure(rt, config, args, rows_total, opts, want_cpu, traffic_passes=True, s
             again = wl.timed(args.steps, args.warmup)
             if again["ms_per_step"] < out["ms_per_step"]:
                 out = again
-        out["from_idle"] = {"ms_per_step": idle["ms_per_step"], "value": idle["value"],
-                            "note": "the same W warm-up + K timed steps started on an idle device (clocks still ramping)"}
-        out["effective_warmup_steps"] = args.warmup + primed_steps + args.warmup + args.steps    # everything that ran before
-        # the K timed steps of the headline: the from-idle pass (W + K), the priming steps, the W warm-up steps
+        if idle:
+            out["from_idle"] = {"ms_per_step": idle["ms_per_step"], "value": idle["value"],
+                                "note": "the same W warm-up + K timed steps started on an idle device (clocks still ramping)"}
+        # everything that ran before the K timed steps of the headline: (--full) the from-idle pass (W + K), the priming
+        # steps, the W warm-up steps
+        out["effective_warmup_steps"] = (args.warmup + args.steps if idle else 0) + primed_steps + args.warmup
         out["clock_priming"] = (f"{primed_steps} untimed steps (>= {PRIME_MS:.0f} ms of work) before the W warm-up steps: this "
                                 "GPU needs ~45 ms of work to go from its idle clock (sclk ~0.5 GHz) to its sustained clock "
                                 "(tools/clock_ramp.py, profiles/r03_clock_ramp.txt); the K timed steps are unchanged")
     else:
         out = wl.timed(args.steps, args.warmup)
         out["effective_warmup_steps"] = args.warmup
+    if dump:
+        rt.fence()
+        wl.dump_outputs(dump, args.steps)
+    out["dtype"] = "f64" if wl.prec == 64 else "f32"
+    out["label"] = wl.label
+    out["tolerance"] = wl.tolerance
+    if not args.full:
+        wl.close()
+        return out
     if rt.use_dist and not args.shard and wl.kind != 1:      # (Paul: the API drops the reference's NaN rows, another workload)
         out["api"] = wl.api_timed(args.steps, args.warmup)
     traffic = None
@@ -866,9 +905,6 @@ def measure(rt, config, args, rows_total, opts, want_cpu, traffic_passes=True, s
         if signal == "white":                 # (the coloured-input block only wants the parity)
             out["cpu_baseline"]["reference_as_is"] = wl.reference_as_is()
             out["cpu_baseline"]["reference_mounted"] = out["cpu_baseline"]["reference_as_is"]["reference_mounted"]
-    out["dtype"] = "f64" if wl.prec == 64 else "f32"
-    out["label"] = wl.label
-    out["tolerance"] = wl.tolerance
     wl.close()
     return out
 
@@ -908,7 +944,15 @@ def main():
     ap.add_argument("--lib", default=None, help="tuning: another build of libcwt_hip.so (a -D variant under tools/lab/)")
     ap.add_argument("--emulate", action="store_true",
                     help="CPU rehearsal of the launch/stdout contract on the emulated kernel library (tests/emu); not a measurement")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float; complex as (re, im) "
+                         "pairs): W at a seeded sample of columns, every row of this rank; the spectrum at the same columns")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: from_idle, roofline, icwt, cold grid, cpu_baseline / "
+                         "parity, the extra workloads, the API and weak-scaling passes of a multi-GPU run")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.shard:
         # plain `python bench.py --gpus N`: become the launcher -- one rank per GPU through torch.distributed.run on the
@@ -939,9 +983,9 @@ def main():
     kind, param, prec, label = CONFIGS[args.config]
     N = 1 << args.logn
     rows_total = args.rows * world if args.weak else args.rows
-    single = world == 1 and not args.no_cpu_baseline and not args.shard
+    single = world == 1 and not args.no_cpu_baseline and not args.shard and args.full
 
-    head = measure(rt, args.config, args, rows_total, opts, want_cpu=single and rank == 0)
+    head = measure(rt, args.config, args, rows_total, opts, want_cpu=single and rank == 0, dump=args.dump_outputs)
     workload = f"N=2^{args.logn} {label} {rows_total} scales"
     if world > 1:
         workload += (f" split over {world} GPUs (contiguous cost-balanced shards)" if args.partition == "balanced"
@@ -960,8 +1004,9 @@ def main():
                                    else "single GPU"),
                    "plan_options": opts, **({"shard_diagnostic": args.shard} if args.shard else {}),
                    **({"signals_in_flight": args.pipeline} if args.pipeline > 1 else {})},
-        "roofline": head["roofline"],
     }
+    if "roofline" in head:
+        out["roofline"] = head["roofline"]
     try:       # which binary was measured: the id embedded in the loaded library against the id of this tree's sources
         from pycwt_amd import _build
         tree = _build.source_id() if all(os.path.exists(d) for d in _build.DEPS) else None
@@ -979,7 +1024,7 @@ def main():
             out[k] = head[k]
     if "clock_priming" in head:
         out["config"]["clock_priming"] = head["clock_priming"]
-    if world > 1 and not args.weak:
+    if world > 1 and not args.weak and args.full:
         # same run, weak-scaling variant (per-GPU work fixed): --rows rows per GPU of a rows*G-row grid
         weak = measure(rt, args.config, args, args.rows * world, opts, want_cpu=False)
         out["weak_scaling"] = {"value": weak["value"], "ms_per_step": weak["ms_per_step"], "rows_total": args.rows * world,

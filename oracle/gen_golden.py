@@ -18,6 +18,9 @@ Cases:
   unpadded       the pyfftw branch (transform length = len(signal), helpers.py:15-19) at n0 = 504, 1000, 331
   sample_<name>  the sample/sample.py recipe on the reference's other datasets (sample/dataset.py:68-135): mauna,
                  monsoon, sunspot, soi -- anomaly / std, default s0 and J, Morlet(6); every third row of W is kept
+  live_reference the reference's outputs for the drop-in checks of tests/test_shim_vs_live_reference.py, the mother-object
+                 cases of tests/test_shim_emulated.py and the oracle cases of tests/test_oracle_golden.py (``live_*``):
+                 seeded calls, edge inputs, the reference's own mother objects, non-finite samples
 The signal itself is stored too (NINO3 data is 504 floats).
 """
 import os
@@ -213,7 +216,131 @@ def mc_significance():
          **{f"c{i}_{k}": v for i, c in enumerate(cases) for k, v in c.items()})
 
 
+FULL = 64           # live_reference: arrays up to this many elements are stored as they are, longer ones as a fingerprint
+
+
+def fingerprint(out, key, a):
+    """`a` under `key`: its shape, and the array itself if it is short; else its dtype-preserving values at a seeded sample of
+    FULL flat positions (`_idx`, `_at`) and the max and L2 norm of every row along the last axis (`_rowmax`, `_rownorm`).
+    tests/conftest.py::match_reference checks an array against it."""
+    a = np.asarray(a)
+    out[key + "_shape"] = np.array(a.shape)
+    if a.size <= FULL:
+        out[key] = a
+        return
+    idx = np.sort(np.random.default_rng(a.size).choice(a.size, FULL, replace=False))
+    out[key + "_idx"], out[key + "_at"] = idx, a.reshape(-1)[idx]
+    mag = np.abs(a.reshape(-1, a.shape[-1])).astype(np.float64)
+    out[key + "_rowmax"], out[key + "_rownorm"] = mag.max(axis=1), np.sqrt((mag * mag).sum(axis=1))
+
+
+def live_cases():
+    """One file of reference outputs, keyed by case: ``<case>_<return>`` for the six returns of cwt (fingerprints, see
+    `fingerprint`), ``<case>_icwt``, flags."""
+    out = {}
+
+    def put(case, res, keep_w=True):
+        for k, v in zip(("W", "sj", "freqs", "coi", "fft", "fftfreqs"), res):
+            if k != "W" or keep_w:
+                fingerprint(out, f"{case}_{k}", v)
+        out[f"{case}_W_shape"] = np.array(res[0].shape)
+        out[f"{case}_W_allnan"] = np.array(bool(np.isnan(res[0]).all()))
+        out[f"{case}_fft_finite_any"] = np.array(bool(np.isfinite(res[4]).any()))
+
+    for name in ("morlet", "paul", "dog", "mexicanhat"):                 # test_oracle_golden.py::test_live_reference
+        x = np.random.default_rng(3).standard_normal(777)
+        res = ref.cwt(x, 0.3, 1 / 6, -1, -1, name)
+        put("live_" + name, res)
+        if name != "paul":
+            fingerprint(out, f"live_{name}_icwt", ref.icwt(res[0], res[1], 0.3, 1 / 6, name))
+    x = np.random.default_rng(5).standard_normal(700)                    # test_shim_emulated.py: the reference's mothers
+    for i, m in enumerate((ref.Morlet(6), ref.Paul(4), ref.DOG(3), ref.MexicanHat())):
+        put(f"mothers_{i}", ref.cwt(x, 0.3, 0.25, -1, -1, m))
+    # seeded calls drawn as the strategy of test_shim_vs_live_reference.py draws them
+    rng = np.random.default_rng(2024)
+    calls = []
+    for i in range(CALLS):
+        n0 = int(rng.integers(20, 601))
+        dt = float(rng.choice([0.25, 1.0, 1 / 12, 7.0]))
+        dj = float(rng.choice([1 / 12, 0.25, 0.5, 1.0]))
+        name = str(rng.choice(["morlet", "paul", "dog", "mexicanhat"]))
+        use_defaults = bool(rng.integers(2))
+        s0 = -1.0 if use_defaults else dt * float(rng.uniform(0.5, 8.0))
+        J = -1 if use_defaults else int(rng.integers(1, 41))
+        use_freqs = bool(rng.integers(2)) and not use_defaults
+        seed = int(rng.integers(0, 2 ** 31))
+        x = np.random.default_rng(seed).standard_normal(n0).cumsum() * 0.1 + np.random.default_rng(seed + 1).standard_normal(n0)
+        kw = {"freqs": np.geomspace(0.4 / dt, 1.0 / (n0 * dt), 7)} if use_freqs else {}
+        res = ref.cwt(x, dt, dj, s0, J, name, **kw)
+        put(f"call{i}", res)
+        out[f"call{i}_seed"] = np.array(seed)
+        out[f"call{i}_args"] = np.array([dt, dj, s0, J, float(use_freqs)])
+        out[f"call{i}_name"] = np.array(name)
+        mother = {"morlet": ref.Morlet(), "paul": ref.Paul(), "dog": ref.DOG(), "mexicanhat": ref.MexicanHat()}[name]
+        if mother.cdelta != -1 and res[0].shape[0] > 1:
+            fingerprint(out, f"call{i}_icwt", ref.icwt(res[0], res[1], dt, dj, name))
+        calls.append(name)
+    for name in ("morlet", "paul", "dog"):                                # one NaN / inf sample: sj, freqs, coi, flags
+        for tag, bad in (("nan", np.nan), ("inf", np.inf)):
+            x = np.random.default_rng(5).standard_normal(33000)
+            x[777] = bad
+            res = ref.cwt(x, 0.5, 0.5, -1, -1, name)
+            out[f"nonfinite_{name}_{tag}_W_shape"] = np.array(res[0].shape)
+            out[f"nonfinite_{name}_{tag}_W_allnan"] = np.array(bool(np.isnan(res[0]).all()))
+            out[f"nonfinite_{name}_{tag}_fft_finite_any"] = np.array(bool(np.isfinite(res[4]).any()))
+        for k, v in zip(("sj", "freqs", "coi"), res[1:4]):                # (they do not depend on the sample values)
+            fingerprint(out, f"nonfinite_{name}_{k}", v)
+    x = np.random.default_rng(1).standard_normal(300)                    # edge inputs
+    put("edge_list", ref.cwt(list(x), 0.25, 0.25, 0.5, 20, "morlet"))
+    put("edge_int", ref.cwt(np.arange(300) % 17, 0.25, 0.25, 0.5, 20, "dog"))
+    x = np.random.default_rng(2).standard_normal(700)
+    put("edge_freqs", ref.cwt(x, 0.5, freqs=np.array([0.3, 0.01, 0.9, 0.05])))
+    put("edge_one_row", ref.cwt(x, 0.5, 0.25, 2.0, 0, "morlet"))
+    x = np.random.default_rng(3).standard_normal(1000)
+    for i, m in enumerate((ref.Paul(2), ref.DOG(3), ref.DOG(6), ref.Morlet(3), ref.MexicanHat())):
+        put(f"edge_mother{i}", ref.cwt(x, 1.0, 0.25, -1, -1, m))
+    try:
+        ref.cwt(np.zeros(64), 1.0, wavelet="Morlet")
+        out["edge_keyerror"] = np.array(False)
+    except KeyError:
+        out["edge_keyerror"] = np.array(True)
+    x = np.random.default_rng(4).standard_normal(128)
+    W, sj = ref.cwt(x, 1.0, 0.5, -1, -1, "morlet")[:2]
+    fingerprint(out, "edge_icwt_W", W)
+    fingerprint(out, "edge_icwt_sj", sj)
+    try:
+        ref.icwt(W, sj[:-1], 1.0, 0.5, "morlet")
+        out["edge_icwt_mismatch_warns"] = np.array(False)
+    except Warning:
+        out["edge_icwt_mismatch_warns"] = np.array(True)
+    fingerprint(out, "edge_icwt", ref.icwt(W, sj, 1.0, 0.5, "morlet"))
+    fingerprint(out, "edge_icwt_T", ref.icwt(np.ascontiguousarray(W.T), sj, 1.0, 0.5, "morlet"))
+    for dtype in (np.complex128, np.complex64):
+        rng = np.random.default_rng(5)
+        z = (rng.standard_normal(500) + 1j * rng.standard_normal(500)).astype(dtype)
+        for name in ("morlet", "dog"):
+            put(f"edge_complex_{np.dtype(dtype).name}_{name}", ref.cwt(z, 0.25, 0.25, 0.5, 24, name))
+    for part in ("real", "imag"):
+        rng = np.random.default_rng(8)
+        z = rng.standard_normal(400) + 1j * rng.standard_normal(400)
+        z[37] = complex(np.nan, z[37].imag) if part == "real" else complex(z[37].real, np.nan)
+        args = (0.05, 0.5, 1.0, 18, "paul")
+        out[f"edge_nanpart_{part}_clean_rows"] = np.array(ref.cwt(np.nan_to_num(z), *args)[0].shape[0])
+        put(f"edge_nanpart_{part}", ref.cwt(z, *args), keep_w=False)
+    x = np.random.default_rng(6).standard_normal(300)
+    put("edge_allpaul", ref.cwt(x, 0.001, 0.5, 1.0, 20, "paul"), keep_w=False)
+    x = np.random.default_rng(7).standard_normal(400).astype(np.float32)
+    put("edge_f32", ref.cwt(x, 0.25, 0.25, 0.5, 20, "morlet"))
+    save("live_reference", n_calls=CALLS, **out)
+
+
+CALLS = 40
+
+
 if __name__ == "__main__":
+    if "--live-only" in sys.argv:
+        live_cases()
+        sys.exit(0)
     if "--mc-only" in sys.argv:
         mc_significance()
         sys.exit(0)
@@ -232,3 +359,4 @@ if __name__ == "__main__":
     small()
     mid()
     big()
+    live_cases()

@@ -39,6 +39,26 @@ def load_golden(name):
     return np.load(os.path.join(GOLDEN, name + ".npz"))
 
 
+def match_reference(g, key, a, rtol=1e-12):
+    """`a` against the reference's array `key` of a fixture written by oracle/gen_golden.py `fingerprint`: shape and dtype,
+    and the values -- all of them for a short array; else a seeded sample of them and the max and L2 norm of every row (NaN
+    where the reference has NaN).  Returns `a`, which may then stand in for the reference's array in full."""
+    a = np.asarray(a)
+    assert a.shape == tuple(g[key + "_shape"]), (key, a.shape, tuple(g[key + "_shape"]))
+    b = g[key] if key in g.files else g[key + "_at"]
+    assert a.dtype == b.dtype, (key, a.dtype, b.dtype)
+    finite = np.abs(b[np.isfinite(b)])
+    atol = rtol * max(1.0, float(finite.max()) if finite.size else 1.0)
+    if key in g.files:
+        np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, equal_nan=True, err_msg=key)
+        return a
+    np.testing.assert_allclose(a.reshape(-1)[g[key + "_idx"]], b, rtol=rtol, atol=atol, equal_nan=True, err_msg=key)
+    mag = np.abs(a.reshape(-1, a.shape[-1])).astype(np.float64)
+    np.testing.assert_allclose(mag.max(axis=1), g[key + "_rowmax"], rtol=rtol, equal_nan=True, err_msg=key)
+    np.testing.assert_allclose(np.sqrt((mag * mag).sum(axis=1)), g[key + "_rownorm"], rtol=rtol, equal_nan=True, err_msg=key)
+    return a
+
+
 @pytest.fixture(scope="session")
 def golden():
     return load_golden

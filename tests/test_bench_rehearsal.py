@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,7 +38,8 @@ def run(cmd, detail=None):
 
 def test_single_rank_line_has_parity_and_cpu_baseline(emu_library, tmp_path):
     detail = tmp_path / "detail.json"
-    d = run([sys.executable, "bench.py", "--emulate", "--logn", "13", "--rows", "12", "--steps", "2", "--warmup", "1"], detail)
+    d = run([sys.executable, "bench.py", "--emulate", "--logn", "13", "--rows", "12", "--steps", "2", "--warmup", "1", "--full"],
+            detail)
     full = json.loads(detail.read_text())
     for k in CONTRACT + ["parity", "cpu_baseline"]:
         assert k in d, k
@@ -61,7 +63,8 @@ def test_single_rank_line_has_parity_and_cpu_baseline(emu_library, tmp_path):
 def test_multi_rank_launch_as_the_driver_does(emu_library, world, tmp_path):
     d = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
              "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "bench.py", "--gpus", str(world),
-             "--steps", "2", "--warmup", "1", "--emulate", "--backend", "gloo", "--logn", "13", "--rows", "12"], tmp_path / "d.json")
+             "--steps", "2", "--warmup", "1", "--emulate", "--backend", "gloo", "--logn", "13", "--rows", "12", "--full"],
+            tmp_path / "d.json")
     for k in CONTRACT:
         assert k in d, k
     assert d["n_gpus"] == world and d["scaling"] == "strong"
@@ -101,3 +104,35 @@ def test_plain_multi_gpu_command_spawns_its_own_ranks(emu_library, tmp_path):
     finally:
         os.environ.update(saved)
     assert d["n_gpus"] == 2 and d["config"]["rows_per_gpu"] == 6 and d["value"] > 0
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(emu_library, tmp_path):
+    """Without --full the line carries the headline alone (no parity, cpu_baseline, roofline or extra passes); --steps is the
+    number of timed steps; --dump-outputs writes the last step's W (seeded column sample) and spectrum as float .npy files,
+    the same from run to run, and they are what the oracle computes."""
+    from oracle import cwt_oracle as orc
+    dumps = []
+    for r in range(2):
+        out = tmp_path / f"out{r}"
+        d = run([sys.executable, "bench.py", "--emulate", "--logn", "13", "--rows", "12", "--steps", "3", "--warmup", "1",
+                 "--dump-outputs", str(out)], tmp_path / f"d{r}.json")
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dtype"] == "f64" and d["higher_is_better"] is True
+        assert not {"parity", "cpu_baseline", "roofline", "extra", "from_idle", "icwt_ms", "cold_grid_ms"} & set(d)
+        files = sorted(os.listdir(out))
+        assert files == ["W.npy", "columns.npy", "fft.npy", "scales.npy"], files
+        arrays = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        dumps.append(arrays)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+    a = dumps[0]
+    cols = a["columns"].astype(np.int64)
+    x = np.random.default_rng(1234).standard_normal(1 << 13)
+    ref = orc.cwt_rows(x, 1.0, a["scales"], orc.Mother(orc.MORLET, 6))[:, cols]
+    W = a["W"][..., 0] + 1j * a["W"][..., 1]
+    assert W.shape == ref.shape == (12, cols.size)
+    assert (np.abs(W - ref).max(axis=1) / np.abs(ref).max(axis=1)).max() < 1e-8
+    np.testing.assert_allclose(a["fft"][:, 0] + 1j * a["fft"][:, 1], np.fft.fft(x)[cols], rtol=0, atol=1e-9)

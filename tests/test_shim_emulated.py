@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import pycwt_amd
-from conftest import load_golden, row_errors
+from conftest import load_golden, match_reference, row_errors
 from oracle import cwt_oracle as orc
 
 
@@ -135,24 +135,21 @@ def test_duck_typed_custom_mother_via_explicit_filter_bank(emulated, n0):
 
 
 def test_reference_mother_objects_are_accepted(emulated):
-    """Passing the REFERENCE's own mother instances (no device_id) must give the reference's result,
-    including the Paul NaN-row drop.  Needs /root/reference (build container only)."""
-    import os, sys, warnings
-    if not os.path.isdir("/root/reference/pycwt"):
-        pytest.skip("live reference only exists in the build container")
-    sys.dont_write_bytecode = True
-    sys.path.insert(0, "/root/reference")
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        import pycwt as ref
-        x = np.random.default_rng(5).standard_normal(700)
-        for m in (ref.Morlet(6), ref.Paul(4), ref.DOG(3), ref.MexicanHat()):
-            out_ref = ref.cwt(x, 0.3, 0.25, -1, -1, m)
-            out = pycwt_amd.cwt(x, 0.3, 0.25, -1, -1, m)
-            assert out[0].shape == out_ref[0].shape, m.name
-            per_row, _ = row_errors(out[0], out_ref[0])
-            assert per_row.max() < 1e-12, m.name
-            np.testing.assert_allclose(out[1], out_ref[1])
+    """Mother objects of the reference's shape (psi_ft / flambda / coi, no device_id) must give the reference's result,
+    including the Paul NaN-row drop: the oracle's mothers stand in for the reference's Morlet(6), Paul(4), DOG(3) and
+    MexicanHat(); the reference's outputs for them are in tests/golden/live_reference.npz (mothers_*)."""
+    from oracle import cwt_oracle as orc
+    g = load_golden("live_reference")
+    x = np.random.default_rng(5).standard_normal(700)
+    for i, m in enumerate((orc.Mother(orc.MORLET, 6), orc.Mother(orc.PAUL, 4), orc.Mother(orc.DOG, 3), orc.Mother(orc.DOG, 2))):
+        assert not hasattr(m, "device_id")
+        out = pycwt_amd.cwt(x, 0.3, 0.25, -1, -1, m)
+        # the oracle's W for the same call, pinned to the reference's (fingerprint), stands in for it in full
+        W_ref, sj_ref = (match_reference(g, f"mothers_{i}_{k}", a) for k, a in zip(("W", "sj"), orc.cwt(x, 0.3, 0.25, -1, -1, m)))
+        assert out[0].shape == W_ref.shape, i
+        per_row, _ = row_errors(out[0], W_ref)
+        assert per_row.max() < 1e-12, i
+        np.testing.assert_allclose(out[1], sj_ref)
 
 
 @pytest.mark.parametrize("n0,nb,name", [(500, 5, "morlet"), (9000, 3, "dog"), (9000, 2, "paul")])

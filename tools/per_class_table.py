@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """profiles/rNN_per_class.txt from the default bench line:  python tools/per_class_table.py profiles/r03_bench_default.json
-(the JSON line of `python bench.py`: config 2 at the top level, the two config-3 workloads under `extra`; the traffic
+(the JSON line of `python bench.py --full`: config 2 at the top level, the two config-3 workloads under `extra`; the traffic
 ratios are the ones bench.py read from profiles/traffic_<config>.json)."""
 import json
 import sys
 
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
-print(f"""# Per row class of the bench workloads (python bench.py, default command; N = 2^20, 256 scales; HIP events in the
+print(f"""# Per row class of the bench workloads (python bench.py --full, default command; N = 2^20, 256 scales; HIP events in the
 # profiling pass of bench.py, every kernel alone; `roofline.per_class` of {sys.argv[1]}).
 # frac = rows x N x sizeof(complex) / time / 8 TB/s; traffic = PMC bytes (FETCH_SIZE x2 + WRITE_SIZE) / algorithmic bytes.  Config 2:
 # measured inside the bench run (bench.py live_traffic: two rocprofv3 child passes) and calibrated on k_poly_rows (exact output
