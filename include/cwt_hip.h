@@ -155,8 +155,7 @@ int cwt_plan_set_stream(cwt_plan* plan, void* hip_stream);
  *                  decimated 4096-point transforms per job); default 0: measured +5 % on the step (strided plane stores)
  *   "aols_small_b" 0 = the band-passed signal's second pass on the default tile under "serial_rows" (default 1: 4096-point
  *                  tiles, 256-thread workgroups, which find a CU beside the overlap-save rows)
- *   "graph"        1 = repeated cwt_transform calls with the same buffers and scale grid are captured into a HIP graph
- *                  and replayed (default 0: measured +-0.5 % on the step, the chain is latency bound, not launch bound)
+ *   "graph"        removed (HIP graph replay of repeated calls: measured +-0.5 % on the step); setting it fails
  *   "ct"           0 = never use the compile-time specialised kernels (generic engine only)
  *   "profile"      1 = time every kernel class with HIP events (cwt_plan_timings) */
 int cwt_plan_set_option(cwt_plan* plan, const char* key, int64_t value);

@@ -8,55 +8,153 @@ using namespace cwtd;
 using namespace cwt;
 
 namespace {
-int prepare_rows_table(cwt_plan* p, bool have_signal, int mother, double param, double dt, const double* scales,
-                       int nrows, int64_t ldw, int64_t ncols) {
-  if (nrows < 1 || nrows > p->max_rows) return fail(CWT_EINVAL, "nrows must be in [1, max_rows]");
-  if (ncols < 1 || ncols > p->N || ldw < ncols) return fail(CWT_EINVAL, "need 1 <= ncols <= nfft and ldw >= ncols");
-  if (!(dt > 0) || !std::isfinite(dt)) return fail(CWT_EINVAL, "dt must be positive");
-  const std::vector<double> key = call_key(0, {p->tolerance, double(mother), param, dt, double(nrows), have_signal ? 1.0 : 0.0, double(ncols)},
-                                           {{scales, nrows}});
+// Calls f(T()) with T = the plan's element type (double or float): each launch is written once.
+template <class F>
+int by_precision(const cwt_plan* p, F&& f) {
+  if (p->prec == 64) return f(double());
+  return f(float());
+}
+
+// What a table-building entry point asks for; a field left at its default is not used by that entry point.  The rows come
+// from scales (row b * nrows + j of a batch of nbatch signals at scales[j]; wavelet.py:94, 102), from explicit filter
+// parameters a / amp_re / amp_im, or from a filter bank of the caller's (tab_klo / tab_nband, mother = MOTHER_TABLE).
+struct TableCall {
+  int kind = -1;                          // cache key kind: 0 ... 3, one per kind of entry point (none shares another's tables);
+  std::vector<double> head;               // -1 = never cached; head: the key's values after the kind
+  int mother = MOTHER_TABLE;
+  double param = 0;
+  int nbatch = 1, nrows = 0;              // signals, rows per signal
+  const double* scales = nullptr;
+  double dt = 0;
+  const double* a = nullptr;
+  const double* amp_re = nullptr;
+  const double* amp_im = nullptr;
+  const int* tab_klo = nullptr;
+  const int* tab_nband = nullptr;
+  int64_t ldw = 0, ncols = 0;             // the output W
+  int64_t spec_ld = 0;                    // elements between the rows' spectra (0: one shared spectrum)
+  int rows_per_signal = 0;                // build_row_table: > 0 for a batch
+  int64_t ols_ncols = 0, out_ncols = 0;   // build_row_table: > 0 where the overlap-save / band-passed forms may be used
+};
+
+// Makes the row table of call c current: the cached one of the same call, or a new one.  A new table gets the side tables
+// of whatever forms it contains: decided here from the table alone, never by the entry point (commit 026261b).
+int prepare_table(cwt_plan* p, const TableCall& c) {
+  const int total = c.nbatch * c.nrows;
+  if (total < 1 || total > p->max_rows) return fail(CWT_EINVAL, "nrows must be in [1, max_rows]");
+  if (c.ncols < 1 || c.ncols > p->N || c.ldw < c.ncols) return fail(CWT_EINVAL, "need 1 <= ncols <= nfft and ldw >= ncols");
+  if (c.spec_ld != 0 && c.spec_ld < p->N) return fail(CWT_EINVAL, "spec_ld must be 0 (shared) or >= nfft");
+  if (c.scales && (!(c.dt > 0) || !std::isfinite(c.dt))) return fail(CWT_EINVAL, "dt must be positive");
+  std::vector<double> key;                        // [kind, head..., the rows' arguments]
+  if (c.kind >= 0) {
+    key = c.scales ? call_key(c.kind, {}, {{c.scales, c.nrows}})
+                   : call_key(c.kind, {}, {{c.a, total}, {c.amp_re, total}, {c.amp_im, total}});
+    key.insert(key.begin() + 1, c.head.begin(), c.head.end());
+  }
   if (!select_table(p, key)) {
-    double cre, cim;
-    int rc = mother_constant(mother, param, &cre, &cim);
+    double cre = 0, cim = 0;
+    // the mother id and order of every call but a filter bank of the caller's (whose id is MOTHER_TABLE)
+    int rc = c.tab_klo ? CWT_OK : mother_constant(c.mother, c.param, &cre, &cim);
     if (rc) return rc;
-    const double w1 = 2.0 * 3.14159265358979323846 * (1.0 / (double(p->N) * dt));  // ftfreqs[1], wavelet.py:94
-    std::vector<double> a(nrows), ar(nrows), ai(nrows);
-    for (int j = 0; j < nrows; ++j) {
-      if (!(scales[j] > 0) || !std::isfinite(scales[j])) return fail(CWT_EINVAL, "scales must be positive and finite");
-      a[j] = scales[j] * w1;
-      const double norm = std::sqrt(scales[j] * w1 * double(p->N));                 // wavelet.py:102
-      ar[j] = norm * cre;
-      ai[j] = norm * cim;
+    const double *a = c.a, *amp_re = c.amp_re, *amp_im = c.amp_im;
+    std::vector<double> va, vr, vi;
+    if (c.scales) {
+      const double w1 = 2.0 * 3.14159265358979323846 * (1.0 / (double(p->N) * c.dt));  // ftfreqs[1], wavelet.py:94
+      va.resize(total); vr.resize(total); vi.resize(total);
+      for (int j = 0; j < total; ++j) {
+        const double s = c.scales[j % c.nrows];
+        if (!(s > 0) || !std::isfinite(s)) return fail(CWT_EINVAL, "scales must be positive and finite");
+        va[j] = s * w1;
+        const double norm = std::sqrt(s * w1 * double(p->N));                         // wavelet.py:102
+        vr[j] = norm * cre;
+        vi[j] = norm * cim;
+      }
+      a = va.data(); amp_re = vr.data(); amp_im = vi.data();
+    } else if (!a) {                                  // a filter bank of the caller's holds the amplitudes
+      va.assign(total, 1.0);
+      vi.assign(total, 0.0);
+      a = amp_re = va.data(); amp_im = vi.data();
     }
-    rc = build_row_table(p, mother, param, a.data(), ar.data(), ai.data(), 0, nrows, nullptr, nullptr, 0, -1,
-                         have_signal ? ncols : 0, ncols);
+    rc = build_row_table(p, c.mother, c.param, a, amp_re, amp_im, c.spec_ld, total, c.tab_klo, c.tab_nband, c.rows_per_signal,
+                         -1, c.ols_ncols, c.out_ncols);
     if (!rc) rc = upload_row_table(p, key);
-    if (!rc && p->rt->n_ols)
-      rc = p->prec == 64 ? fill_ols_tables<double>(p, mother_of(mother, param)) : fill_ols_tables<float>(p, mother_of(mother, param));
-    if (!rc && p->rt->n_aols)
-      rc = p->prec == 64 ? fill_aols_tables<double>(p, mother_of(mother, param)) : fill_aols_tables<float>(p, mother_of(mother, param));
-    if (!rc && p->rt->poly_rtab_elems)
-      rc = p->prec == 64 ? fill_poly_tables<double>(p) : fill_poly_tables<float>(p);
+    const Mother mo = mother_of(c.mother, c.param);
+    if (!rc) rc = by_precision(p, [&](auto t) {
+      using T = decltype(t);
+      int r = p->rt->n_ols ? fill_ols_tables<T>(p, mo) : CWT_OK;
+      if (!r && p->rt->n_aols) r = fill_aols_tables<T>(p, mo);
+      if (!r && p->rt->poly_rtab_elems) r = fill_poly_tables<T>(p);
+      return r;
+    });
     if (rc) { p->rt->key.clear(); return rc; }
   }
   set_split(p);
   return CWT_OK;
 }
 
-// Rows of W from the spectrum xhat_dev; x_dev != NULL: the real signal the spectrum came from (n0 samples), which lets
-// time-compact rows take the overlap-save form.
-int transform_rows_common(cwt_plan* p, const void* xhat_dev, const void* x_dev, int64_t n0, int mother, double param,
-                          double dt, const double* scales, int nrows, void* W_dev, int64_t ldw, int64_t ncols) {
-  int rc = prepare_rows_table(p, x_dev != nullptr, mother, param, dt, scales, nrows, ldw, ncols);
-  if (!rc && p->logN >= 18 && !p->profile) rc = ensure_distinct_queues(p);
-  if (rc) return rc;
-  const Mother mo = mother_of(mother, param);
-  return p->prec == 64 ? rows_impl<double>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0)
-                       : rows_impl<float>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0);
+// The rows of a call by scales (every table-building entry point but cwt_filter_rows and cwt_transform_rows_table)
+TableCall scale_rows(int mother, double param, double dt, const double* scales, int nrows, int64_t ldw, int64_t ncols) {
+  TableCall c;
+  c.mother = mother;
+  c.param = param;
+  c.dt = dt;
+  c.scales = scales;
+  c.nrows = nrows;
+  c.ldw = ldw;
+  c.ncols = ncols;
+  return c;
 }
 
-// The overlap-save rows need the signal only: cwt_transform queues them on side stream 1 BEFORE the forward FFT, so
-// that they run beside it and beside the two-pass chain; rows_impl then skips them and joins the stream at its end.
+// Row table of cwt_transform / cwt_transform_rows / cwt_plan_classify
+int prepare_rows_table(cwt_plan* p, bool have_signal, int mother, double param, double dt, const double* scales,
+                       int nrows, int64_t ldw, int64_t ncols) {
+  TableCall c = scale_rows(mother, param, dt, scales, nrows, ldw, ncols);
+  c.kind = 0;
+  c.head = {p->tolerance, double(mother), param, dt, double(nrows), have_signal ? 1.0 : 0.0, double(ncols)};
+  c.ols_ncols = have_signal ? ncols : 0;
+  c.out_ncols = ncols;
+  return prepare_table(p, c);
+}
+
+// Every row of the current row table, as a call of its own (no per-call state)
+int queue_rows(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw, int64_t ncols) {
+  CallScope scope(p);
+  return scope.done(by_precision(p, [&](auto t) { return rows_impl<decltype(t)>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols); }));
+}
+
+// The spectrum of cwt_transform, inside its CallScope.  The overlap-save rows need the signal only: their block spectra are
+// queued on side stream 1 BEFORE the forward FFT, so that they run beside it and beside the two-pass chain; rows_impl then
+// skips them and joins the stream at its end.
+int queue_spectrum(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev) {
+  if (p->rt->n_ols && p->ols_early && !p->profile) {
+    p->call.ols_first_on_main = p->serial_rows >= 2 && serial_schedule(p, true) && p->rt->ols_grp[0].nrows > 0;
+    const int rc = by_precision(p, [&](auto t) { return launch_ols_early<decltype(t)>(p, x_dev, n0); });
+    if (rc) return rc;
+    p->call.ols_launched = 1;
+  }
+  // serial_rows = 2: the forward FFT on side stream 0 (the bands + coefficients of the polynomial rows follow it there), so that
+  // the first overlap-save rows start on the caller's stream as soon as their block spectra exist
+  const bool fft_aside = p->serial_rows >= 2 && serial_schedule(p, p->call.ols_launched != 0);
+  int rc = CWT_OK;
+  {
+    StreamGuard caller(p);
+    if (fft_aside) {
+      if (!p->call.ols_launched) HIPCHECK(hipEventRecord(p->ev_fork, p->stream));
+      HIPCHECK(hipStreamWaitEvent(p->side[0], p->ev_fork, 0));
+      p->stream = p->side[0];
+      p->call.fft_small = p->fft_aside_small;
+    }
+    rc = by_precision(p, [&](auto t) { return fft_rows_impl<decltype(t), IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev); });
+  }
+  p->call.fft_small = 0;
+  if (rc) return rc;
+  if (fft_aside) {
+    HIPCHECK(hipEventRecord(p->ev_a[1], p->side[0]));
+    p->call.spectrum_ready = p->ev_a[1];
+  }
+  return CWT_OK;
+}
+
 
 std::mutex g_pinned_mutex;
 std::map<uintptr_t, size_t> g_pinned;
@@ -255,8 +353,10 @@ int cwt_plan_create(cwt_plan** plan, int device, int64_t nfft, int precision, in
     if (t > 0 && t <= 1e-2) p->tolerance = t;
   }
   if (const char* e = std::getenv("CWT_QUEUE_PROBE")) p->queue_probe = std::atoi(e) != 0;   // (diagnostic: plans the caller does not create itself)
-  int rc = precision == 64 ? build_tables<double>(p) : build_tables<float>(p);
-  if (!rc) rc = precision == 64 ? set_func_attrs<double>() : set_func_attrs<float>();
+  int rc = by_precision(p, [&](auto t) {
+    const int r = build_tables<decltype(t)>(p);
+    return r ? r : set_func_attrs<decltype(t)>();
+  });
   for (int i = 0; i < 2 && !rc; ++i) {
     if (create_side_stream(&p->side[i]) != hipSuccess ||
         order_event(&p->ev_a[i]) != hipSuccess || order_event(&p->ev_b[i]) != hipSuccess)
@@ -304,7 +404,6 @@ int cwt_plan_destroy(cwt_plan* p) {
   if (p->ev_probe) (void)hipEventDestroy(p->ev_probe);
   if (p->probe_dev) (void)hipFree(p->probe_dev);
   if (p->ev_big) (void)hipEventDestroy(p->ev_big);
-  for (auto& g : p->graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (auto& t : p->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   for (auto e : p->free_events) (void)hipEventDestroy(e);
   void* bufs[] = {p->tw_all, p->twn_lo, p->weights_dev, p->Z, p->xs, p->xm, p->xsa, p->pcoef, p->pband, p->range_dev, p->hx, p->hxhat, p->hW,
@@ -338,10 +437,11 @@ int cwt_plan_set_option(cwt_plan* p, const char* key, int64_t value) {
   if (!p || !key) return fail(CWT_EINVAL, "plan/key is NULL");
   const std::string k(key);
   auto pow2 = [](int64_t v) { return v > 0 && (v & (v - 1)) == 0; };
-  for (const char* gone : {"overlap", "pass_b_prefetch", "pass_b_small", "stamps", "ols_tile", "ols_fwd_real", "sched", "narrow_wave"})
+  for (const char* gone : {"overlap", "pass_b_prefetch", "pass_b_small", "stamps", "ols_tile", "ols_fwd_real", "sched", "narrow_wave",
+                           "graph"})
     if (k == gone)
-      return fail(CWT_EINVAL, "option " + k + " belonged to a measured-and-rejected variant or a diagnostic that left the sources in "
-                              "round 4 (EXPERIMENTS.md names the commit that still has it)");
+      return fail(CWT_EINVAL, "option " + k + " belonged to a measured-and-rejected variant or a diagnostic that has left the sources "
+                              "(EXPERIMENTS.md has its measurements)");
   for (auto& t : p->slots) t.key.clear();   // the classification depends on the options
   struct Restore {   // a rejected geometry leaves every geometry-affecting field as it was
     cwt_plan* p; int lmax, wg, logk, nmax;
@@ -366,7 +466,6 @@ int cwt_plan_set_option(cwt_plan* p, const char* key, int64_t value) {
   else if (k == "pass_a_small") p->pass_a_small = value != 0;
   else if (k == "narrow_terms") { if (value < 1 || value > 16) return fail(CWT_EINVAL, "narrow_terms in [1,16]"); p->narrow_terms = int(value); }
   else if (k == "ols") p->ols = value != 0;
-  else if (k == "graph") p->graph = value != 0;
   else if (k == "host_direct") p->host_direct = value != 0;
   else if (k == "aols") p->aols = value != 0;
   else if (k == "aols_zc") p->aols_zc = value != 0;
@@ -429,12 +528,12 @@ int cwt_spectrum_range(cwt_plan* p, const void* xhat_dev, int64_t n, double* max
   // slices of at least 4096 bins, at most two workgroups per CU
   const int groups = int(std::max<int64_t>(1, std::min<int64_t>(kGroupsMax, n / 4096)));
   double* part = p->range_dev + kOut;
-  if (p->prec == 64)
-    hipLaunchKernelGGL((k_spectrum_range<double>), dim3(groups), dim3(256), (256 + kOut + 2) * sizeof(double), p->stream,
-                       static_cast<const double2*>(xhat_dev), long(n), part);
-  else
-    hipLaunchKernelGGL((k_spectrum_range<float>), dim3(groups), dim3(256), (256 + kOut + 2) * sizeof(double), p->stream,
-                       static_cast<const float2*>(xhat_dev), long(n), part);
+  by_precision(p, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_spectrum_range<T>), dim3(groups), dim3(256), (256 + kOut + 2) * sizeof(double), p->stream,
+                       static_cast<const cplx<T>*>(xhat_dev), long(n), part);
+    return CWT_OK;
+  });
   hipLaunchKernelGGL((k_spectrum_fold<0>), dim3(1), dim3(192), 0, p->stream, part, groups, p->range_dev);
   HIPCHECK(hipGetLastError());
   double h[kOut] = {0};
@@ -471,7 +570,7 @@ int cwt_spectrum_range(cwt_plan* p, const void* xhat_dev, int64_t n, double* max
 // a decade of tolerance, not accuracy); a power of sqrt(10) (calls with like spectra share one cached row table), never
 // looser than the target, never below round-off.  A spectrum with an empty stretch or a non-finite bin: round-off.
 static double auto_tolerance_of(const cwt_plan* p, double target, double mx, double fl) {
-  const double round_off = p->prec == 64 ? kDefaultTolerance64 : kDefaultTolerance32;
+  const double round_off = default_tolerance(p);
   double tol = target;
   if (!(fl > 0) || !std::isfinite(mx)) return round_off;
   const double excess = (mx / fl) / 8.0;
@@ -492,7 +591,7 @@ int cwt_plan_auto_tolerance(cwt_plan* p, const void* xhat_dev, double target, do
 
 int cwt_plan_get_tolerance(cwt_plan* p, double* rel_tol) {
   if (!p || !rel_tol) return fail(CWT_EINVAL, "NULL argument");
-  *rel_tol = p->tolerance > 0 ? p->tolerance : (p->prec == 64 ? kDefaultTolerance64 : kDefaultTolerance32);
+  *rel_tol = p->tolerance > 0 ? p->tolerance : default_tolerance(p);
   return CWT_OK;
 }
 
@@ -541,8 +640,7 @@ int cwt_forward_fft(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev) 
   if (!p || !x_dev || !xhat_dev) return fail(CWT_EINVAL, "NULL argument");
   if (n0 < 1 || n0 > p->N) return fail(CWT_EINVAL, "n0 must be in [1, nfft]");
   HIPCHECK(hipSetDevice(p->device));
-  return p->prec == 64 ? fft_rows_impl<double, IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev)
-                       : fft_rows_impl<float, IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev);
+  return by_precision(p, [&](auto t) { return fft_rows_impl<decltype(t), IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev); });
 }
 
 
@@ -551,7 +649,10 @@ int cwt_transform_rows(cwt_plan* p, const void* xhat_dev, int mother, double par
                        const double* scales, int nrows, void* W_dev, int64_t ldw, int64_t ncols) {
   if (!p || !xhat_dev || !scales || !W_dev) return fail(CWT_EINVAL, "NULL argument");
   HIPCHECK(hipSetDevice(p->device));
-  return transform_rows_common(p, xhat_dev, nullptr, 0, mother, param, dt, scales, nrows, W_dev, ldw, ncols);
+  int rc = prepare_rows_table(p, false, mother, param, dt, scales, nrows, ldw, ncols);
+  if (!rc && p->logN >= 18 && !p->profile) rc = ensure_distinct_queues(p);
+  if (rc) return rc;
+  return queue_rows(p, xhat_dev, mother_of(mother, param), nrows, W_dev, ldw, ncols);
 }
 
 int cwt_transform(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double param, double dt,
@@ -570,86 +671,12 @@ int cwt_transform(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double
     xhat_dev = p->hxhat;
   }
   const Mother mo = mother_of(mother, param);
-  auto enqueue = [&]() -> int {
-    p->ols_launched = 0;
-    int r = CWT_OK;
-    if (only_ols)
-      return p->prec == 64 ? rows_impl<double>(p, nullptr, mo, nrows, W_dev, ldw, ncols, x_dev, n0)
-                           : rows_impl<float>(p, nullptr, mo, nrows, W_dev, ldw, ncols, x_dev, n0);
-    if (p->rt->n_ols && p->ols_early && !p->profile) {
-      p->ols_first_on_main = p->serial_rows >= 2 && serial_schedule(p, true) && p->rt->ols_grp[0].nrows > 0;
-      r = p->prec == 64 ? launch_ols_early<double>(p, x_dev, n0, W_dev, ldw, ncols)
-                        : launch_ols_early<float>(p, x_dev, n0, W_dev, ldw, ncols);
-      if (r) return r;
-    }
-    // serial_rows = 2: the forward FFT on side stream 0 (the bands + coefficients of the polynomial rows follow it there), so that
-    // the first overlap-save rows start on the caller's stream as soon as their block spectra exist
-    const bool fft_aside = p->serial_rows >= 2 && serial_schedule(p, p->ols_launched != 0);
-    hipStream_t caller = p->stream;
-    if (fft_aside) {
-      if (!p->ols_launched) HIPCHECK(hipEventRecord(p->ev_fork, caller));
-      HIPCHECK(hipStreamWaitEvent(p->side[0], p->ev_fork, 0));
-      p->stream = p->side[0];
-      p->fft_small = p->fft_aside_small;
-    }
-    r = p->prec == 64 ? fft_rows_impl<double, IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev)
-                      : fft_rows_impl<float, IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev);
-    p->stream = caller;
-    p->fft_small = 0;
-    if (fft_aside && !r) {
-      HIPCHECK(hipEventRecord(p->ev_a[1], p->side[0]));
-      p->spectrum_ready = p->ev_a[1];
-    }
-    if (!r) r = p->prec == 64 ? rows_impl<double>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0)
-                              : rows_impl<float>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0);
-    p->ols_launched = 0;
-    p->ols_first_on_main = 0;
-    p->spectrum_ready = nullptr;
-    return r;
-  };
-  if (!p->graph || p->profile) return enqueue();
-  // Option "graph": the same call (buffers, shapes, row table) for the second time is captured into a HIP graph -- the side
-  // streams join the capture through the events that fork and join them -- and replayed from then on: one launch instead
-  // of 10-20 launches and as many event operations per transform.
-  const std::vector<uint64_t> gkey = {uint64_t(reinterpret_cast<uintptr_t>(x_dev)), uint64_t(n0),
-                                      uint64_t(reinterpret_cast<uintptr_t>(xhat_dev)), uint64_t(reinterpret_cast<uintptr_t>(W_dev)),
-                                      uint64_t(ldw), uint64_t(ncols), uint64_t(reinterpret_cast<uintptr_t>(p->rt)), p->rt->build_id,
-                                      uint64_t(reinterpret_cast<uintptr_t>(p->stream)), g_scratch_gen};
-  cwt_plan::GraphSlot* slot = nullptr;
-  for (auto& g : p->graphs) if (g.key == gkey) slot = &g;
-  if (slot && slot->exec) {
-    slot->used = ++p->tick;
-    ++p->graph_replays;
-    HIPCHECK(hipGraphLaunch(slot->exec, p->stream));
-    return CWT_OK;
-  }
-  if (!slot) {                                            // first occurrence: remember it (least recently used slot), run plainly
-    slot = &p->graphs[0];
-    for (auto& g : p->graphs) if (g.used < slot->used) slot = &g;
-    if (slot->exec) { HIPCHECK(hipStreamSynchronize(p->stream)); (void)hipGraphExecDestroy(slot->exec); slot->exec = nullptr; }
-    slot->key = gkey; slot->seen = 1; slot->used = ++p->tick;
-    return enqueue();
-  }
-  slot->used = ++p->tick;                                 // second occurrence: every buffer has its size, nothing allocates
-  if (hipStreamBeginCapture(p->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    (void)hipGetLastError();
-    p->graph = 0;                                         // no capture on this runtime: plain launches from now on
-    return enqueue();
-  }
-  rc = enqueue();
-  hipGraph_t graph = nullptr;
-  const hipError_t ec = hipStreamEndCapture(p->stream, &graph);
-  if (rc || ec != hipSuccess || !graph) {
-    if (graph) (void)hipGraphDestroy(graph);
-    (void)hipGetLastError();
-    p->graph = 0;
-    return rc ? rc : enqueue();
-  }
-  const hipError_t ei = hipGraphInstantiate(&slot->exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  if (ei != hipSuccess) { slot->exec = nullptr; (void)hipGetLastError(); p->graph = 0; return enqueue(); }
-  HIPCHECK(hipGraphLaunch(slot->exec, p->stream));
-  return CWT_OK;
+  CallScope scope(p);
+  if (!only_ols) rc = queue_spectrum(p, x_dev, n0, xhat_dev);
+  if (rc) return rc;
+  return scope.done(by_precision(p, [&](auto t) {
+    return rows_impl<decltype(t)>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0);
+  }));
 }
 
 int cwt_transform_rows_batch(cwt_plan* p, const void* xhat_dev, int nbatch, int64_t xhat_ld, int mother,
@@ -659,36 +686,17 @@ int cwt_transform_rows_batch(cwt_plan* p, const void* xhat_dev, int nbatch, int6
   if (nbatch < 1 || nrows < 1 || int64_t(nbatch) * nrows > p->max_rows)
     return fail(CWT_EINVAL, "need nbatch*nrows <= max_rows");
   if (xhat_ld < p->N) return fail(CWT_EINVAL, "xhat_ld must be >= nfft");
-  if (ncols < 1 || ncols > p->N || ldw < ncols) return fail(CWT_EINVAL, "need 1 <= ncols <= nfft and ldw >= ncols");
-  if (!(dt > 0) || !std::isfinite(dt)) return fail(CWT_EINVAL, "dt must be positive");
   HIPCHECK(hipSetDevice(p->device));
-  const int total = nbatch * nrows;
-  const std::vector<double> key = call_key(2, {p->tolerance, double(mother), param, dt, double(nbatch), double(xhat_ld), double(nrows)},
-                                           {{scales, nrows}});
-  if (!select_table(p, key)) {
-    double cre, cim;
-    int rc = mother_constant(mother, param, &cre, &cim);
-    if (rc) return rc;
-    const double w1 = 2.0 * 3.14159265358979323846 * (1.0 / (double(p->N) * dt));
-    std::vector<double> a(total), ar(total), ai(total);
-    for (int j = 0; j < total; ++j) {
-      const double s = scales[j % nrows];
-      if (!(s > 0) || !std::isfinite(s)) return fail(CWT_EINVAL, "scales must be positive and finite");
-      a[j] = s * w1;
-      const double norm = std::sqrt(s * w1 * double(p->N));
-      ar[j] = norm * cre;
-      ai[j] = norm * cim;
-    }
-    // W is treated as one (nbatch*nrows) x ldw matrix: row b*nrows + j = scale j of signal b
-    rc = build_row_table(p, mother, param, a.data(), ar.data(), ai.data(), xhat_ld, total, nullptr, nullptr, nrows);
-    if (!rc) rc = upload_row_table(p, key);
-    if (rc) return rc;
-  }
-  set_split(p);
-  Mother mo;
-  mo.kind = mother; mo.m = int(std::lround(param)); mo.p = param; mo.table = nullptr;
-  return p->prec == 64 ? rows_impl<double>(p, xhat_dev, mo, total, W_dev, ldw, ncols)
-                       : rows_impl<float>(p, xhat_dev, mo, total, W_dev, ldw, ncols);
+  // W is treated as one (nbatch*nrows) x ldw matrix: row b*nrows + j = scale j of signal b
+  TableCall c = scale_rows(mother, param, dt, scales, nrows, ldw, ncols);
+  c.kind = 2;
+  c.head = {p->tolerance, double(mother), param, dt, double(nbatch), double(xhat_ld), double(nrows)};
+  c.nbatch = nbatch;
+  c.rows_per_signal = nrows;
+  c.spec_ld = xhat_ld;
+  const int rc = prepare_table(p, c);
+  if (rc) return rc;
+  return queue_rows(p, xhat_dev, mother_of(mother, param), nbatch * nrows, W_dev, ldw, ncols);
 }
 
 int cwt_transform_batch(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother,
@@ -698,64 +706,43 @@ int cwt_transform_batch(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld
   if (nbatch < 1 || nrows < 1 || int64_t(nbatch) * nrows > p->max_rows)
     return fail(CWT_EINVAL, "need nbatch*nrows <= max_rows");
   if (n0 < 1 || n0 > p->N || x_ld < n0) return fail(CWT_EINVAL, "need 1 <= n0 <= nfft and x_ld >= n0");
-  if (ncols < 1 || ncols > p->N || ldw < ncols) return fail(CWT_EINVAL, "need 1 <= ncols <= nfft and ldw >= ncols");
-  if (!(dt > 0) || !std::isfinite(dt)) return fail(CWT_EINVAL, "dt must be positive");
   HIPCHECK(hipSetDevice(p->device));
-  const int total = nbatch * nrows;
-  const std::vector<double> key = call_key(3, {p->tolerance, double(mother), param, dt, double(nbatch), double(nrows), double(ncols)},
-                                           {{scales, nrows}});
-  if (!select_table(p, key)) {
-    double cre, cim;
-    int rc = mother_constant(mother, param, &cre, &cim);
-    if (rc) return rc;
-    const double w1 = 2.0 * 3.14159265358979323846 * (1.0 / (double(p->N) * dt));
-    std::vector<double> a(total), ar(total), ai(total);
-    for (int j = 0; j < total; ++j) {
-      const double s = scales[j % nrows];
-      if (!(s > 0) || !std::isfinite(s)) return fail(CWT_EINVAL, "scales must be positive and finite");
-      a[j] = s * w1;
-      const double norm = std::sqrt(s * w1 * double(p->N));
-      ar[j] = norm * cre;
-      ai[j] = norm * cim;
-    }
-    // as cwt_transform_rows_batch, with the signals at hand: time-compact rows may take the overlap-save form
-    rc = build_row_table(p, mother, param, a.data(), ar.data(), ai.data(), p->N, total, nullptr, nullptr, nrows, -1, ncols, ncols);
-    if (!rc) rc = upload_row_table(p, key);
-    if (!rc && p->rt->n_ols)
-      rc = p->prec == 64 ? fill_ols_tables<double>(p, mother_of(mother, param)) : fill_ols_tables<float>(p, mother_of(mother, param));
-    if (!rc && p->rt->n_aols)
-      rc = p->prec == 64 ? fill_aols_tables<double>(p, mother_of(mother, param)) : fill_aols_tables<float>(p, mother_of(mother, param));
-    if (rc) { p->rt->key.clear(); return rc; }
-  }
-  set_split(p);
-  const Mother mo = mother_of(mother, param);
-  int rc = p->prec == 64 ? fft_rows_impl<double, IN_REAL>(p, x_dev, x_ld, nbatch, n0, xhat_dev)
-                         : fft_rows_impl<float, IN_REAL>(p, x_dev, x_ld, nbatch, n0, xhat_dev);
+  // as cwt_transform_rows_batch, with the signals at hand: time-compact rows may take the overlap-save form
+  TableCall c = scale_rows(mother, param, dt, scales, nrows, ldw, ncols);
+  c.kind = 3;
+  c.head = {p->tolerance, double(mother), param, dt, double(nbatch), double(nrows), double(ncols)};
+  c.nbatch = nbatch;
+  c.rows_per_signal = nrows;
+  c.spec_ld = p->N;
+  c.ols_ncols = ncols;
+  c.out_ncols = ncols;
+  int rc = prepare_table(p, c);
   if (rc) return rc;
-  p->ols_launched = 0;
-  p->ols_x_ld = x_ld;
-  rc = p->prec == 64 ? rows_impl<double>(p, xhat_dev, mo, total, W_dev, ldw, ncols, x_dev, n0)
-                     : rows_impl<float>(p, xhat_dev, mo, total, W_dev, ldw, ncols, x_dev, n0);
-  p->ols_x_ld = 0;
-  return rc;
+  const Mother mo = mother_of(mother, param);
+  CallScope scope(p);
+  rc = by_precision(p, [&](auto t) { return fft_rows_impl<decltype(t), IN_REAL>(p, x_dev, x_ld, nbatch, n0, xhat_dev); });
+  if (rc) return rc;
+  p->call.ols_x_ld = x_ld;
+  return scope.done(by_precision(p, [&](auto t) {
+    return rows_impl<decltype(t)>(p, xhat_dev, mo, nbatch * nrows, W_dev, ldw, ncols, x_dev, n0);
+  }));
 }
 
 int cwt_transform_rows_table(cwt_plan* p, const void* xhat_dev, const void* table_dev, const int* k_lo,
                              const int* nband, int nrows, void* W_dev, int64_t ldw, int64_t ncols) {
   if (!p || !xhat_dev || !table_dev || !k_lo || !nband || !W_dev) return fail(CWT_EINVAL, "NULL argument");
-  if (nrows < 1 || nrows > p->max_rows) return fail(CWT_EINVAL, "nrows must be in [1, max_rows]");
-  if (ncols < 1 || ncols > p->N || ldw < ncols) return fail(CWT_EINVAL, "need 1 <= ncols <= nfft and ldw >= ncols");
   HIPCHECK(hipSetDevice(p->device));
-  select_table(p, {});                                   // explicit filter banks are not cached
-  std::vector<double> one(nrows, 1.0), zero(nrows, 0.0);
-  int rc = build_row_table(p, MOTHER_TABLE, 0.0, one.data(), one.data(), zero.data(), 0, nrows, k_lo, nband);
-  if (!rc) rc = upload_row_table(p, {});
+  TableCall c;                                           // (kind -1: explicit filter banks are not cached)
+  c.nrows = nrows;
+  c.tab_klo = k_lo;
+  c.tab_nband = nband;
+  c.ldw = ldw;
+  c.ncols = ncols;
+  const int rc = prepare_table(p, c);
   if (rc) return rc;
-  set_split(p);
-  Mother mo;
-  mo.kind = MOTHER_TABLE; mo.m = 0; mo.p = 0; mo.table = table_dev;
-  return p->prec == 64 ? rows_impl<double>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols)
-                       : rows_impl<float>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols);
+  Mother mo = mother_of(MOTHER_TABLE, 0.0);
+  mo.table = table_dev;
+  return queue_rows(p, xhat_dev, mo, nrows, W_dev, ldw, ncols);
 }
 
 int cwt_fft_rows(cwt_plan* p, const void* in_dev, int in_complex, int nrows, int64_t in_ld, int64_t ncols_in,
@@ -764,47 +751,43 @@ int cwt_fft_rows(cwt_plan* p, const void* in_dev, int in_complex, int nrows, int
   if (nrows < 1) return fail(CWT_EINVAL, "nrows must be >= 1");
   if (ncols_in < 1 || ncols_in > p->N || in_ld < ncols_in) return fail(CWT_EINVAL, "need 1 <= ncols_in <= nfft and in_ld >= ncols_in");
   HIPCHECK(hipSetDevice(p->device));
-  if (p->prec == 64)
-    return in_complex ? fft_rows_impl<double, IN_CPLX>(p, in_dev, in_ld, nrows, ncols_in, spec_dev)
-                      : fft_rows_impl<double, IN_REAL>(p, in_dev, in_ld, nrows, ncols_in, spec_dev);
-  return in_complex ? fft_rows_impl<float, IN_CPLX>(p, in_dev, in_ld, nrows, ncols_in, spec_dev)
-                    : fft_rows_impl<float, IN_REAL>(p, in_dev, in_ld, nrows, ncols_in, spec_dev);
+  return by_precision(p, [&](auto t) {
+    using T = decltype(t);
+    return in_complex ? fft_rows_impl<T, IN_CPLX>(p, in_dev, in_ld, nrows, ncols_in, spec_dev)
+                      : fft_rows_impl<T, IN_REAL>(p, in_dev, in_ld, nrows, ncols_in, spec_dev);
+  });
 }
 
 int cwt_filter_rows(cwt_plan* p, const void* spec_dev, int64_t spec_ld, int mother, double param,
                     const double* a, const double* amp_re, const double* amp_im, int nrows, void* W_dev,
                     int64_t ldw, int64_t ncols) {
   if (!p || !spec_dev || !a || !amp_re || !amp_im || !W_dev) return fail(CWT_EINVAL, "NULL argument");
-  if (nrows < 1 || nrows > p->max_rows) return fail(CWT_EINVAL, "nrows must be in [1, max_rows]");
-  if (ncols < 1 || ncols > p->N || ldw < ncols) return fail(CWT_EINVAL, "need 1 <= ncols <= nfft and ldw >= ncols");
-  if (spec_ld != 0 && spec_ld < p->N) return fail(CWT_EINVAL, "spec_ld must be 0 (shared) or >= nfft");
   HIPCHECK(hipSetDevice(p->device));
-  const std::vector<double> key = call_key(1, {p->tolerance, double(mother), param, double(spec_ld), double(nrows)},
-                                           {{a, nrows}, {amp_re, nrows}, {amp_im, nrows}});
-  if (!select_table(p, key)) {
-    double cre, cim;
-    int rc = mother_constant(mother, param, &cre, &cim);   // validates mother / order only
-    if (!rc) rc = build_row_table(p, mother, param, a, amp_re, amp_im, spec_ld, nrows);
-    if (!rc) rc = upload_row_table(p, key);
-    if (!rc && p->rt->poly_rtab_elems)                    // polynomial rows: the tables of their economised weights
-      rc = p->prec == 64 ? fill_poly_tables<double>(p) : fill_poly_tables<float>(p);
-    if (rc) { p->rt->key.clear(); return rc; }
-  }
-  set_split(p);
-  Mother mo;
-  mo.kind = mother; mo.m = int(std::lround(param)); mo.p = param; mo.table = nullptr;
-  return p->prec == 64 ? rows_impl<double>(p, spec_dev, mo, nrows, W_dev, ldw, ncols)
-                       : rows_impl<float>(p, spec_dev, mo, nrows, W_dev, ldw, ncols);
+  TableCall c;
+  c.kind = 1;
+  c.head = {p->tolerance, double(mother), param, double(spec_ld), double(nrows)};
+  c.mother = mother;
+  c.param = param;
+  c.nrows = nrows;
+  c.a = a;
+  c.amp_re = amp_re;
+  c.amp_im = amp_im;
+  c.ldw = ldw;
+  c.ncols = ncols;
+  c.spec_ld = spec_ld;
+  const int rc = prepare_table(p, c);
+  if (rc) return rc;
+  return queue_rows(p, spec_dev, mother_of(mother, param), nrows, W_dev, ldw, ncols);
 }
-
 
 int cwt_wct_products(cwt_plan* p, const void* W1_dev, const void* W2_dev, const double* scales, int nrows,
                      int64_t ld, int64_t ncols, void* P_dev, void* C_dev, void* angle_dev) {
   if (!p || !W1_dev || !W2_dev || !scales || !P_dev || !C_dev || !angle_dev) return fail(CWT_EINVAL, "NULL argument");
   if (nrows < 1 || nrows > p->max_rows || ncols < 1 || ld < ncols) return fail(CWT_EINVAL, "bad shape");
   HIPCHECK(hipSetDevice(p->device));
-  return p->prec == 64 ? wct_products_impl<double>(p, W1_dev, W2_dev, scales, nrows, ld, ncols, P_dev, C_dev, angle_dev)
-                       : wct_products_impl<float>(p, W1_dev, W2_dev, scales, nrows, ld, ncols, P_dev, C_dev, angle_dev);
+  return by_precision(p, [&](auto t) {
+    return wct_products_impl<decltype(t)>(p, W1_dev, W2_dev, scales, nrows, ld, ncols, P_dev, C_dev, angle_dev);
+  });
 }
 
 int cwt_cross_spectrum(cwt_plan* p, const void* W1_dev, const void* W2_dev, int nrows, int64_t ld, int64_t ncols,
@@ -813,13 +796,12 @@ int cwt_cross_spectrum(cwt_plan* p, const void* W1_dev, const void* W2_dev, int 
   if (nrows < 1 || nrows > 65535 || ncols < 1 || ld < ncols) return fail(CWT_EINVAL, "bad shape");
   HIPCHECK(hipSetDevice(p->device));
   const dim3 grid(unsigned((ncols + 255) / 256), unsigned(nrows));
-  return timed_launch(p, KC_ELEMENTWISE, [&] {
-    if (p->prec == 64)
-      hipLaunchKernelGGL((k_cross_spectrum<double>), grid, dim3(256), 0, p->stream, static_cast<const double2*>(W1_dev),
-                         static_cast<const double2*>(W2_dev), long(ld), long(ncols), static_cast<double2*>(out_dev));
-    else
-      hipLaunchKernelGGL((k_cross_spectrum<float>), grid, dim3(256), 0, p->stream, static_cast<const float2*>(W1_dev),
-                         static_cast<const float2*>(W2_dev), long(ld), long(ncols), static_cast<float2*>(out_dev));
+  return by_precision(p, [&](auto t) {
+    using T = decltype(t);
+    return timed_launch(p, KC_ELEMENTWISE, [&] {
+      hipLaunchKernelGGL((k_cross_spectrum<T>), grid, dim3(256), 0, p->stream, static_cast<const cplx<T>*>(W1_dev),
+                         static_cast<const cplx<T>*>(W2_dev), long(ld), long(ncols), static_cast<cplx<T>*>(out_dev));
+    });
   });
 }
 
@@ -829,8 +811,7 @@ int cwt_boxcar_scales(cwt_plan* p, const void* in_dev, int nrows, int64_t ld, in
   if (nrows < 1 || ncols < 1 || ld < ncols || nwin < 1 || nwin > p->max_rows) return fail(CWT_EINVAL, "bad shape");
   if (in_dev == out_dev) return fail(CWT_EINVAL, "boxcar cannot run in place");
   HIPCHECK(hipSetDevice(p->device));
-  return p->prec == 64 ? boxcar_impl<double>(p, in_dev, nrows, ld, ncols, win, nwin, out_dev)
-                       : boxcar_impl<float>(p, in_dev, nrows, ld, ncols, win, nwin, out_dev);
+  return by_precision(p, [&](auto t) { return boxcar_impl<decltype(t)>(p, in_dev, nrows, ld, ncols, win, nwin, out_dev); });
 }
 
 int cwt_wct_coherence(cwt_plan* p, const void* S_dev, const void* S12_dev, int nrows, int64_t ld, int64_t ncols,
@@ -838,8 +819,7 @@ int cwt_wct_coherence(cwt_plan* p, const void* S_dev, const void* S12_dev, int n
   if (!p || !S_dev || !S12_dev || !out_dev) return fail(CWT_EINVAL, "NULL argument");
   if (nrows < 1 || ncols < 1 || ld < ncols) return fail(CWT_EINVAL, "bad shape");
   HIPCHECK(hipSetDevice(p->device));
-  return p->prec == 64 ? coherence_impl<double>(p, S_dev, S12_dev, nrows, ld, ncols, out_dev)
-                       : coherence_impl<float>(p, S_dev, S12_dev, nrows, ld, ncols, out_dev);
+  return by_precision(p, [&](auto t) { return coherence_impl<decltype(t)>(p, S_dev, S12_dev, nrows, ld, ncols, out_dev); });
 }
 
 
@@ -849,11 +829,11 @@ int cwt_reduce_scales(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols
   if (nrows < 1 || nrows > p->max_rows) return fail(CWT_EINVAL, "nrows must be in [1, max_rows]");
   if (ncols < 1 || ldw < ncols) return fail(CWT_EINVAL, "need ncols >= 1 and ldw >= ncols");
   HIPCHECK(hipSetDevice(p->device));
-  if (p->prec == 64)
-    return power ? reduce_scales_impl<double, true>(p, W_dev, ldw, ncols, nrows, weights, coeff, out_dev)
-                 : reduce_scales_impl<double, false>(p, W_dev, ldw, ncols, nrows, weights, coeff, out_dev);
-  return power ? reduce_scales_impl<float, true>(p, W_dev, ldw, ncols, nrows, weights, coeff, out_dev)
-               : reduce_scales_impl<float, false>(p, W_dev, ldw, ncols, nrows, weights, coeff, out_dev);
+  return by_precision(p, [&](auto t) {
+    using T = decltype(t);
+    return power ? reduce_scales_impl<T, true>(p, W_dev, ldw, ncols, nrows, weights, coeff, out_dev)
+                 : reduce_scales_impl<T, false>(p, W_dev, ldw, ncols, nrows, weights, coeff, out_dev);
+  });
 }
 
 int cwt_icwt_reduce(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols, int nrows,
@@ -872,14 +852,12 @@ int cwt_time_mean_power(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t nco
   if (!p || !W_dev || !out_dev) return fail(CWT_EINVAL, "NULL argument");
   if (nrows < 1 || ncols < 1 || ldw < ncols) return fail(CWT_EINVAL, "bad shape");
   HIPCHECK(hipSetDevice(p->device));
-  if (p->prec == 64)
+  return by_precision(p, [&](auto t) {
+    using T = decltype(t);
     return timed_launch(p, KC_ICWT, [&] {
-      hipLaunchKernelGGL((k_time_mean<double>), dim3(nrows), dim3(256), 256 * sizeof(double), p->stream,
-                         static_cast<const double2*>(W_dev), long(ldw), long(ncols), static_cast<double*>(out_dev));
+      hipLaunchKernelGGL((k_time_mean<T>), dim3(nrows), dim3(256), 256 * sizeof(double), p->stream,
+                         static_cast<const cplx<T>*>(W_dev), long(ldw), long(ncols), static_cast<T*>(out_dev));
     });
-  return timed_launch(p, KC_ICWT, [&] {
-    hipLaunchKernelGGL((k_time_mean<float>), dim3(nrows), dim3(256), 256 * sizeof(double), p->stream,
-                       static_cast<const float2*>(W_dev), long(ldw), long(ncols), static_cast<float*>(out_dev));
   });
 }
 
@@ -892,15 +870,13 @@ int cwt_coherence_histogram(cwt_plan* p, const void* r2_dev, int64_t ld, int nro
   static_assert(sizeof(long) == sizeof(int64_t) && sizeof(unsigned long long) == sizeof(uint64_t), "LP64 expected");
   const unsigned gx = unsigned(std::min<int64_t>(512, (max_span + 4095) / 4096));   // >= 16 columns per thread
   const size_t lds = size_t(nbins) * sizeof(unsigned);
-  return timed_launch(p, KC_ELEMENTWISE, [&] {
-    if (p->prec == 64)
-      hipLaunchKernelGGL((k_coherence_hist<double>), dim3(gx, nrows), dim3(256), lds, p->stream,
-                         static_cast<const double*>(r2_dev), long(ld), reinterpret_cast<const long*>(lo_dev),
+  return by_precision(p, [&](auto t) {
+    using T = decltype(t);
+    return timed_launch(p, KC_ELEMENTWISE, [&] {
+      hipLaunchKernelGGL((k_coherence_hist<T>), dim3(gx, nrows), dim3(256), lds, p->stream,
+                         static_cast<const T*>(r2_dev), long(ld), reinterpret_cast<const long*>(lo_dev),
                          reinterpret_cast<const long*>(hi_dev), nbins, reinterpret_cast<unsigned long long*>(hist_dev));
-    else
-      hipLaunchKernelGGL((k_coherence_hist<float>), dim3(gx, nrows), dim3(256), lds, p->stream,
-                         static_cast<const float*>(r2_dev), long(ld), reinterpret_cast<const long*>(lo_dev),
-                         reinterpret_cast<const long*>(hi_dev), nbins, reinterpret_cast<unsigned long long*>(hist_dev));
+    });
   });
 }
 
@@ -909,8 +885,7 @@ int cwt_random_normal(cwt_plan* p, uint64_t seed, uint64_t offset, int64_t n, do
   if (!p || !out_dev) return fail(CWT_EINVAL, "NULL argument");
   if (n < 1) return fail(CWT_EINVAL, "n must be >= 1");
   HIPCHECK(hipSetDevice(p->device));
-  return p->prec == 64 ? random_normal_impl<double>(p, seed, offset, n, scale, out_dev)
-                       : random_normal_impl<float>(p, seed, offset, n, scale, out_dev);
+  return by_precision(p, [&](auto t) { return random_normal_impl<decltype(t)>(p, seed, offset, n, scale, out_dev); });
 }
 
 int cwt_ar1_filter(cwt_plan* p, const void* e_dev, int64_t tau, int64_t n, double g, void* out_dev) {
@@ -919,13 +894,13 @@ int cwt_ar1_filter(cwt_plan* p, const void* e_dev, int64_t tau, int64_t n, doubl
   if (!(std::fabs(g) < 1.0)) return fail(CWT_EINVAL, "the AR(1) coefficient must be inside (-1, 1)");
   if (e_dev == out_dev) return fail(CWT_EINVAL, "the filter cannot run in place");
   HIPCHECK(hipSetDevice(p->device));
-  return p->prec == 64 ? ar1_filter_impl<double>(p, e_dev, tau, n, g, out_dev) : ar1_filter_impl<float>(p, e_dev, tau, n, g, out_dev);
+  return by_precision(p, [&](auto t) { return ar1_filter_impl<decltype(t)>(p, e_dev, tau, n, g, out_dev); });
 }
 
 int cwt_forward_fft_n(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev) {
   if (!p || !x_dev || !xhat_dev) return fail(CWT_EINVAL, "NULL argument");
   HIPCHECK(hipSetDevice(p->device));
-  return p->prec == 64 ? forward_fft_n_impl<double>(p, x_dev, n0, xhat_dev) : forward_fft_n_impl<float>(p, x_dev, n0, xhat_dev);
+  return by_precision(p, [&](auto t) { return forward_fft_n_impl<decltype(t)>(p, x_dev, n0, xhat_dev); });
 }
 
 int cwt_transform_rows_n(cwt_plan* p, const void* xhat_dev, int64_t n0, int mother, double param, double dt,
@@ -936,8 +911,18 @@ int cwt_transform_rows_n(cwt_plan* p, const void* xhat_dev, int64_t n0, int moth
   if (!(dt > 0) || !std::isfinite(dt)) return fail(CWT_EINVAL, "dt must be positive");
   if (mother < MOTHER_MORLET || mother > MOTHER_DOG) return fail(CWT_EINVAL, "unknown mother id");
   HIPCHECK(hipSetDevice(p->device));
-  return p->prec == 64 ? transform_rows_n_impl<double>(p, xhat_dev, n0, mother, param, dt, scales, nrows, W_dev, ldw)
-                       : transform_rows_n_impl<float>(p, xhat_dev, n0, mother, param, dt, scales, nrows, W_dev, ldw);
+  return by_precision(p, [&](auto t) {
+    return transform_rows_n_impl<decltype(t)>(p, xhat_dev, n0, mother, param, dt, scales, nrows, W_dev, ldw);
+  });
+}
+
+// The plan's page-locked staging buffer of cwt_execute_host (allocated on first use)
+constexpr size_t kHostStage = size_t(4) << 20;
+static int ensure_hstage(cwt_plan* p) {
+  if (p->hstage_bytes >= kHostStage) return CWT_OK;
+  if (hipHostMalloc(&p->hstage, kHostStage) != hipSuccess) return fail(CWT_ENOMEM, "pinned staging allocation failed");
+  p->hstage_bytes = kHostStage;
+  return CWT_OK;
 }
 
 // Page-locked host buffers handed out by cwt_host_malloc (start -> bytes): cwt_execute_host lets the kernels of a short
@@ -980,16 +965,11 @@ int cwt_execute_host(cwt_plan* p, const void* x_host, int64_t n0, int mother, do
     const size_t in_b = (size_t(n0) * es + 255) & ~size_t(255), xh_b = size_t(p->N) * 2 * es;
     const size_t w_b = size_t(nrows) * size_t(n0) * 2 * es;
     const bool w_direct = is_pinned(W_host, w_b);
-    if (in_b + xh_b + (w_direct ? 0 : w_b) <= (size_t(4) << 20)) {
-      if (p->hstage_bytes < (size_t(4) << 20)) {
-        if (hipHostMalloc(&p->hstage, size_t(4) << 20) != hipSuccess) return fail(CWT_ENOMEM, "pinned staging allocation failed");
-        p->hstage_bytes = size_t(4) << 20;
-      }
-      if (p->auto_target > 0) {                            // (round-off costs such transforms nothing: no need to look)
-        const double floor_tol = p->prec == 64 ? kDefaultTolerance64 : kDefaultTolerance32;
-        p->tolerance = floor_tol;
-      }
-      int rc = grow(&p->hxhat, &p->hxhat_bytes, xh_b, p->stream);
+    if (in_b + xh_b + (w_direct ? 0 : w_b) <= kHostStage) {
+      int rc = ensure_hstage(p);
+      if (rc) return rc;
+      if (p->auto_target > 0) p->tolerance = default_tolerance(p);   // (round-off costs such transforms nothing: no need to look)
+      rc = grow(&p->hxhat, &p->hxhat_bytes, xh_b, p->stream);
       if (rc) return rc;
       char* stage = static_cast<char*>(p->hstage);
       std::memcpy(stage, x_host, size_t(n0) * es);
@@ -1012,13 +992,11 @@ int cwt_execute_host(cwt_plan* p, const void* x_host, int64_t n0, int mother, do
   // plan instead -- memcpy in, three asynchronous copies, one synchronisation, memcpy out.
   const size_t in_b = size_t(n0) * es, xh_b = xhat_host ? size_t(p->N) * 2 * es : 0;
   const size_t w_b = W_host ? size_t(nrows) * size_t(n0) * 2 * es : 0;
-  const bool staged = in_b + xh_b + w_b <= (size_t(4) << 20);
+  const bool staged = in_b + xh_b + w_b <= kHostStage;
   char* stage = nullptr;
   if (staged) {
-    if (p->hstage_bytes < (size_t(4) << 20)) {
-      if (hipHostMalloc(&p->hstage, size_t(4) << 20) != hipSuccess) return fail(CWT_ENOMEM, "pinned staging allocation failed");
-      p->hstage_bytes = size_t(4) << 20;
-    }
+    rc = ensure_hstage(p);
+    if (rc) return rc;
     stage = static_cast<char*>(p->hstage);
     std::memcpy(stage, x_host, in_b);
     HIPCHECK(hipMemcpyAsync(p->hx, stage, in_b, hipMemcpyHostToDevice, p->stream));
@@ -1027,8 +1005,7 @@ int cwt_execute_host(cwt_plan* p, const void* x_host, int64_t n0, int mother, do
   }
   if (W_host && p->auto_target > 0 && p->logN <= p->loglmax) {
     // single-workgroup transforms compute every bin of every row anyway: round-off costs nothing, no need to look
-    const double floor_tol = p->prec == 64 ? kDefaultTolerance64 : kDefaultTolerance32;
-    p->tolerance = floor_tol;
+    p->tolerance = default_tolerance(p);
   } else if (W_host && p->auto_target > 0) {
     // accuracy target of THIS call = auto_target / (dynamic range of its spectrum relative to white noise), a power of
     // ten (so that calls with like spectra share one cached row table), never looser than the target itself

@@ -187,7 +187,7 @@ void launch_pass_a_ct(cwt_plan* p, const void* in, const RowDesc* rows, int cnt,
     }
   }
   if constexpr (MODE == IN_REAL && LOGR <= LOGP - 1 && LOGR >= 8) {
-    if (p->fft_small) {      // the forward FFT beside the overlap-save rows (serial_rows = 2): half-size tiles get their turn on the CUs
+    if (p->call.fft_small) { // the forward FFT beside the overlap-save rows (serial_rows = 2): half-size tiles get their turn on the CUs
       constexpr int LP = LOGP - 1;
       hipLaunchKernelGGL((k_pass_a_ct<T, LOGR, LP, MODE>), dim3(1u << (p->logN - LP), cnt), dim3(1 << (LP - 4)),
                          (size_t(1) << LP) * sizeof(T), st, in, rows, mo, tw_table<T>(p, LOGR), twn_of<T>(p), p->logN, n0, in_ld, Z);
@@ -256,7 +256,7 @@ void launch_pass_b_ct(cwt_plan* p, const RowDesc* rows, int cnt, cplx<T>* W, int
                       const cplx<T>* Z, hipStream_t st) {
   constexpr int LOGP = default_logp<T>();
   if constexpr (CONJ && LOGK <= LOGP - 1) {
-    if (p->fft_small) return launch_pass_b_ct_lp<T, LOGK, LOGP - 1, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st);
+    if (p->call.fft_small) return launch_pass_b_ct_lp<T, LOGK, LOGP - 1, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st);
   }
   launch_pass_b_ct_lp<T, LOGK, LOGP, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st);
 }
@@ -345,7 +345,7 @@ int launch_ols_fwd_r(cwt_plan* p, const void* x_dev, int64_t n0, long blocks, co
     hipLaunchKernelGGL((k_ols_fwd_r<T, LOGM>), dim3(unsigned(blocks), unsigned(p->rt->ols_nbatch)), dim3(1 << (LOGM - 4)),
                        lds, st, static_cast<const T*>(x_dev), long(n0), p->logN, cls,
                        static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p), static_cast<cplx<T>*>(p->xs),
-                       long(p->ols_x_ld), p->rt->ols_xs_sig);
+                       long(p->call.ols_x_ld), p->rt->ols_xs_sig);
   }, st);
 }
 // (g_only / d_only >= 0: only that tile group / only its blocks of 2^d tiles; d_only = -2: every block length but one tile)
@@ -649,9 +649,9 @@ int rows_launch_serial(cwt_plan* p, const void* xhat_dev, const Mother& mo, void
     rc = launch_aols<T>(p, xhat_dev, W, ldw, ncols, S1, M, p->ev_b[1], 1);
     if (rc) return rc;
   }
-  const bool g0_split = p->ols_first_on_main && rt->ols_grp[0].wgs > rt->ols_grp[0].wgs_base;   // longer blocks on the half-size tiles:
+  const bool g0_split = p->call.ols_first_on_main && rt->ols_grp[0].wgs > rt->ols_grp[0].wgs_base;   // longer blocks on the half-size tiles:
   if (rt->n_ols) {                                        // block spectra queued by cwt_transform on side stream 1
-    if (!p->ols_first_on_main) HIPCHECK(hipStreamWaitEvent(M, p->ev_b[0], 0));
+    if (!p->call.ols_first_on_main) HIPCHECK(hipStreamWaitEvent(M, p->ev_b[0], 0));
     rc = launch_ols_rows<T>(p, W, ldw, ncols, M, 0, g0_split ? 0 : -1);   // their spectra come from side stream 1, behind ev_ols
     if (rc) return rc;
   }
@@ -704,29 +704,32 @@ struct StreamGuard {
   ~StreamGuard() { p->stream = keep; }
 };
 
-template <typename T>
-int rows_launch(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw,
-                int64_t ncols, const void* x_dev, int64_t n0);
+// One call that queues rows (cwt_transform, cwt_transform_batch and every other way into rows_impl).  When it is left, on
+// any path, the per-call state p->call is cleared and the plan's stream restored; unless the call reported success through
+// done(), the side streams are drained first, so that no kernel forked to them still reads the row table, the block spectra
+// or the filter tables when the caller (or the next call) frees or rebuilds them.
+struct CallScope {
+  cwt_plan* p;
+  hipStream_t keep;
+  bool ok = false;
+  explicit CallScope(cwt_plan* plan) : p(plan), keep(plan->stream) {}
+  int done(int rc) { ok = rc == CWT_OK; return rc; }
+  ~CallScope() {
+    if (!ok) {
+      const std::string msg = g_err;                       // the drain below must not overwrite the message
+      for (hipStream_t s : {p->side[0], p->side[1], p->side2}) if (s) (void)hipStreamSynchronize(s);
+      (void)hipGetLastError();
+      g_err = msg;
+    }
+    p->call = {};
+    p->stream = keep;
+  }
+};
 
-// Queues every row of the current row table.  On an error after work was forked to the side streams the side streams
-// are drained before returning, so that no kernel still reads the row table, the block spectra or the filter tables when
-// the caller (or the next call) frees or rebuilds them.
+// Queues every row of the current row table (inside a CallScope).
 template <typename T>
 int rows_impl(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw,
               int64_t ncols, const void* x_dev = nullptr, int64_t n0 = 0) {
-  const int rc = rows_launch<T>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0);
-  if (rc) {
-    const std::string msg = g_err;                       // the drain below must not overwrite the message
-    for (hipStream_t s : {p->side[0], p->side[1], p->side2}) if (s) (void)hipStreamSynchronize(s);
-    (void)hipGetLastError();
-    g_err = msg;
-  }
-  return rc;
-}
-
-template <typename T>
-int rows_launch(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw,
-                int64_t ncols, const void* x_dev, int64_t n0) {
   const int logN = p->logN;
   const cplx<T>* xhat = static_cast<const cplx<T>*>(xhat_dev);
   cplx<T>* W = static_cast<cplx<T>*>(W_dev);
@@ -760,14 +763,14 @@ int rows_launch(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, 
   const bool side_narrow = p->overlap_narrow && !p->profile && (p->rt->n_wide || p->rt->n_ols || p->rt->n_aols) &&
                            (p->rt->n_narrow || p->rt->n_poly) && logN >= 18;
   // block spectra of the overlap-save rows: beside the two-pass chain on side stream 1 (they only need the signal)
-  const bool ols_early = p->rt->n_ols && p->ols_launched;       // already queued on side stream 1 by cwt_transform
+  const bool ols_early = p->rt->n_ols && p->call.ols_launched;  // already queued on side stream 1 by cwt_transform
   const bool ols_side = p->rt->n_ols && !ols_early && p->ols_side && !p->profile && p->rt->n_wide;
   if (p->rt->n_ols && !ols_early) {
     rc = grow(&p->xs, &p->xs_bytes, size_t(p->rt->ols_xs_elems) * sizeof(cplx<T>), p->stream);
     if (rc) return rc;
   }
   if (serial_schedule(p, ols_early))
-    return rows_launch_serial<T>(p, xhat_dev, mo, W_dev, ldw, ncols, p->spectrum_ready);
+    return rows_launch_serial<T>(p, xhat_dev, mo, W_dev, ldw, ncols, p->call.spectrum_ready);
   if (side_narrow || ols_side) HIPCHECK(hipEventRecord(p->ev_fork, p->stream));
   if (side_narrow) HIPCHECK(hipStreamWaitEvent(p->side[0], p->ev_fork, 0));   // starts after the spectrum exists
   if (ols_side) {
@@ -966,12 +969,12 @@ int fill_poly_tables(cwt_plan* p) {
 }
 
 template <typename T>
-int launch_ols_early(cwt_plan* p, const void* x_dev, int64_t n0, void* W_dev, int64_t ldw, int64_t ncols) {
+int launch_ols_early(cwt_plan* p, const void* x_dev, int64_t n0) {
   int rc = grow(&p->xs, &p->xs_bytes, size_t(p->rt->ols_xs_elems) * sizeof(cplx<T>), p->stream);
   if (rc) return rc;
   HIPCHECK(hipEventRecord(p->ev_fork, p->stream));        // after the previous call's work and the row-table upload
   HIPCHECK(hipStreamWaitEvent(p->side[1], p->ev_fork, 0));
-  if (p->ols_first_on_main) {                           // serial_rows = 2: the first rows' spectra where the rows will follow
+  if (p->call.ols_first_on_main) {                      // serial_rows = 2: the first rows' spectra where the rows will follow
     rc = launch_ols_fwd<T>(p, x_dev, n0, p->stream, nullptr, 0, 0);
     if (!rc) rc = launch_ols_fwd<T>(p, x_dev, n0, p->side[1], nullptr, 0, -2);    // (the half-size tiles' longer blocks)
     if (!rc) rc = launch_ols_fwd<T>(p, x_dev, n0, p->side[1], nullptr, 1);
@@ -980,8 +983,6 @@ int launch_ols_early(cwt_plan* p, const void* x_dev, int64_t n0, void* W_dev, in
   }
   if (rc) return rc;
   HIPCHECK(hipEventRecord(p->ev_ols, p->side[1]));      // serial schedule: all block spectra exist (the other one records it again behind the rows)
-  (void)W_dev; (void)ldw; (void)ncols;
-  p->ols_launched = 1;
   return CWT_OK;
 }
 
@@ -1090,9 +1091,10 @@ int bluestein_convolve(cwt_plan* p, const void* spec, int nrows, int which, void
   if (!rc) rc = upload_row_table(p, {});
   if (rc) return rc;
   set_split(p);
-  Mother mo;
-  mo.kind = MOTHER_TABLE; mo.m = 0; mo.p = 0; mo.table = p->bs_khat[which];
-  return rows_impl<T>(p, spec, mo, nrows, out, ldo, n0);
+  Mother mo = mother_of(MOTHER_TABLE, 0.0);
+  mo.table = p->bs_khat[which];
+  CallScope scope(p);
+  return scope.done(rows_impl<T>(p, spec, mo, nrows, out, ldo, n0));
 }
 
 template <typename T>
@@ -1141,8 +1143,7 @@ int transform_rows_n_impl(cwt_plan* p, const void* xhat_dev, int64_t n0, int mot
   rc = grow(&p->bs_a, &p->bs_a_bytes, std::max(size_t(p->N), size_t(slab) * size_t(n0)) * sizeof(cplx<T>), p->stream);
   if (!rc) rc = grow(&p->bs_spec, &p->bs_spec_bytes, size_t(slab) * size_t(p->N) * sizeof(cplx<T>), p->stream);
   if (rc) return rc;
-  Mother mo;
-  mo.kind = mother; mo.m = int(std::lround(param)); mo.p = param; mo.table = nullptr;
+  const Mother mo = mother_of(mother, param);
   for (int first = 0; first < nrows; first += slab) {
     const int cnt = std::min(slab, nrows - first);
     const dim3 grid(unsigned((n0 + 255) / 256), unsigned(cnt));
@@ -1194,7 +1195,7 @@ int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g
   X int fill_ols_tables<T>(cwt_plan*, const Mother&);                                                                               \
   X int fill_aols_tables<T>(cwt_plan*, const Mother&);                                                                              \
   X int fill_poly_tables<T>(cwt_plan*);                                                                                             \
-  X int launch_ols_early<T>(cwt_plan*, const void*, int64_t, void*, int64_t, int64_t);                                              \
+  X int launch_ols_early<T>(cwt_plan*, const void*, int64_t);                                                                       \
   X int wct_products_impl<T>(cwt_plan*, const void*, const void*, const double*, int, int64_t, int64_t, void*, void*, void*);       \
   X int boxcar_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, const double*, int, void*);                                   \
   X int coherence_impl<T>(cwt_plan*, const void*, const void*, int, int64_t, int64_t, void*);                                       \

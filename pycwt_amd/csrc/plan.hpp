@@ -34,9 +34,6 @@ namespace cwtd {
 using namespace cwt;
 
 extern thread_local std::string g_err;
-// bumped whenever a plan scratch buffer is freed and reallocated (grow, ensure_z): part of the key of a captured HIP graph,
-// whose kernels have those pointers baked in (option "graph")
-extern uint64_t g_scratch_gen;
 int fail(int code, const std::string& msg);
 
 #define HIPCHECK(expr)                                                                        \
@@ -67,6 +64,16 @@ struct cwt_plan {
   int prec = 64;
   int max_rows = 0;
   hipStream_t stream = nullptr;
+  // State of the one cwt_transform / cwt_transform_batch in progress, read by the launches of launch_impl.hpp.  Written only
+  // inside that call's CallScope (launch_impl.hpp), which clears it again on every way out.
+  struct Call {
+    hipEvent_t spectrum_ready = nullptr;   // recorded behind the forward FFT when that ran on side stream 0
+    int fft_small = 0;                     // the forward FFT being queued on side stream 0 (serial_rows = 2) takes half-size tiles
+    int ols_launched = 0;                  // the block spectra of the overlap-save rows are queued already (launch_ols_early)
+    int ols_first_on_main = 0;             // serial_rows = 2: ... those of the half-size tiles on the caller's stream
+    int64_t ols_x_ld = 0;                  // cwt_transform_batch: elements between the signals of the batch
+  };
+  Call call;
   // options
   int chunk_rows = 0;      // rows per two-pass chunk; 0 = as many as fit 192 MiB of intermediate, which
                            // stays inside the 256 MiB Infinity Cache (12 rows at N = 2^20 fp64)
@@ -102,8 +109,6 @@ struct cwt_plan {
   int coef_small = 0;      // interval coefficients of every K' in one launch of 256-thread workgroups (K' = 8192 / 16384 split in 2 / 4); measured slower (EXPERIMENTS R6.2)
   int poly_chunk_mb = 96;  // coefficient planes computed and consumed per chunk of polynomial rows (MiB; 0 = all rows at once)
   int host_direct = 1;     // cwt_execute_host, transforms that fit one workgroup: the kernels read the signal from / write W into page-locked host memory
-  int graph = 0;           // cwt_transform: capture the launches of a repeated call (same buffers, same row table) into a
-                           // HIP graph on its second occurrence and replay it from the third on
   int aols = 1;            // rows clipped at Nyquist as overlap-save rows on the band-passed complex signal (k_aols_*)
   int aols_zc = 1;         // Paul rows not clipped at Nyquist on the band-passed signal too, their profile continued through f = 0
   int aols_long = 1;       // complex128: clipped rows with halos of 512 ... 2048 samples in the second (8192-point) class of the band-passed rows
@@ -113,13 +118,8 @@ struct cwt_plan {
                            // caller's stream (its rows follow at a kernel boundary) and the forward FFT on side stream 0
   int serial_s1_once = 1;  // serial schedule: the caller's stream waits ONCE for side stream 1 (block spectra of the longer blocks, band-passed signal
                            // and its block spectra: one in-order chain) instead of once per consumer
-  hipEvent_t spectrum_ready = nullptr;   // (transient) set by cwt_transform when the forward FFT ran on side stream 0
   int fft_aside_small = 1; // serial_rows = 2: the forward FFT (on side stream 0 beside the first overlap-save rows) on half-size tiles
   int aols_small_b = 1;    // serial schedule, complex128: the band-passed signal's second pass on 4096-point tiles (256-thread workgroups)
-  int fft_small = 0;       // (transient) set by cwt_transform while the forward FFT is queued on side stream 0 (serial_rows = 2)
-  int ols_launched = 0;    // (transient) set by cwt_transform for rows_impl
-  int ols_first_on_main = 0;   // (transient) serial_rows = 2: the block spectra of the half-size tiles were queued on the caller's stream
-  int64_t ols_x_ld = 0;    // (transient) set by cwt_transform_batch: elements between the signals of the batch
   int ols_min_logn = 18;   // shortest transform that takes the form (measured: 2^18 +12 %, 2^17 -10 %, 2^16 -13 %)
   int ols_small_max_halo = 512;   // rows with a halo up to this many samples run on half-size tiles (0 = none)
   int ols_small_big = 1;   // half-size tiles: rows with a halo in (ols_small_max_halo, 1024] and a block support <= 1/8 tile
@@ -225,7 +225,6 @@ struct cwt_plan {
     cwt::RowDesc* rows_pinned = nullptr;
     hipEvent_t uploaded = nullptr;
     uint64_t used = 0;
-    uint64_t build_id = 0;               // changes whenever the table is rebuilt (graphs captured over it are stale then)
   };
   RowTable slots[4];
   RowTable* rt = &slots[0];
@@ -239,10 +238,6 @@ struct cwt_plan {
   void* bs_a = nullptr; size_t bs_a_bytes = 0;          // chirp-premultiplied rows, slab x n0
   void* bs_spec = nullptr; size_t bs_spec_bytes = 0;    // their spectra, slab x M
   void* bs_par = nullptr; size_t bs_par_bytes = 0;      // per-row a, amp_re, amp_im (doubles)
-  // HIP graphs of repeated cwt_transform calls (option "graph"): key = the call's buffers + the row table's identity
-  struct GraphSlot { std::vector<uint64_t> key; hipGraphExec_t exec = nullptr; int seen = 0; uint64_t used = 0; };
-  GraphSlot graphs[4];
-  uint64_t graph_replays = 0;
   std::vector<cwtd::Timed> timed;
   std::vector<hipEvent_t> free_events;
   hipStream_t side[2] = {nullptr, nullptr};       // side streams of the two-pass pipeline
@@ -272,6 +267,7 @@ namespace cwtd {
 // signal's spectrum; a caller that knows its spectra (bench.py: white noise) or measures them (cwt_spectrum_range; the
 // automatic mode of cwt_execute_host, cwt_plan_set_auto_tolerance) passes a looser target and gets the faster forms.
 constexpr double kDefaultTolerance64 = 1e-16, kDefaultTolerance32 = 1e-8;
+inline double default_tolerance(const cwt_plan* p) { return p->prec == 64 ? kDefaultTolerance64 : kDefaultTolerance32; }
 // The truncations that make the fast forms possible, all derived from the one accuracy target tol of the plan:
 //   support  bins whose profile is below this fraction of its peak are treated as exactly zero (band limiting);
 //   halo     neglected fraction of the L1 mass of |psi| beyond the overlap-save halo (a bound on the relative error);

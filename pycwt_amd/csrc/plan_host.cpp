@@ -8,7 +8,6 @@
 namespace cwtd {
 
 thread_local std::string g_err;
-uint64_t g_scratch_gen = 0;
 
 int fail(int code, const std::string& msg) {
   g_err = msg;
@@ -1263,7 +1262,6 @@ int check_geometry(const cwt_plan* p) {
 int ensure_z(cwt_plan* p, int rows) {
   const size_t need = size_t(rows) * size_t(p->N) * 2 * p->esize();
   if (p->z_bytes >= need) return CWT_OK;
-  ++g_scratch_gen;
   if (p->Z) { HIPCHECK(hipStreamSynchronize(p->stream)); HIPCHECK(hipFree(p->Z)); p->Z = nullptr; p->z_bytes = 0; }
   if (hipMalloc(&p->Z, need) != hipSuccess) return fail(CWT_ENOMEM, "cannot allocate two-pass workspace");
   p->z_bytes = need;
@@ -1317,7 +1315,6 @@ hipError_t create_side_stream(hipStream_t* s) { return hipStreamCreateWithFlags(
 
 int grow(void** buf, size_t* have, size_t need, hipStream_t s) {
   if (*have >= need) return CWT_OK;
-  ++g_scratch_gen;
   if (*buf) { HIPCHECK(hipStreamSynchronize(s)); HIPCHECK(hipFree(*buf)); *buf = nullptr; *have = 0; }
   if (hipMalloc(buf, need) != hipSuccess) return fail(CWT_ENOMEM, "device allocation failed");
   *have = need;
@@ -1354,7 +1351,6 @@ int upload_row_table(cwt_plan* p, const std::vector<double>& key) {
                           p->stream));
   HIPCHECK(hipEventRecord(t->uploaded, p->stream));
   t->key = key;
-  t->build_id = ++p->tick;
   return CWT_OK;
 }
 

@@ -130,15 +130,3 @@ static inline hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t a, i
 }
 template <typename F>
 static inline hipError_t hipFuncSetAttribute(F, hipFuncAttribute, int) { return hipSuccess; }
-// graphs: not emulated -- capture is refused, the library then keeps launching plainly
-typedef struct hipemuGraph* hipGraph_t;
-typedef struct hipemuGraphExec* hipGraphExec_t;
-enum hipStreamCaptureStatus { hipStreamCaptureStatusNone = 0, hipStreamCaptureStatusActive, hipStreamCaptureStatusInvalidated };
-static inline hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus* s) { *s = hipStreamCaptureStatusNone; return hipSuccess; }
-enum hipStreamCaptureMode { hipStreamCaptureModeGlobal, hipStreamCaptureModeThreadLocal, hipStreamCaptureModeRelaxed };
-static inline hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipErrorInvalidValue; }
-static inline hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t* g) { *g = nullptr; return hipErrorInvalidValue; }
-static inline hipError_t hipGraphInstantiate(hipGraphExec_t* e, hipGraph_t, void*, void*, size_t) { *e = nullptr; return hipErrorInvalidValue; }
-static inline hipError_t hipGraphDestroy(hipGraph_t) { return hipSuccess; }
-static inline hipError_t hipGraphExecDestroy(hipGraphExec_t) { return hipSuccess; }
-static inline hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { return hipErrorInvalidValue; }

@@ -183,12 +183,38 @@ def test_k2048_single_pass_rows(emu_library, kind, param):
 
 
 def test_lab_only_options_are_refused_by_the_product_sources(emu_library):
-    """The options of the measured-and-rejected variants and diagnostics of rounds 1-3 (EXPERIMENTS.md) are refused by name:
-    that code left the sources in round 4."""
+    """The options of measured-and-rejected variants and diagnostics that have left the sources (EXPERIMENTS.md has their
+    measurements) are refused by name: those of rounds 1-3, which left in round 4, and "graph" (HIP graph replay)."""
     plan = _hip.Plan(1 << 12, 64, max_rows=4, lib=emu_library)
-    for key in ("overlap", "pass_b_prefetch", "pass_b_small", "stamps", "ols_tile", "ols_fwd_real", "sched", "narrow_wave"):
+    for key in ("overlap", "pass_b_prefetch", "pass_b_small", "stamps", "ols_tile", "ols_fwd_real", "sched", "narrow_wave", "graph"):
         with pytest.raises(_hip.HipError, match="EXPERIMENTS.md"):
             plan.set_option(key, 1)
+    plan.close()
+
+
+def test_mother_table_id_is_refused_where_the_rows_come_from_scales_or_filter_parameters(emu_library):
+    """MOTHER_TABLE (3) names a filter bank of the caller's and is only taken by cwt_transform_rows_table: every entry point whose
+    rows come from a mother wavelet refuses it before it builds a row table (which would have no table to read)."""
+    N, rows = 1 << 12, 4
+    plan = _hip.Plan(N, 64, max_rows=2 * rows, lib=emu_library)
+    x = _hip.DeviceBuffer(2 * 8 * N, lib=emu_library)
+    xhat = _hip.DeviceBuffer(2 * 2 * 8 * N, lib=emu_library)
+    W = _hip.DeviceBuffer(2 * rows * 2 * 8 * N, lib=emu_library)
+    x.upload(plan, np.zeros(2 * N))
+    scales = np.geomspace(2.0, 200.0, rows)
+    calls = {
+        "transform_rows": lambda: plan.transform_rows(xhat.ptr, 3, 0.0, 1.0, scales, W.ptr, N, N),
+        "transform": lambda: plan.transform(x.ptr, N, 3, 0.0, 1.0, scales, xhat.ptr, W.ptr, N, N),
+        "filter_rows": lambda: plan.filter_rows(xhat.ptr, 0, 3, 0.0, scales * (2 * np.pi / N), 1.0, W.ptr, N, N),
+        "transform_rows_batch": lambda: plan.transform_rows_batch(xhat.ptr, 2, N, 3, 0.0, 1.0, scales, W.ptr, N, N),
+        "transform_batch": lambda: plan.transform_batch(x.ptr, 2, N, N, 3, 0.0, 1.0, scales, xhat.ptr, W.ptr, N, N),
+        "classify": lambda: plan.classify(3, 0.0, 1.0, scales, N),
+    }
+    for name, call in calls.items():
+        with pytest.raises(_hip.HipError, match="unknown mother id"):
+            call()
+    plan.transform_rows(xhat.ptr, _hip.MORLET, 6.0, 1.0, scales, W.ptr, N, N)      # the plan is still usable
+    plan.sync()
     plan.close()
 
 
