@@ -21,20 +21,11 @@ int by_precision(const cwt_plan* p, F&& f) {
 struct TableCall {
   int kind = -1;                          // cache key kind: 0 ... 3, one per kind of entry point (none shares another's tables);
   std::vector<double> head;               // -1 = never cached; head: the key's values after the kind
-  int mother = MOTHER_TABLE;
-  double param = 0;
   int nbatch = 1, nrows = 0;              // signals, rows per signal
   const double* scales = nullptr;
   double dt = 0;
-  const double* a = nullptr;
-  const double* amp_re = nullptr;
-  const double* amp_im = nullptr;
-  const int* tab_klo = nullptr;
-  const int* tab_nband = nullptr;
   int64_t ldw = 0, ncols = 0;             // the output W
-  int64_t spec_ld = 0;                    // elements between the rows' spectra (0: one shared spectrum)
-  int rows_per_signal = 0;                // build_row_table: > 0 for a batch
-  int64_t ols_ncols = 0, out_ncols = 0;   // build_row_table: > 0 where the overlap-save / band-passed forms may be used
+  RowRequest rows;                        // (its nrows, and a / amp_* of a call by scales, are filled in by prepare_table)
 };
 
 // Makes the row table of call c current: the cached one of the same call, or a new one.  A new table gets the side tables
@@ -43,20 +34,21 @@ int prepare_table(cwt_plan* p, const TableCall& c) {
   const int total = c.nbatch * c.nrows;
   if (total < 1 || total > p->max_rows) return fail(CWT_EINVAL, "nrows must be in [1, max_rows]");
   if (c.ncols < 1 || c.ncols > p->N || c.ldw < c.ncols) return fail(CWT_EINVAL, "need 1 <= ncols <= nfft and ldw >= ncols");
-  if (c.spec_ld != 0 && c.spec_ld < p->N) return fail(CWT_EINVAL, "spec_ld must be 0 (shared) or >= nfft");
+  if (c.rows.spec_ld != 0 && c.rows.spec_ld < p->N) return fail(CWT_EINVAL, "spec_ld must be 0 (shared) or >= nfft");
   if (c.scales && (!(c.dt > 0) || !std::isfinite(c.dt))) return fail(CWT_EINVAL, "dt must be positive");
   std::vector<double> key;                        // [kind, head..., the rows' arguments]
   if (c.kind >= 0) {
     key = c.scales ? call_key(c.kind, {}, {{c.scales, c.nrows}})
-                   : call_key(c.kind, {}, {{c.a, total}, {c.amp_re, total}, {c.amp_im, total}});
+                   : call_key(c.kind, {}, {{c.rows.a, total}, {c.rows.amp_re, total}, {c.rows.amp_im, total}});
     key.insert(key.begin() + 1, c.head.begin(), c.head.end());
   }
   if (!select_table(p, key)) {
     double cre = 0, cim = 0;
     // the mother id and order of every call but a filter bank of the caller's (whose id is MOTHER_TABLE)
-    int rc = c.tab_klo ? CWT_OK : mother_constant(c.mother, c.param, &cre, &cim);
+    int rc = c.rows.tab_klo ? CWT_OK : mother_constant(c.rows.mother, c.rows.param, &cre, &cim);
     if (rc) return rc;
-    const double *a = c.a, *amp_re = c.amp_re, *amp_im = c.amp_im;
+    RowRequest r = c.rows;                        // (a / amp_*: the call's own, or made here)
+    r.nrows = total;
     std::vector<double> va, vr, vi;
     if (c.scales) {
       const double w1 = 2.0 * 3.14159265358979323846 * (1.0 / (double(p->N) * c.dt));  // ftfreqs[1], wavelet.py:94
@@ -69,16 +61,15 @@ int prepare_table(cwt_plan* p, const TableCall& c) {
         vr[j] = norm * cre;
         vi[j] = norm * cim;
       }
-      a = va.data(); amp_re = vr.data(); amp_im = vi.data();
-    } else if (!a) {                                  // a filter bank of the caller's holds the amplitudes
+      r.a = va.data(); r.amp_re = vr.data(); r.amp_im = vi.data();
+    } else if (!r.a) {                                // a filter bank of the caller's holds the amplitudes
       va.assign(total, 1.0);
       vi.assign(total, 0.0);
-      a = amp_re = va.data(); amp_im = vi.data();
+      r.a = r.amp_re = va.data(); r.amp_im = vi.data();
     }
-    rc = build_row_table(p, c.mother, c.param, a, amp_re, amp_im, c.spec_ld, total, c.tab_klo, c.tab_nband, c.rows_per_signal,
-                         -1, c.ols_ncols, c.out_ncols);
+    rc = build_row_table(p, r);
     if (!rc) rc = upload_row_table(p, key);
-    const Mother mo = mother_of(c.mother, c.param);
+    const Mother mo = mother_of(r.mother, r.param);
     if (!rc) rc = by_precision(p, [&](auto t) {
       using T = decltype(t);
       int r = p->rt->n_ols ? fill_ols_tables<T>(p, mo) : CWT_OK;
@@ -95,8 +86,7 @@ int prepare_table(cwt_plan* p, const TableCall& c) {
 // The rows of a call by scales (every table-building entry point but cwt_filter_rows and cwt_transform_rows_table)
 TableCall scale_rows(int mother, double param, double dt, const double* scales, int nrows, int64_t ldw, int64_t ncols) {
   TableCall c;
-  c.mother = mother;
-  c.param = param;
+  c.rows.mother = mother; c.rows.param = param;
   c.dt = dt;
   c.scales = scales;
   c.nrows = nrows;
@@ -111,8 +101,8 @@ int prepare_rows_table(cwt_plan* p, bool have_signal, int mother, double param, 
   TableCall c = scale_rows(mother, param, dt, scales, nrows, ldw, ncols);
   c.kind = 0;
   c.head = {p->tolerance, double(mother), param, dt, double(nrows), have_signal ? 1.0 : 0.0, double(ncols)};
-  c.ols_ncols = have_signal ? ncols : 0;
-  c.out_ncols = ncols;
+  c.rows.ols_ncols = have_signal ? ncols : 0;
+  c.rows.out_ncols = ncols;
   return prepare_table(p, c);
 }
 
@@ -346,7 +336,7 @@ int cwt_plan_create(cwt_plan** plan, int device, int64_t nfft, int precision, in
   p->prec = precision;
   p->max_rows = max_rows;
   p->log_wg_points = precision == 64 ? 13 : 14;
-  p->narrow_terms = precision == 64 ? 4 : 8;      // see the cost table in build_row_table
+  p->narrow_terms = precision == 64 ? 4 : 8;      // see the cost table in classify_row
   p->serial_rows = precision == 64 ? 2 : 0;       // [measured, round 6: c2 -1 %, fp64 Paul -5.7 %; fp32 DOG +-0, fp32 Paul +1.4 %]
   if (const char* e = std::getenv("CWT_TOLERANCE")) {   // default accuracy target of plans created from here on
     const double t = std::atof(e);
@@ -692,8 +682,7 @@ int cwt_transform_rows_batch(cwt_plan* p, const void* xhat_dev, int nbatch, int6
   c.kind = 2;
   c.head = {p->tolerance, double(mother), param, dt, double(nbatch), double(xhat_ld), double(nrows)};
   c.nbatch = nbatch;
-  c.rows_per_signal = nrows;
-  c.spec_ld = xhat_ld;
+  c.rows.rows_per_signal = nrows; c.rows.spec_ld = xhat_ld;
   const int rc = prepare_table(p, c);
   if (rc) return rc;
   return queue_rows(p, xhat_dev, mother_of(mother, param), nbatch * nrows, W_dev, ldw, ncols);
@@ -712,10 +701,8 @@ int cwt_transform_batch(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld
   c.kind = 3;
   c.head = {p->tolerance, double(mother), param, dt, double(nbatch), double(nrows), double(ncols)};
   c.nbatch = nbatch;
-  c.rows_per_signal = nrows;
-  c.spec_ld = p->N;
-  c.ols_ncols = ncols;
-  c.out_ncols = ncols;
+  c.rows.rows_per_signal = nrows; c.rows.spec_ld = p->N;
+  c.rows.ols_ncols = c.rows.out_ncols = ncols;
   int rc = prepare_table(p, c);
   if (rc) return rc;
   const Mother mo = mother_of(mother, param);
@@ -734,8 +721,7 @@ int cwt_transform_rows_table(cwt_plan* p, const void* xhat_dev, const void* tabl
   HIPCHECK(hipSetDevice(p->device));
   TableCall c;                                           // (kind -1: explicit filter banks are not cached)
   c.nrows = nrows;
-  c.tab_klo = k_lo;
-  c.tab_nband = nband;
+  c.rows.tab_klo = k_lo; c.rows.tab_nband = nband;
   c.ldw = ldw;
   c.ncols = ncols;
   const int rc = prepare_table(p, c);
@@ -766,15 +752,12 @@ int cwt_filter_rows(cwt_plan* p, const void* spec_dev, int64_t spec_ld, int moth
   TableCall c;
   c.kind = 1;
   c.head = {p->tolerance, double(mother), param, double(spec_ld), double(nrows)};
-  c.mother = mother;
-  c.param = param;
+  c.rows.mother = mother; c.rows.param = param;
   c.nrows = nrows;
-  c.a = a;
-  c.amp_re = amp_re;
-  c.amp_im = amp_im;
+  c.rows.a = a; c.rows.amp_re = amp_re; c.rows.amp_im = amp_im;
   c.ldw = ldw;
   c.ncols = ncols;
-  c.spec_ld = spec_ld;
+  c.rows.spec_ld = spec_ld;
   const int rc = prepare_table(p, c);
   if (rc) return rc;
   return queue_rows(p, spec_dev, mother_of(mother, param), nrows, W_dev, ldw, ncols);

@@ -85,7 +85,7 @@ template <typename T> constexpr int default_logp() { return sizeof(T) == 8 ? 13 
 // all band-limited rows in one launch (k_narrow_ct_all); false if the geometry is not the default one
 template <typename T>
 bool narrow_ct_all_applies(const cwt_plan* p) {
-  if (!p->use_ct || std::min(p->log_wg_points, p->logN) != default_logp<T>()) return false;
+  if (!default_tile_ct(p)) return false;
   for (const auto& g : p->rt->narrow_groups) {
     if (g.logK == 11 && sizeof(T) == 8 && g.nterms >= 1 && g.nterms <= 8) continue;      // k_narrow_ct_big
     if (g.logK < 4 || g.logK > 10 || g.nterms < 1 || g.nterms > 16 || (g.nterms > 1 && g.logK != 10)) return false;
@@ -229,7 +229,7 @@ void launch_pass_a_ct_rows(cwt_plan* p, const void* in, const RowDesc* rows, int
 template <typename T, int MODE>
 bool try_pass_a_ct(cwt_plan* p, int logR, const void* in, const RowDesc* rows, int cnt, const Mother& mo,
                    long n0, long in_ld, cplx<T>* Z, hipStream_t st) {
-  if (!p->use_ct || std::min(p->log_wg_points, p->logN) != default_logp<T>()) return false;
+  if (!default_tile_ct(p)) return false;
 #define CWT_CASE(LR)                                                                                  \
   case LR:                                                                                            \
     if constexpr (MODE == IN_SPECTRUM) launch_pass_a_ct_rows<T, LR>(p, in, rows, cnt, mo, Z, st);    \
@@ -265,7 +265,7 @@ void launch_pass_b_ct(cwt_plan* p, const RowDesc* rows, int cnt, cplx<T>* W, int
 template <typename T, bool CONJ>
 bool try_pass_b_ct(cwt_plan* p, int logK, const RowDesc* rows, int cnt, cplx<T>* W, int64_t ldw,
                    int64_t ncols, const cplx<T>* Z, hipStream_t st) {
-  if (!p->use_ct || std::min(p->log_wg_points, p->logN) != default_logp<T>()) return false;
+  if (!default_tile_ct(p)) return false;
   switch (logK) {
     case 9: launch_pass_b_ct<T, 9, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st); return true;
     case 10: launch_pass_b_ct<T, 10, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st); return true;
@@ -1086,8 +1086,15 @@ int bluestein_convolve(cwt_plan* p, const void* spec, int nrows, int which, void
   select_table(p, {});
   std::vector<double> one(nrows, 1.0), zero(nrows, 0.0);
   std::vector<int> klo(nrows, int(-(p->N / 2))), nb(nrows, int(p->N));
-  int rc = build_row_table(p, MOTHER_TABLE, 0.0, one.data(), one.data(), zero.data(), p->N, nrows, klo.data(), nb.data(),
-                           0, 0);
+  RowRequest r;                                    // MOTHER_TABLE
+  r.a = r.amp_re = one.data();
+  r.amp_im = zero.data();
+  r.spec_ld = p->N;
+  r.nrows = nrows;
+  r.tab_klo = klo.data();
+  r.tab_nband = nb.data();
+  r.tab_ld = 0;
+  int rc = build_row_table(p, r);
   if (!rc) rc = upload_row_table(p, {});
   if (rc) return rc;
   set_split(p);

@@ -1,6 +1,6 @@
 // plan.hpp -- the plan (struct cwt_plan) and the host-side internals shared by the translation units of libcwt_hip.so:
-//   plan_host.cpp    row classification (build_row_table and its searches), row-table cache, scratch buffers, host copies,
-//                    shard cost model -- plain C++ against the HIP runtime API, no kernels
+//   plan_host.cpp    row classification (build_row_table: per-call gates, per-row form searches, one layout pass per form),
+//                    row-table cache, scratch buffers, host copies -- plain C++ against the HIP runtime API, no kernels
 //   launch_impl.hpp  every kernel launch, as templates over the precision; instantiated by launch_f64.hip / launch_f32.hip
 //   abi.hip          the exported C functions (include/cwt_hip.h)
 // Everything here lives in namespace cwtd ("detail"); nothing is exported but the C ABI.
@@ -54,6 +54,20 @@ struct Timed { int cls; hipEvent_t a, b; };
 
 struct HostCopier;
 HostCopier* copier_for(int device);
+
+// The rows build_row_table classifies: W[j,:] = IFFT_N( spec_j[k] * (amp_j * profile(a_j * signed_bin(k))) ), j < nrows
+struct RowRequest {
+  int mother = MOTHER_TABLE;
+  double param = 0;
+  const double *a = nullptr, *amp_re = nullptr, *amp_im = nullptr;   // a_j; amp_j WITHOUT the 1/N of the inverse FFT
+  int nrows = 0, rows_per_signal = 0;     // > 0: a batch, row j of signal j / rows_per_signal
+  int64_t spec_ld = 0;                    // elements between the rows' (signals') spectra; 0: one shared spectrum
+  const int *tab_klo = nullptr, *tab_nband = nullptr;   // MOTHER_TABLE: each row's band, its filter tab_ld elements after
+  int64_t tab_ld = -1;                                  // the previous row's (-1: N, 0: one filter for all)
+  int64_t ols_ncols = 0;    // > 0: the caller also has the real signal (cwt_transform): time-compact rows may take the
+                            // overlap-save form, their output blocks covering ols_ncols columns
+  int64_t out_ncols = 0;    // > 0: W's columns, for the rows on the band-passed signal (which need the spectrum only)
+};
 
 }  // namespace cwtd
 
@@ -168,9 +182,9 @@ struct cwt_plan {
   // the smoothing filter rows, draw after draw) build and upload each table once.  No host synchronisation on the
   // way: every slot has its own pinned staging buffer and an event that marks its last copy as done.
   struct Group { int logK; int first; int count; int nterms; };
-  struct RowTable {
-    std::vector<double> key;             // the call it was built from; empty = not valid
-    std::vector<cwt::RowDesc> table;          // ordered: [small | narrow classes by logK | wide]
+  // The host side of a row table: its rows and how the launches cut them.  build_row_table replaces it whole.
+  struct RowLayout {
+    std::vector<cwt::RowDesc> table;     // small | narrow by launch class | two-pass | overlap-save | A | A2 | masks | polynomial
     std::vector<Group> narrow_groups;
     int n_small = 0, n_narrow = 0, n_wide = 0, wide_first = 0;
     int n_ols = 0, ols_first = 0;        // overlap-save rows (after the wide rows), sorted by halo class
@@ -178,7 +192,7 @@ struct cwt_plan {
     // in flight per CU instead of two; measured -10...-20 % per row, profiles/r03_ols_tiles.txt), group 1 = the default tile
     struct OlsGroup {
       int logp = 13;                     // log2 of the workgroup tile
-      cwt::OlsClasses cls;                    // halo classes of this group (wg_first / row_first relative to the group)
+      cwt::OlsClasses cls{};                  // halo classes of this group (wg_first / row_first relative to the group)
       long wgs = 0;                      // workgroups of its k_ols_ct launch
       long wgs_base = 0;                 // ... of which the classes on blocks of ONE tile come first (their block spectra are the first to exist)
       long fwd_blocks[3] = {0, 0, 0};    // blocks of P, 2P, 4P points (k_ols_fwd_r launches)
@@ -188,8 +202,6 @@ struct cwt_plan {
     long ols_xs_elems = 0, ols_gt_elems = 0;
     int ols_nbatch = 1;                  // signals of a batched call (cwt_transform_batch): block spectra per signal,
     long ols_xs_sig = 0;                 // ols_xs_sig elements apart; the rows carry their signal's offset in spec_off
-    void* gt_dev = nullptr;              // filter tables of the overlap-save rows, written when the table is built
-    size_t gt_bytes = 0;
     // rows clipped at Nyquist on the band-passed complex signal (after the overlap-save rows), one halo class; the
     // table entry at aux_first is the pseudo-row whose "filter" is the mask (profile 1 on the bins [k_s, N/2))
     // band-limited rows in polynomial form (at the end of the table), grouped by K'
@@ -209,8 +221,6 @@ struct cwt_plan {
     struct PolyRtab { int logK, deg; long off; };
     std::vector<PolyRtab> poly_rtabs;
     long poly_rtab_elems = 0;
-    void* prt_dev = nullptr;
-    size_t prt_bytes = 0;
     int n_aols = 0, aols_first = 0, aux_first = -1, aols_logp = 12;
     int aols_nbatch = 1;                 // signals of a batched call: aols_geom.nrows rows and one mask pseudo-row (aux_first + b) each
     cwt::AolsGeom aols_geom{};
@@ -219,8 +229,13 @@ struct cwt_plan {
     int n_aols2 = 0, aols2_first = 0;
     cwt::AolsGeom aols2_geom{};
     long aols2_wgs = 0;
-    void* agt_dev = nullptr;             // their (real) filter tables
-    size_t agt_bytes = 0;
+  };
+  // A slot of the cache: a layout, the call it was built from and its device copies
+  struct RowTable : RowLayout {
+    std::vector<double> key;             // the call it was built from; empty = not valid
+    void* gt_dev = nullptr; size_t gt_bytes = 0;     // filter tables of the overlap-save rows, written when the table is built
+    void* agt_dev = nullptr; size_t agt_bytes = 0;   // ... of the rows on the band-passed signal (real)
+    void* prt_dev = nullptr; size_t prt_bytes = 0;   // ... of the economised weights of the polynomial rows
     cwt::RowDesc* rows_dev = nullptr;
     cwt::RowDesc* rows_pinned = nullptr;
     hipEvent_t uploaded = nullptr;
@@ -276,15 +291,14 @@ inline double default_tolerance(const cwt_plan* p) { return p->prec == 64 ? kDef
 // Each is floored where the arithmetic's own rounding takes over.
 struct Tolerances { double support, halo, clip; };
 Tolerances tolerances(const cwt_plan* p);
+// Compile-time specialised kernels at the default workgroup tile (8192 points in fp64, 16384 in fp32): most fast forms need them
+inline bool default_tile_ct(const cwt_plan* p) { return p->use_ct && std::min(p->log_wg_points, p->logN) == (p->prec == 64 ? 13 : 14); }
 
 // ---- plan_host.cpp ----
 int get_event(cwt_plan* p, hipEvent_t* e);
 int mother_constant(int mother, double param, double* cre, double* cim);
 size_t table_capacity(int max_rows);
-int build_row_table(cwt_plan* p, int mother, double param, const double* a, const double* amp_re,
-                    const double* amp_im, int64_t spec_ld, int nrows, const int* tab_klo = nullptr,
-                    const int* tab_nband = nullptr, int rows_per_signal = 0, int64_t tab_ld = -1,
-                    int64_t ols_ncols = 0, int64_t out_ncols = 0);
+int build_row_table(cwt_plan* p, const RowRequest& r);
 void set_split(cwt_plan* p);
 bool serial_schedule(const cwt_plan* p, bool ols_early);
 int chunk_rows_of(const cwt_plan* p);

@@ -1,5 +1,5 @@
 // plan_host.cpp -- host side without kernels: error state, row classification (which row takes which form: the searches for
-// supports, halos, degrees; build_row_table), the row-table cache, scratch buffers, device -> host copies.  Plain C++ against
+// supports, halos, degrees: build_row_table), the row-table cache, scratch buffers, device -> host copies.  Plain C++ against
 // the HIP runtime API (streams, events, allocations); compiles in seconds and runs on the CPU stand-in of tests/emu unchanged.
 // Reference lines: the filter bank of pycwt/wavelet.py:102-104 is never built; what is decided here is how each row of
 // wavelet.py:105-106 is computed instead.
@@ -496,708 +496,711 @@ int mother_constant(int mother, double param, double* cre, double* cim) {
 // Entries of a plan's row tables: max_rows rows + the pseudo-rows some forms add.
 size_t table_capacity(int max_rows) { return size_t(max_rows) + size_t(max_rows) / 3 + 4; }
 
-// Row table for W[j,:] = IFFT_N( spec_j[k] * (amp_j * profile(a_j * signed_bin(k))) ), spec_j = spec + j*spec_ld.
-// a_j = profile argument per bin, amp_j = complex amplitude WITHOUT the 1/N of the inverse FFT.
-// ols_ncols > 0: the caller also has the real signal (cwt_transform): time-compact rows may take the overlap-save
-// form, their output blocks covering ols_ncols columns.
-int build_row_table(cwt_plan* p, int mother, double param, const double* a, const double* amp_re,
-                    const double* amp_im, int64_t spec_ld, int nrows, const int* tab_klo,
-                    const int* tab_nband, int rows_per_signal, int64_t tab_ld,
-                    int64_t ols_ncols, int64_t out_ncols) {
-  const int64_t N = p->N;
-  double f_lo = 0, f_hi = 0;
-  if (mother < MOTHER_MORLET || mother > MOTHER_TABLE) return fail(CWT_EINVAL, "unknown mother id");
-  const Tolerances tol = tolerances(p);
-  if (mother != MOTHER_TABLE) profile_support(mother, param, tol.support, &f_lo, &f_hi);
+namespace {
 
-  const int logP = std::min(p->log_wg_points, p->logN);
-  const bool use_small = p->logN <= p->loglmax;
-  const int narrow_cap = std::min(p->narrow_max_logk, logP - 1);
-  // pass A specialised for narrow column supports (default geometry only)
-  const int two_pass_logr = p->logN - two_pass_logk(p);
-  const bool band_pass_a = p->use_ct && p->band_pass_a && logP == (p->prec == 64 ? 13 : 14);
+using RowLayout = cwt_plan::RowLayout;
+constexpr int kOlsLogp = 13;    // workgroup tile of the overlap-save rows: 8192 points (512 threads)
+constexpr int kAolsLogp = 12;   // ... of the first class of rows on the band-passed signal: 4096 points, four block transforms in flight per CU
+
+// Which forms the rows of one call may take, and the constants the per-row searches share
+struct Gates {
+  Tolerances tol;                // (tolerances(p))
+  double f_lo = 0, f_hi = 0;     // the mother's support (profile argument) at tol.support
+  double fc_lo = 0, fc_hi = 0;   // ... at tol.clip: a row whose bins at Nyquist lie outside it vanishes there
+  bool use_small, multi_ok, big_ok, band_pass_a, ols_ok, ols_big, ols_big4, aols_ok, poly_ok;
+  int narrow_cap, tp_logk, ols_logp_s, ols_hmax, ols_nbatch, aols_nbatch;
+  double ols_ch;                 // halo of an overlap-save row in scales (time_halo_factor)
+};
+Gates gates(const cwt_plan* p, const RowRequest& r) {
+  Gates g;
+  g.tol = tolerances(p);
+  if (r.mother != MOTHER_TABLE) profile_support(r.mother, r.param, g.tol.support, &g.f_lo, &g.f_hi);
+  const bool ct = default_tile_ct(p);
+  const int rps = r.rows_per_signal;
+  g.use_small = p->logN <= p->loglmax;
+  g.narrow_cap = std::min(p->narrow_max_logk, std::min(p->log_wg_points, p->logN) - 1);
+  g.tp_logk = two_pass_logk(p);
+  g.band_pass_a = ct && p->band_pass_a;   // pass A specialised for narrow column supports
   // the multi-term form exists only in the compile-time kernel for K = 1024 at the default geometry
-  const bool multi_ok = p->use_ct && p->narrow_terms > 1 && narrow_cap >= 10 &&
-                        logP == (p->prec == 64 ? 13 : 14);
+  g.multi_ok = ct && p->narrow_terms > 1 && g.narrow_cap >= 10;
   // K = 2048 single-pass rows: fp64 only, N >= 2^14 (a 16384-point workgroup tile must fit the row)
-  const bool big_ok = p->use_ct && p->narrow_big && p->prec == 64 && narrow_cap >= 10 && logP == 13 &&
-                      p->logN >= 14;
-  // overlap-save rows: default geometry, at least 4 workgroup tiles per row, built-in mothers, one shared spectrum
-  // workgroup tile of the overlap-save rows: 8192 points (512 threads)
-  const int ols_logp = 13;
-  // half-size tiles for short halos (only beside the default 8192-point tile)
-  const int ols_logp_s = (p->ols_small_max_halo > 0 && ols_logp == 13) ? 12 : 0;
-  // a batch of signals (cwt_transform_batch: rows_per_signal > 0 with the signals at hand) has nbatch times the blocks
-  // of one signal to fill the GPU with, so the form pays from shorter transforms: the threshold counts the batch
-  const int ols_nbatch = (rows_per_signal > 0 && ols_ncols > 0) ? std::max(1, nrows / rows_per_signal) : 1;
-  const bool ols_batch_ok = true;
-  const bool ols_layout = rows_per_signal > 0 ? (ols_batch_ok && ols_ncols > 0 && nrows % rows_per_signal == 0) : spec_ld == 0;
-  const bool ols_ok = p->ols && ols_ncols > 0 && p->use_ct && logP == (p->prec == 64 ? 13 : 14) &&
-                      p->logN + ilog2(ols_nbatch) >= p->ols_min_logn && p->logN >= ols_logp + 2 &&
-                      mother != MOTHER_TABLE && ols_layout && !use_small;
-  const int ols_P = 1 << ols_logp;
-  const int ols_hmax = p->ols_max_halo > 0 ? std::min(p->ols_max_halo, ols_P / 4) : ols_P / 4;
-  const bool ols_big = ols_ok && p->ols_big && ols_logp == 13 && p->logN >= ols_logp + 3;   // blocks of 2P points
-  const bool ols_big4 = ols_big && p->ols_big >= 2 && p->logN >= ols_logp + 4;               // ... and of 4P points
-  const double ols_ch = ols_ok ? time_halo_factor(mother, param, tol.halo) : 0.0;
-  // "not clipped at Nyquist": the profile at the Nyquist bins is below this fraction of its peak (the jump there is what
-  // gives the sampled wavelet its slow 1/t tail; measured error of the form ~ a tenth of that fraction)
+  g.big_ok = ct && p->narrow_big && p->prec == 64 && g.narrow_cap >= 10 && p->logN >= 14;
+  // overlap-save rows: default geometry, at least 4 workgroup tiles per row, built-in mothers, one shared spectrum or the
+  // signals of a batch at hand (cwt_transform_batch).  A batch has nbatch times the blocks of one signal to fill the GPU with,
+  // so the form pays from shorter transforms: the threshold counts the batch
+  g.ols_nbatch = (rps > 0 && r.ols_ncols > 0) ? std::max(1, r.nrows / rps) : 1;
+  const bool ols_layout = rps > 0 ? (r.ols_ncols > 0 && r.nrows % rps == 0) : r.spec_ld == 0;
+  g.ols_ok = p->ols && r.ols_ncols > 0 && ct && p->logN + ilog2(g.ols_nbatch) >= p->ols_min_logn && p->logN >= kOlsLogp + 2 &&
+             r.mother != MOTHER_TABLE && ols_layout && !g.use_small;
+  g.ols_logp_s = p->ols_small_max_halo > 0 ? kOlsLogp - 1 : 0;     // half-size tiles for short halos
+  g.ols_hmax = p->ols_max_halo > 0 ? std::min(p->ols_max_halo, (1 << kOlsLogp) / 4) : (1 << kOlsLogp) / 4;
+  g.ols_big = g.ols_ok && p->ols_big && p->logN >= kOlsLogp + 3;   // blocks of 2P points
+  g.ols_big4 = g.ols_big && p->ols_big >= 2 && p->logN >= kOlsLogp + 4;   // ... and of 4P points
+  g.ols_ch = g.ols_ok ? time_halo_factor(r.mother, r.param, g.tol.halo) : 0.0;
   // rows clipped at Nyquist as overlap-save rows on the band-passed complex signal (k_aols_*): needs the spectrum only;
   // Morlet and Paul (a real mother constant and nothing to keep on the masked-out bins), one shared spectrum
   // DOG (order >= 1): also, but only when the call hands over the REAL signal (its negative bins are the mirror image then)
   // a batch (rows_per_signal > 0: the same rows for every signal): one mask pseudo-row and one set of block spectra per
   // signal; like the overlap-save rows the form pays from shorter transforms there, the threshold counts the batch
-  const int aols_nbatch = rows_per_signal > 0 ? std::max(1, nrows / rows_per_signal) : 1;
-  const bool aols_layout = rows_per_signal > 0 ? (nrows % rows_per_signal == 0 && size_t(nrows) + size_t(aols_nbatch) <= table_capacity(p->max_rows))
-                                               : spec_ld == 0;
-  const bool aols_ok = p->ols && p->aols && out_ncols > 0 && p->use_ct && logP == (p->prec == 64 ? 13 : 14) &&
-                       p->logN + ilog2(aols_nbatch) >= p->ols_min_logn && p->logN >= 15 && aols_layout && !use_small &&
-                       (mother == MOTHER_MORLET || mother == MOTHER_PAUL ||
-                        (mother == MOTHER_DOG && param >= 1 && ols_ncols > 0));
-  double fc_lo = 0, fc_hi = 0;
-  if (ols_ok || aols_ok) profile_support(mother, param, tol.clip, &fc_lo, &fc_hi);
-  std::vector<RowDesc> narrow_rows, wide_rows, small_rows, poly_rows;
-  std::vector<char> wide_clipped, wide_unclipped;
-  const bool poly_ok = p->poly && p->use_ct && logP == (p->prec == 64 ? 13 : 14) && mother != MOTHER_TABLE &&
-                       p->logN >= std::max(POLY_LOGP, p->poly_min_logn) && !use_small && rows_per_signal == 0;   // (not for batches yet)
-  struct OlsRow { RowDesc rd; int grp, lb, h64; };
-  std::vector<OlsRow> ols_rows;
-  for (int j = 0; j < nrows; ++j) {
-    if (!(a[j] > 0) || !std::isfinite(a[j])) return fail(CWT_EINVAL, "scales must be positive and finite");
-    RowDesc rd;
-    rd.a = a[j];
-    rd.amp_re = amp_re[j] / double(N);
-    rd.amp_im = amp_im[j] / double(N);
-    // batched signals: row j belongs to signal j / rows_per_signal, whose spectrum starts at spec_ld * that
-    rd.spec_off = rows_per_signal ? long(spec_ld) * (j / rows_per_signal) : long(spec_ld) * j;
-    rd.tab_off = (tab_ld < 0 ? long(N) : long(tab_ld)) * j;       // tab_ld = 0: every row uses the same table
-    rd.aux_off = 0;
-    rd.kc_off = 0;
-    rd.rtab_off = -1;
-    rd.nyq_re = rd.nyq_im = 0.0;
-    double row_lo = f_lo, row_hi = f_hi, row_best = 0.0;     // row_best: log of the filter's largest value on the row's bins / its peak
-    if (mother != MOTHER_TABLE) {
-      // The support threshold is meant relative to the largest value the filter takes ON THE ROW'S BINS.  Where the bins
-      // are coarser than the profile (a >~ 1: the largest scales) that is far below the profile's own peak: the
-      // threshold follows it, or the row would lose the few bins that carry all of its (tiny) energy.
-      const double kc = profile_peak_f(mother, param) / rd.a;
-      double best = -std::numeric_limits<double>::infinity();
-      for (double k : {std::floor(kc), std::ceil(kc), -std::floor(kc), -std::ceil(kc)}) {
-        if (mother == MOTHER_PAUL) k = std::max(k, 1.0);
-        if (mother == MOTHER_MORLET && k < 0) continue;
-        k = std::min(std::max(k, -double(N / 2)), double(N / 2 - 1));
-        best = std::max(best, profile_log_rel(mother, param, rd.a * k));
-      }
-      if (std::isfinite(best) && best < std::log(0.25)) {
-        const double eps_row = std::max(tol.support * std::exp(best), 1e-300);
-        profile_support(mother, param, eps_row, &row_lo, &row_hi);
-        row_best = best;
-      }
+  g.aols_nbatch = rps > 0 ? std::max(1, r.nrows / rps) : 1;
+  const bool aols_layout = rps > 0 ? (r.nrows % rps == 0 && size_t(r.nrows) + size_t(g.aols_nbatch) <= table_capacity(p->max_rows))
+                                   : r.spec_ld == 0;
+  g.aols_ok = p->ols && p->aols && r.out_ncols > 0 && ct && p->logN + ilog2(g.aols_nbatch) >= p->ols_min_logn && p->logN >= 15 &&
+              aols_layout && !g.use_small &&
+              (r.mother == MOTHER_MORLET || r.mother == MOTHER_PAUL || (r.mother == MOTHER_DOG && r.param >= 1 && r.ols_ncols > 0));
+  // "not clipped at Nyquist": the profile at the Nyquist bins is below this fraction of its peak (the jump there is what
+  // gives the sampled wavelet its slow 1/t tail; measured error of the form ~ a tenth of that fraction)
+  if (g.ols_ok || g.aols_ok) profile_support(r.mother, r.param, g.tol.clip, &g.fc_lo, &g.fc_hi);
+  g.poly_ok = p->poly && ct && r.mother != MOTHER_TABLE && p->logN >= std::max(POLY_LOGP, p->poly_min_logn) && !g.use_small &&
+              rps == 0;   // (not for batches yet)
+  return g;
+}
+
+// Row j with its support on the transform's bins
+struct RowSupport {
+  RowDesc rd;
+  double best;     // log of the filter's largest value on the row's bins / its peak (0 unless far below the peak)
+  bool vanishes;   // the filter vanishes at the Nyquist bins (at tol.clip)
+};
+int row_support(const cwt_plan* p, const RowRequest& r, const Gates& g, int j, RowSupport* s) {
+  const int64_t N = p->N;
+  if (!(r.a[j] > 0) || !std::isfinite(r.a[j])) return fail(CWT_EINVAL, "scales must be positive and finite");
+  RowDesc& rd = s->rd;
+  rd = RowDesc{};
+  rd.a = r.a[j];
+  rd.amp_re = r.amp_re[j] / double(N);
+  rd.amp_im = r.amp_im[j] / double(N);
+  // batched signals: row j belongs to signal j / rows_per_signal, whose spectrum starts at spec_ld * that
+  rd.spec_off = r.rows_per_signal ? long(r.spec_ld) * (j / r.rows_per_signal) : long(r.spec_ld) * j;
+  rd.tab_off = (r.tab_ld < 0 ? long(N) : long(r.tab_ld)) * j;       // tab_ld = 0: every row uses the same table
+  rd.rtab_off = -1;
+  double row_lo = g.f_lo, row_hi = g.f_hi;
+  s->best = 0.0;
+  if (r.mother != MOTHER_TABLE) {
+    // The support threshold is meant relative to the largest value the filter takes ON THE ROW'S BINS.  Where the bins
+    // are coarser than the profile (a >~ 1: the largest scales) that is far below the profile's own peak: the
+    // threshold follows it, or the row would lose the few bins that carry all of its (tiny) energy.
+    const double kc = profile_peak_f(r.mother, r.param) / rd.a;
+    double best = -std::numeric_limits<double>::infinity();
+    for (double k : {std::floor(kc), std::ceil(kc), -std::floor(kc), -std::ceil(kc)}) {
+      if (r.mother == MOTHER_PAUL) k = std::max(k, 1.0);
+      if (r.mother == MOTHER_MORLET && k < 0) continue;
+      k = std::min(std::max(k, -double(N / 2)), double(N / 2 - 1));
+      best = std::max(best, profile_log_rel(r.mother, r.param, rd.a * k));
     }
-    double klo = std::ceil(row_lo / rd.a), khi = std::floor(row_hi / rd.a);
-    if (mother == MOTHER_PAUL) klo = std::max(klo, 1.0);
-    const bool vanishes = std::ceil(fc_lo / rd.a) > -double(N / 2) &&                 // F_j vanishes at the Nyquist bins
-                          std::floor(fc_hi / rd.a) < double(N / 2 - 1);
-    const bool unclipped = ols_ok && vanishes;
-    klo = std::max(klo, -double(N / 2));
-    khi = std::min(khi, double(N / 2 - 1));
-    if (mother == MOTHER_TABLE) { klo = tab_klo[j]; khi = klo + tab_nband[j] - 1; }
-    if (khi < klo - 1) khi = klo - 1;
-    if (klo < -double(N / 2) || khi > double(N / 2 - 1)) return fail(CWT_EINVAL, "filter support outside [-N/2, N/2)");
-    rd.k_lo = int(klo);
-    rd.nband = khi >= klo ? int(khi - klo + 1) : 0;
-    if (rd.nband == 0) rd.k_lo = 0;
-    rd.out_row = j;
-    rd.logK = 0;
-    rd.nterms = 1;
-    if (use_small) {
-      small_rows.push_back(rd);
+    if (std::isfinite(best) && best < std::log(0.25)) {
+      const double eps_row = std::max(g.tol.support * std::exp(best), 1e-300);
+      profile_support(r.mother, r.param, eps_row, &row_lo, &row_hi);
+      s->best = best;
+    }
+  }
+  double klo = std::ceil(row_lo / rd.a), khi = std::floor(row_hi / rd.a);
+  if (r.mother == MOTHER_PAUL) klo = std::max(klo, 1.0);
+  s->vanishes = std::ceil(g.fc_lo / rd.a) > -double(N / 2) && std::floor(g.fc_hi / rd.a) < double(N / 2 - 1);
+  klo = std::max(klo, -double(N / 2));
+  khi = std::min(khi, double(N / 2 - 1));
+  if (r.mother == MOTHER_TABLE) { klo = r.tab_klo[j]; khi = klo + r.tab_nband[j] - 1; }
+  if (khi < klo - 1) khi = klo - 1;
+  if (klo < -double(N / 2) || khi > double(N / 2 - 1)) return fail(CWT_EINVAL, "filter support outside [-N/2, N/2)");
+  rd.nband = khi >= klo ? int(khi - klo + 1) : 0;
+  rd.k_lo = rd.nband ? int(klo) : 0;
+  rd.out_row = j; rd.nterms = 1;
+  return CWT_OK;
+}
+
+// An overlap-save row: its description on the block grid, tile group (0 = half-size tiles), log2 block length, halo / 64
+struct OlsRow { RowDesc rd; int grp, lb, h64; };
+
+// Row rd sampled on the coarser frequency grid of a 2^logb-point block: bin k' of the block is bin k' N / P_b.  K-point block
+// FFTs, K >= the support; the band start is moved down to a multiple of K/16 (the bins added lie below the support
+// threshold) so that the aliased index wraps at the same slot in every thread
+RowDesc block_row(const cwt_plan* p, const RowRequest& r, const Gates& g, const RowDesc& rd, int logb, int logp_tile) {
+  RowDesc o = rd;
+  const int Pb = 1 << logb;
+  const double ab = rd.a * double(p->N >> logb);
+  double kl = std::ceil(g.f_lo / ab), kh = std::floor(g.f_hi / ab);
+  if (r.mother == MOTHER_PAUL) kl = std::max(kl, 1.0);
+  kl = std::max(kl, -double(Pb / 2));
+  kh = std::min(kh, double(Pb / 2 - 1));
+  o.a = ab;
+  o.amp_re = r.amp_re[rd.out_row] / double(Pb);
+  o.amp_im = r.amp_im[rd.out_row] / double(Pb);
+  o.nband = kh >= kl ? int(kh - kl + 1) : 0;
+  o.k_lo = o.nband ? int(kl) : 0;
+  for (o.logK = std::max(4, ilog2(std::max(o.nband, 1))); o.logK < logp_tile; ++o.logK) {
+    const int nt = 1 << (o.logK - 4);
+    const int lo = o.k_lo - (((o.k_lo % nt) + nt) % nt);
+    if (o.nband + (o.k_lo - lo) <= (1 << o.logK) && lo >= -(Pb / 2)) {
+      o.nband += o.k_lo - lo;
+      o.k_lo = lo;
+      break;
+    }
+  }
+  return o;
+}
+
+// The overlap-save form of a row (see k_ols_ct), false if it has none: halo H = c_H * (scale in samples), a multiple of 64 so
+// that whole wavefronts fall inside or outside the kept part of a block.  Block length P_b = P, or 2P / 4P where that keeps a
+// larger fraction of every block transform and the stores stay >= 128-byte segments (K <= P/8).
+bool ols_candidate(const cwt_plan* p, const RowRequest& r, const Gates& g, const RowSupport& s, OlsRow* o) {
+  const RowDesc& rd = s.rd;
+  if (!g.ols_ok || !s.vanishes || rd.nband == 0) return false;
+  const double s_samples = rd.a * double(p->N) / 6.283185307179586476925;
+  const double hh = std::ceil(g.ols_ch * s_samples / 64.0) * 64.0;
+  const double cap = g.ols_big4 ? std::max(double(std::min(p->ols_big4_max_halo, 4 * g.ols_hmax)), 2.0 * g.ols_hmax)
+                                : double(g.ols_hmax) * (g.ols_big ? 2.0 : 1.0);
+  if (hh > cap) return false;
+  const int halo = std::max(64, int(hh)), ls = g.ols_logp_s;
+  if (ls && p->ols_small_big && halo > p->ols_small_max_halo && halo <= (1 << (ls + 1)) / 8 && p->logN >= ls + 3) {
+    // (halo <= 1/8 block: three quarters of every block transform are kept) blocks of two half-size tiles: the same
+    // 8192-point blocks as the default tile's, on 256-thread workgroups (four per CU)
+    const RowDesc two = block_row(p, r, g, rd, ls + 1, ls);
+    if (two.logK <= ls - 3) { *o = {two, 0, ls + 1, halo / 64}; return true; }
+  }
+  if (ls && halo <= p->ols_small_max_halo) { *o = {block_row(p, r, g, rd, ls, ls), 0, ls, halo / 64}; return true; }
+  if (g.ols_big4 && halo >= p->ols_big4_min_halo) {           // blocks of 4P points: the stores stay >= 128-byte segments
+    const RowDesc big = block_row(p, r, g, rd, kOlsLogp + 2, kOlsLogp);   // while K <= P/8, as for 2P
+    if (big.logK <= kOlsLogp - 3) { *o = {big, 1, kOlsLogp + 2, halo / 64}; return true; }
+  }
+  if (g.ols_big && halo >= p->ols_big_min_halo && halo <= 2 * g.ols_hmax) {
+    const RowDesc big = block_row(p, r, g, rd, kOlsLogp + 1, kOlsLogp);
+    if (big.logK <= kOlsLogp - 3) { *o = {big, 1, kOlsLogp + 1, halo / 64}; return true; }
+  }
+  if (halo > g.ols_hmax) return false;
+  *o = {block_row(p, r, g, rd, kOlsLogp, kOlsLogp), 1, kOlsLogp, halo / 64};
+  return true;
+}
+
+// The polynomial form of a row (k_poly_coef / k_poly_rows) in *o, false if it has none: K' >= the support, intervals of
+// R = N / K' >= 64 samples (128 in complex64: a lane stores two outputs), degree D from the filter-weighted truncation rule
+bool poly_candidate(const cwt_plan* p, const RowRequest& r, const Gates& g, const RowSupport& s, RowDesc* o) {
+  const RowDesc& rd = s.rd;
+  if (!g.poly_ok || rd.nband == 0) return false;
+  const int lk_max = std::min(p->poly_max_logk, p->logN - POLY_MIN_LOGR);
+  const int kc = rd.k_lo + (rd.nband >> 1);
+  PolyBandSamples band;
+  if (std::max(8, ilog2(rd.nband)) <= lk_max) poly_band_samples(r.mother, r.param, rd.a, kc, rd.k_lo, rd.nband, s.best, &band);
+  // The carrier k_c: the band's centre minimises the largest |theta|, but the bound weighs theta by the filter -- for a
+  // lopsided filter (Paul: peak at 9 % of its band; DOG) a carrier nearer the peak needs a lower degree at the same K',
+  // i.e. fewer or shorter coefficient planes.  Candidates: centre + c nband / 16, c = -7 ... 7 (the centre wins ties).
+  // (a filter whose peak sits within 1/16 band of the centre -- Morlet -- keeps the centre: the search is 15 evaluations of the
+  // degree rule per K', the whole cost of classifying a new scale grid)
+  int cmax = 0;
+  if (p->poly_carrier && band.npts > 16) {
+    int ipk = 0;
+    for (int i = 1; i < band.npts; ++i) if (band.g[i] > band.g[ipk]) ipk = i;
+    if (std::abs(2 * ipk - (band.npts - 1)) * 8 > band.npts) cmax = 7;
+  }
+  bool searched = false;
+  int c_prev = 0;
+  for (int lk = std::max(8, ilog2(rd.nband)); lk <= lk_max; ++lk) {
+    int best_deg = POLY_MAX_DEGREE + 2, best_c = 0;
+    auto try_c = [&](int cc) {
+      const double shift = double(cc) * double(rd.nband) / 16.0;
+      const int deg = poly_degree_for(band, lk, g.tol.support, std::round(shift), p->poly_cheb != 0, best_deg, cmax ? 4 : 1);
+      if (deg < best_deg || (deg == best_deg && std::abs(cc) < std::abs(best_c))) { best_deg = deg; best_c = cc; }
+    };
+    if (!searched) {                                   // all candidates at the first K', the neighbours of the winner after that
+      for (int c = 0; c <= cmax; ++c)
+        for (int sgn = (c ? -1 : 1); sgn <= 1; sgn += 2) try_c(sgn * c);
+      searched = true;
     } else {
-      const int need = std::max(4, ilog2(std::max(rd.nband, 1)));
-      // Support wider than 1024 bins: several aliased terms per FFT input, at K = 1024 (8192-point tiles) or, fp64
-      // only, K = 2048 (16384-point tiles, one workgroup per CU).  Measured us per row at N = 2^20 (tools/
-      // terms_sweep.py; two-pass: 9.1 fp64, 5.0 fp32): fp64 K = 1024: 4.3 / 4.9 / 6.1 / 7.2 / 8.5 for 2 / 3 / 4 / 6 / 8
-      // terms, K = 2048: 5.0 / 5.5 / 6.2 / 6.8 / 7.6 / 8.2 / 9.4 for 1 / 2 / 3 / 4 / 5 / 6 / 8; fp32 K = 1024: 2.9 /
-      // 3.2 / 3.5 / 4.3 / 4.8 / 5.3 for 2 / 3 / 4 / 6 / 8 / 10.  Hence: K = 1024 up to 3 terms, K = 2048 beyond.
-      const int t1 = (rd.nband + 1023) >> 10, t2 = (rd.nband + 2047) >> 11;
-      const bool k1_ok = p->narrow && multi_ok && t1 <= p->narrow_terms;
-      const bool k2_ok = p->narrow && big_ok && t2 <= p->big_terms;
-      // overlap-save form (see k_ols_ct): halo H = c_H * (scale in samples), a multiple of 64 so that whole
-      // wavefronts fall inside or outside the kept part of a block.  Block length P_b = P, or 2P (fp64) where that
-      // keeps a larger fraction of every block transform and the stores stay >= 128-byte segments (K <= P/8).
-      int halo = 0, lb = ols_logp, grp = 1;
-      if (ols_ok && unclipped && rd.nband > 0) {
-        const double s_samples = rd.a * double(N) / 6.283185307179586476925;
-        const double hh = std::ceil(ols_ch * s_samples / 64.0) * 64.0;
-        const double cap = ols_big4 ? std::max(double(std::min(p->ols_big4_max_halo, 4 * ols_hmax)), 2.0 * ols_hmax)
-                                    : double(ols_hmax) * (ols_big ? 2.0 : 1.0);
-        if (hh <= cap) halo = std::max(64, int(hh));
-      }
-      RowDesc od = rd;
-      if (halo) {
-        // the same filter sampled on the block's coarser frequency grid: bin k' of a P_b-point block is bin k' N / P_b.
-        // K-point block FFTs, K >= the support; the band start is moved down to a multiple of K/16 (the bins added
-        // lie below the support threshold) so that the aliased index wraps at the same slot in every thread
-        auto describe = [&](int logb, int logp_tile, RowDesc& o) {
-          const int Pb = 1 << logb;
-          const double ab = rd.a * double(N >> logb);
-          double kl = std::ceil(f_lo / ab), kh = std::floor(f_hi / ab);
-          if (mother == MOTHER_PAUL) kl = std::max(kl, 1.0);
-          kl = std::max(kl, -double(Pb / 2));
-          kh = std::min(kh, double(Pb / 2 - 1));
-          o.a = ab;
-          o.amp_re = amp_re[j] / double(Pb);
-          o.amp_im = amp_im[j] / double(Pb);
-          o.k_lo = int(kl);
-          o.nband = kh >= kl ? int(kh - kl + 1) : 0;
-          if (o.nband == 0) o.k_lo = 0;
-          for (o.logK = std::max(4, ilog2(std::max(o.nband, 1))); o.logK < logp_tile; ++o.logK) {
-            const int nt = 1 << (o.logK - 4);
-            const int lo = o.k_lo - (((o.k_lo % nt) + nt) % nt);
-            if (o.nband + (o.k_lo - lo) <= (1 << o.logK) && lo >= -(Pb / 2)) {
-              o.nband += o.k_lo - lo;
-              o.k_lo = lo;
-              break;
-            }
-          }
-        };
-        RowDesc big = rd;
-        bool big_fits = false;
-        bool small_big = false;
-        if (ols_logp_s && p->ols_small_big && halo > p->ols_small_max_halo && halo <= (1 << (ols_logp_s + 1)) / 8 &&
-            p->logN >= ols_logp_s + 3) {                  // (halo <= 1/8 block: three quarters of every block transform are kept)
-          // blocks of two half-size tiles: the same 8192-point blocks as the default tile's, on 256-thread workgroups (four per CU)
-          RowDesc two = rd;
-          describe(ols_logp_s + 1, ols_logp_s, two);
-          if (two.logK <= ols_logp_s - 3) { od = two; lb = ols_logp_s + 1; grp = 0; small_big = true; }
-        }
-        if (small_big) {
-        } else if (ols_logp_s && halo <= p->ols_small_max_halo) {
-          describe(ols_logp_s, ols_logp_s, od);
-          lb = ols_logp_s; grp = 0;
-        } else {
-          int big_lb = 0;
-          if (ols_big4 && halo >= p->ols_big4_min_halo) {       // blocks of 4P points: the stores stay >= 128-byte segments
-            describe(ols_logp + 2, ols_logp, big);             // while K <= P/8, as for 2P
-            if (big.logK <= ols_logp - 3) { big_fits = true; big_lb = ols_logp + 2; }
-          }
-          if (!big_fits && ols_big && halo >= p->ols_big_min_halo && halo <= 2 * ols_hmax) {
-            big = rd;
-            describe(ols_logp + 1, ols_logp, big);
-            if (big.logK <= ols_logp - 3) { big_fits = true; big_lb = ols_logp + 1; }
-          }
-          if (big_fits) { od = big; lb = big_lb; }
-          else if (halo <= ols_hmax) describe(ols_logp, ols_logp, od);
-          else halo = 0;
-        }
-      }
-      // polynomial form (k_poly_coef / k_poly_rows): K' >= the support intervals of R = N / K' >= 64 samples (128 in
-      // complex64: a lane stores two outputs), degree D from the filter-weighted truncation rule
-      int poly_logk = 0, poly_deg = 0, poly_shift = 0;
-      if (poly_ok && rd.nband > 0) {
-        const int lk_max = std::min(p->poly_max_logk, p->logN - POLY_MIN_LOGR);
-        const int kc = rd.k_lo + (rd.nband >> 1);
-        PolyBandSamples band;
-        if (std::max(8, ilog2(rd.nband)) <= lk_max) poly_band_samples(mother, param, rd.a, kc, rd.k_lo, rd.nband, row_best, &band);
-        // The carrier k_c: the band's centre minimises the largest |theta|, but the bound weighs theta by the filter -- for a
-        // lopsided filter (Paul: peak at 9 % of its band; DOG) a carrier nearer the peak needs a lower degree at the same K',
-        // i.e. fewer or shorter coefficient planes.  Candidates: centre + c nband / 16, c = -7 ... 7 (the centre wins ties).
-        // (a filter whose peak sits within 1/16 band of the centre -- Morlet -- keeps the centre: the search is 15 evaluations of the
-        // degree rule per K', the whole cost of classifying a new scale grid)
-        int cmax = 0;
-        if (p->poly_carrier && band.npts > 16) {
-          int ipk = 0;
-          for (int i = 1; i < band.npts; ++i) if (band.g[i] > band.g[ipk]) ipk = i;
-          if (std::abs(2 * ipk - (band.npts - 1)) * 8 > band.npts) cmax = 7;
-        }
-        bool searched = false;
-        int c_prev = 0;
-        for (int lk = std::max(8, ilog2(rd.nband)); lk <= lk_max; ++lk) {
-          int best_deg = POLY_MAX_DEGREE + 2, best_c = 0;
-          auto try_c = [&](int cc) {
-            const double shift = double(cc) * double(rd.nband) / 16.0;
-            const int deg = poly_degree_for(band, lk, tol.support, std::round(shift), p->poly_cheb != 0, best_deg, cmax ? 4 : 1);
-            if (deg < best_deg || (deg == best_deg && std::abs(cc) < std::abs(best_c))) { best_deg = deg; best_c = cc; }
-          };
-          if (!searched) {                                   // all candidates at the first K', the neighbours of the winner after that
-            for (int c = 0; c <= cmax; ++c)
-              for (int sgn = (c ? -1 : 1); sgn <= 1; sgn += 2) try_c(sgn * c);
-            searched = true;
-          } else {
-            for (int cc = std::max(-cmax, c_prev - 1); cc <= std::min(cmax, c_prev + 1); ++cc) try_c(cc);
-          }
-          c_prev = best_c;
-          if (cmax && best_deg <= POLY_MAX_DEGREE)            // the winner's degree from every sample
-            best_deg = poly_degree_for(band, lk, tol.support, std::round(double(best_c) * double(rd.nband) / 16.0), p->poly_cheb != 0);
-          if (best_deg > POLY_MAX_DEGREE) continue;
-          poly_logk = lk; poly_deg = best_deg;
-          poly_shift = int(std::round(double(best_c) * double(rd.nband) / 16.0));
-          if (best_deg <= p->poly_degree) break;
-        }
-      }
-      if (poly_logk) {
-        rd.logK = poly_logk;
-        rd.nterms = poly_deg;
-        rd.kc_off = (rd.nband >> 1) + poly_shift;
-        poly_rows.push_back(rd);
-      } else if (p->narrow && need <= narrow_cap) {
-        rd.logK = need;
-        narrow_rows.push_back(rd);
-      } else if (halo) {
-        ols_rows.push_back({od, grp, lb, halo / 64});
-      } else if (k1_ok && (!k2_ok || t1 <= 3)) {
-        rd.logK = 10;                                   // k_narrow_ct_all (<= 4 terms) / k_narrow_ct_many
-        rd.nterms = t1;
-        narrow_rows.push_back(rd);
-      } else if (k2_ok) {
-        rd.logK = 11;                                   // k_narrow_ct_big
-        rd.nterms = t2;
-        narrow_rows.push_back(rd);
+      for (int cc = std::max(-cmax, c_prev - 1); cc <= std::min(cmax, c_prev + 1); ++cc) try_c(cc);
+    }
+    c_prev = best_c;
+    if (cmax && best_deg <= POLY_MAX_DEGREE)            // the winner's degree from every sample
+      best_deg = poly_degree_for(band, lk, g.tol.support, std::round(double(best_c) * double(rd.nband) / 16.0), p->poly_cheb != 0);
+    if (best_deg > POLY_MAX_DEGREE) continue;
+    *o = rd;
+    o->logK = lk; o->nterms = best_deg;
+    o->kc_off = (rd.nband >> 1) + int(std::round(double(best_c) * double(rd.nband) / 16.0));   // the carrier, from the centre
+    if (best_deg <= p->poly_degree) break;
+  }
+  return o->logK != 0;
+}
+
+// The rows of a call by form, in the order they were classified
+struct Forms {
+  std::vector<RowDesc> small, narrow, wide, poly;
+  std::vector<char> wide_clipped, wide_unclipped;   // per two-pass row: a candidate of the band-passed form (aols_pass)
+  std::vector<OlsRow> ols;
+};
+
+// Row j takes the first form it qualifies for: polynomial, band-limited on one tile, overlap-save, band-limited with several
+// terms at K = 1024, then at K = 2048, two-pass
+int classify_row(const cwt_plan* p, const RowRequest& r, const Gates& g, int j, Forms* f) {
+  RowSupport s;
+  if (const int rc = row_support(p, r, g, j, &s)) return rc;
+  RowDesc rd = s.rd;
+  if (g.use_small) { f->small.push_back(rd); return CWT_OK; }
+  const int need = std::max(4, ilog2(std::max(rd.nband, 1)));
+  // Support wider than 1024 bins: several aliased terms per FFT input, at K = 1024 (8192-point tiles) or, fp64
+  // only, K = 2048 (16384-point tiles, one workgroup per CU).  Measured us per row at N = 2^20 (tools/
+  // terms_sweep.py; two-pass: 9.1 fp64, 5.0 fp32): fp64 K = 1024: 4.3 / 4.9 / 6.1 / 7.2 / 8.5 for 2 / 3 / 4 / 6 / 8
+  // terms, K = 2048: 5.0 / 5.5 / 6.2 / 6.8 / 7.6 / 8.2 / 9.4 for 1 / 2 / 3 / 4 / 5 / 6 / 8; fp32 K = 1024: 2.9 /
+  // 3.2 / 3.5 / 4.3 / 4.8 / 5.3 for 2 / 3 / 4 / 6 / 8 / 10.  Hence: K = 1024 up to 3 terms, K = 2048 beyond.
+  const int t1 = (rd.nband + 1023) >> 10, t2 = (rd.nband + 2047) >> 11;
+  const bool k1_ok = p->narrow && g.multi_ok && t1 <= p->narrow_terms;
+  const bool k2_ok = p->narrow && g.big_ok && t2 <= p->big_terms;
+  RowDesc pr{};
+  OlsRow o{};
+  if (poly_candidate(p, r, g, s, &pr)) {
+    f->poly.push_back(pr);
+  } else if (p->narrow && need <= g.narrow_cap) {
+    rd.logK = need; f->narrow.push_back(rd);
+  } else if (ols_candidate(p, r, g, s, &o)) {
+    f->ols.push_back(o);
+  } else if (k1_ok && (!k2_ok || t1 <= 3)) {
+    rd.logK = 10; rd.nterms = t1; f->narrow.push_back(rd);   // k_narrow_ct_all (<= 4 terms) / k_narrow_ct_many
+  } else if (k2_ok) {
+    rd.logK = 11; rd.nterms = t2; f->narrow.push_back(rd);   // k_narrow_ct_big
+  } else {
+    // pass A class: how many bins k1 of a column can be non-zero (see pass_a_band_body)
+    const int span = (rd.nband >> g.tp_logk) + 2;
+    const int cls = span <= 16 ? 4 : span <= 64 ? 6 : span <= 256 ? 8 : 0;
+    rd.logK = (g.band_pass_a && cls && cls < p->logN - g.tp_logk) ? cls : 0;   // only if shorter than the column
+    f->wide.push_back(rd);
+    f->wide_clipped.push_back(g.aols_ok && !s.vanishes && rd.nband > 0 &&
+                              (r.mother == MOTHER_DOG ? (r.amp_re[j] == 0.0) != (r.amp_im[j] == 0.0) : r.amp_im[j] == 0.0));
+    f->wide_unclipped.push_back(g.aols_ok && s.vanishes && rd.nband > 0 && r.amp_im[j] == 0.0);
+  }
+  return CWT_OK;
+}
+
+// Rows of the band-passed form (A): the first class on 4096-point tiles, the second on 8192-point tiles, the mask's first bin
+struct AolsForm { std::vector<RowDesc> rows, rows2; AolsGeom geom{}, geom2{}; int ks = 1; };
+
+// Paul rows whose filter has died out at Nyquist (two-pass rows so far: the kink of f^m H(f) at f = 0 gives the wavelet its
+// 1/t^(m+1) tail, a halo of ~250 scales at 1e-10): the profile continued THROUGH f = 0 and cut below it by a taper of the
+// row's own width (AolsGeom::zc_*, k_aols_gtab).  Taper centre c, width c / 6 (u(0) = 1 - 1e-17).  The lobe below 0 is
+// ~c^m e^c / (2 m^m e^-m) times the filter; the band-passed signal has nothing there but rounding noise, so that factor times
+// the arithmetic's epsilon must stay a tenth of the accuracy target: c = 4 in fp64 at 1e-9 (x 1.5e3), not available in fp32.
+// Returns c, 0 if the continuation is not used.
+double paul_zc_centre(const cwt_plan* p, const RowRequest& r, const Gates& g) {
+  const int m = int(std::lround(r.param));
+  if (!p->aols_zc || r.mother != MOTHER_PAUL || m < 1 || r.rows_per_signal != 0) return 0;
+  const double mach = p->prec == 64 ? 1.2e-16 : 6e-8;
+  const double budget = 0.1 * std::max(g.tol.clip, 10 * mach) / mach;
+  const double peak = std::pow(double(m), m) * std::exp(-double(m));
+  for (double c : {4.0, 3.5, 3.0, 2.5, 2.0})
+    if (std::pow(c, m) * std::exp(c) * 0.5 / peak <= budget) return c;
+  return 0;
+}
+
+// One mask and one window for all rows of form A (from the smallest scale); false if there is none
+bool aols_window(const cwt_plan* p, const RowRequest& r, const Gates& g, const Forms& f, double zc_c, AolsGeom* ag, int* ks) {
+  double a_min = 0;
+  bool any_zc = false;
+  for (size_t i = 0; i < f.wide.size(); ++i) {
+    if (f.wide_clipped[i] && (a_min == 0 || f.wide[i].a < a_min)) a_min = f.wide[i].a;
+    any_zc = any_zc || (zc_c > 0 && f.wide_unclipped[i]);
+  }
+  if (!(a_min > 0 || any_zc)) return false;
+  ag->z = erfc_arg(std::max(g.tol.halo * 0.1, 1e-19));
+  if (r.mother == MOTHER_MORLET) {
+    // the filter of the smallest scale is above the support threshold from f1_lo on (negative: Morlet's Gaussian is
+    // not gated at f = 0, mothers.py:26-28); below it a taper of 1/32 cycle per sample, then the mask ends
+    ag->f1_lo = std::min(g.f_lo / (a_min * double(p->N)), 0.0);
+    ag->f_s = ag->f1_lo - 1.0 / 32.0;
+    if (0.5 + ag->f_s < 0.12) ag->f_s = ag->f1_lo - 1.0 / 128.0;
+    *ks = int(std::ceil(ag->f_s * double(p->N)));
+    return 0.5 + ag->f_s >= 0.10;                      // room for the taper above Nyquist
+  }
+  if (r.mother == MOTHER_DOG) {
+    // two-sided profile, smooth through f = 0: the mask is the positive bins 1 .. N/2 - 1 (the negative ones are their
+    // mirror image, added by the kernel's epilogue), the window continues the profile below 0 and tapers it there
+    // (a quarter cycle each side: the profile is NOT small there, so the tapers must be as gentle as the one above Nyquist)
+    ag->f1_lo = 0.0;
+    ag->f_s = -0.25;
+  } else {                                             // Paul: Heaviside -- the mask starts at bin 1
+    ag->f1_lo = ag->f_s = 1.0 / double(p->N);
+  }
+  *ks = 1;
+  return true;
+}
+
+// The halo of every two-pass row in form A: h (first class, <= 512), h2 (second class), zc (continued through f = 0)
+struct AolsHalos {
+  std::vector<int> h, h2;
+  std::vector<char> zc;
+  int hmax = 0, hmax2 = 0, cnt = 0, cnt2 = 0;
+};
+AolsHalos aols_halos(const cwt_plan* p, const RowRequest& r, const Gates& g, const Forms& f, const AolsGeom& ag) {
+  const size_t n = f.wide.size();
+  AolsHalos a;
+  a.h.assign(n, 0); a.h2.assign(n, 0); a.zc.assign(n, 0);
+  auto take = [&](size_t i, int h) {                   // continued through f = 0: 4096-point tiles up to a halo of 512,
+    if (h > 0 && h <= 512) { a.h[i] = h; ++a.cnt; a.hmax = std::max(a.hmax, h); }   // 8192-point tiles up to 2048
+    else if (h > 512) { a.h2[i] = h; ++a.cnt2; a.hmax2 = std::max(a.hmax2, h); }
+    return (a.zc[i] = h > 0) != 0;
+  };
+  const int m = int(std::lround(r.param)), rps = r.rows_per_signal > 0 ? r.rows_per_signal : r.nrows;
+  const double eps = std::max(g.tol.halo, p->prec == 64 ? 2e-14 : 5e-7);
+  std::vector<int> halo_of_scale(size_t(rps), -1);     // (a numeric tail search each: once per scale, not per signal)
+  const std::vector<double> window = aols_window_grid(ag, 512);
+  std::vector<double> window2;                          // ... on the grid of the long-halo search (made when a row asks for it)
+  double zc_f_safe = 0, zc_factor = 0, zc_dummy = 0;
+  if (ag.zc_c > 0) {
+    profile_support(MOTHER_PAUL, r.param, eps * 1e-3, &zc_dummy, &zc_f_safe);
+    zc_factor = zc_halo_factor(m, ag.zc_c, ag.zc_w, eps);
+  }
+  for (size_t i = 0; i < n; ++i) {
+    const double aN = f.wide[i].a * double(p->N);
+    double amp = 0;
+    if (ag.zc_c > 0 && f.wide_clipped[i] && aN > 4.0 * (ag.zc_c + 6.0 * ag.zc_w) &&   // filter alive at Nyquist AND room
+        take(i, aols_halo_zc(m, aN, ag.zc_c, ag.zc_w, eps, 2048, &amp, nullptr, ag.z)))  // for both continuations
+      continue;
+    if (ag.zc_c > 0 && f.wide_unclipped[i]) {
+      // scale-invariant halo where the filter has died out far below eps long before Nyquist, the numeric search otherwise
+      int h = 0;
+      if (0.5 * aN > zc_f_safe && zc_factor > 0) {
+        const double want = zc_factor * aN / (2.0 * 3.14159265358979323846) * 1.01 + 2.0;
+        h = want <= 2048.0 ? std::max(64, int((int64_t(std::ceil(want)) + 63) / 64 * 64)) : 0;
       } else {
-        // pass A class: how many bins k1 of a column can be non-zero (see pass_a_band_body)
-        const int span = (rd.nband >> two_pass_logk(p)) + 2;
-        const int cls = span <= 16 ? 4 : span <= 64 ? 6 : span <= 256 ? 8 : 0;
-        rd.logK = (band_pass_a && cls && cls < two_pass_logr) ? cls : 0;   // only if shorter than the column
-        wide_rows.push_back(rd);
-        wide_clipped.push_back(aols_ok && !vanishes && rd.nband > 0 &&
-                               (mother == MOTHER_DOG ? (amp_re[j] == 0.0) != (amp_im[j] == 0.0) : amp_im[j] == 0.0));
-        wide_unclipped.push_back(aols_ok && vanishes && rd.nband > 0 && amp_im[j] == 0.0);
+        h = aols_halo_zc(m, aN, ag.zc_c, ag.zc_w, eps, 2048, &amp);
       }
+      take(i, h);
+      continue;
+    }
+    if (!f.wide_clipped[i]) continue;
+    int& h = halo_of_scale[size_t(f.wide[i].out_row % rps)];
+    if (h < 0) h = aols_halo(r.mother, r.param, aN, ag, eps, 512, window);
+    a.h[i] = h;
+    if (h) { ++a.cnt; a.hmax = std::max(a.hmax, h); }
+    else if (p->aols_long && p->prec == 64 && r.rows_per_signal == 0 && r.mother != MOTHER_DOG && p->logN >= 16) {
+      // clipped rows whose kernel is longer than the 4096-point tile allows (fp64 Paul, s = 2.2 ... 11: the kink of f^m H(f) at
+      // f = 0 with no room for the continuation through it): the second class, 8192-point tiles, halos up to 2048
+      if (window2.empty()) window2 = aols_window_grid(ag, 2048);
+      const int h2 = aols_halo(r.mother, r.param, aN, ag, eps, 2048, window2);
+      if (h2 > 512) { a.h2[i] = h2; ++a.cnt2; a.hmax2 = std::max(a.hmax2, h2); }
     }
   }
-  // Rows clipped at Nyquist (so far two-pass rows) that can run as overlap-save rows on the band-passed complex signal:
-  // one mask and one window for all of them (from the smallest scale), the halo of each from its kernel, one halo class.
-  std::vector<RowDesc> aols_rows, aols2_rows;
-  AolsGeom ag{}, ag2{};
-  int aols_logp = 12, aols_ks = 1;
-  // Paul rows whose filter has died out at Nyquist (two-pass rows so far: the kink of f^m H(f) at f = 0 gives the wavelet its
-  // 1/t^(m+1) tail, a halo of ~250 scales at 1e-10): the profile continued THROUGH f = 0 and cut below it by a taper of the
-  // row's own width (AolsGeom::zc_*, k_aols_gtab).  Taper centre c, width c / 6 (u(0) = 1 - 1e-17).  The lobe below 0 is
-  // ~c^m e^c / (2 m^m e^-m) times the filter; the band-passed signal has nothing there but rounding noise, so that factor times
-  // the arithmetic's epsilon must stay a tenth of the accuracy target: c = 4 in fp64 at 1e-9 (x 1.5e3), not available in fp32.
-  const int paul_m = int(std::lround(param));
-  double zc_c = 0;
-  if (aols_ok && p->aols_zc && mother == MOTHER_PAUL && paul_m >= 1 && rows_per_signal == 0) {
-    const double mach = p->prec == 64 ? 1.2e-16 : 6e-8;
-    const double budget = 0.1 * std::max(tol.clip, 10 * mach) / mach;
-    const double peak = std::pow(double(paul_m), paul_m) * std::exp(-double(paul_m));
-    for (double c : {4.0, 3.5, 3.0, 2.5, 2.0})
-      if (std::pow(c, paul_m) * std::exp(c) * 0.5 / peak <= budget) { zc_c = c; break; }
+  if (a.cnt2 && !a.cnt) {                              // (the second class rides on the first one's band-passed signal: keep
+    a.cnt2 = 0;                                        // the layout simple -- no first class, no second)
+    std::fill(a.h2.begin(), a.h2.end(), 0);
   }
-  if (aols_ok) {
-    double a_min = 0;
-    bool any_zc = false;
-    for (size_t i = 0; i < wide_rows.size(); ++i) {
-      if (wide_clipped[i] && (a_min == 0 || wide_rows[i].a < a_min)) a_min = wide_rows[i].a;
-      any_zc = any_zc || (zc_c > 0 && wide_unclipped[i]);
+  return a;
+}
+
+// Rows clipped at Nyquist (so far two-pass rows) that can run as overlap-save rows on the band-passed complex signal leave the
+// two-pass rows for form A, if enough of them qualify (the band-passed signal costs about one two-pass row)
+void aols_pass(const cwt_plan* p, const RowRequest& r, const Gates& g, Forms* f, AolsForm* a) {
+  if (!g.aols_ok) return;
+  const double zc_c = paul_zc_centre(p, r, g);
+  AolsGeom &ag = a->geom, &ag2 = a->geom2;
+  if (!aols_window(p, r, g, *f, zc_c, &ag, &a->ks)) return;
+  ag.zc_c = ag2.zc_c = zc_c;
+  ag.zc_w = ag2.zc_w = zc_c / 6.0;
+  const AolsHalos h = aols_halos(p, r, g, *f, ag);
+  const int nb = g.aols_nbatch;
+  if (h.cnt % nb != 0 || (h.cnt + h.cnt2) / nb < std::max(1, p->aols_min_rows) || h.cnt == 0) return;
+  const int64_t N = p->N;
+  const int P = 1 << kAolsLogp, L = P - 2 * h.hmax;
+  ag.halo = h.hmax; ag.nrows = h.cnt / nb;            // (rows per signal)
+  ag.nblocks = int((r.out_ncols + L - 1) / L);
+  ag.ksp = int(std::ceil(ag.f_s * double(P)));
+  // the second class: 8192-point tiles, its own halo / block grid, its tables behind the first class's
+  const int P2 = 1 << 13, L2 = P2 - 2 * h.hmax2;
+  ag2.f_s = ag.f_s; ag2.f1_lo = ag.f1_lo; ag2.z = ag.z;
+  ag2.halo = h.hmax2; ag2.nrows = h.cnt2;
+  ag2.nblocks = h.cnt2 ? int((r.out_ncols + L2 - 1) / L2) : 0;
+  ag2.ksp = int(std::ceil(ag2.f_s * double(P2)));
+  long toff = 0, toff2 = long(ag.nrows) << kAolsLogp;
+  const int rps = r.rows_per_signal > 0 ? r.rows_per_signal : r.nrows;
+  std::vector<long> tab_of_scale(size_t(rps), -1);      // one filter table per scale, shared by the signals
+  std::vector<RowDesc> keep;
+  for (size_t i = 0; i < f->wide.size(); ++i) {
+    if (!h.h[i] && !h.h2[i]) { keep.push_back(f->wide[i]); continue; }
+    const int logp = h.h2[i] ? 13 : kAolsLogp;
+    RowDesc o = f->wide[i];
+    o.a = o.a * double(N >> logp);                     // profile argument per block bin
+    o.amp_re = r.amp_re[o.out_row] / double(1 << logp);   // 1/P of the block's inverse transform (x_M carries its own 1/N)
+    o.amp_im = o.nyq_re = o.nyq_im = 0.0;
+    o.k_lo = h.h2[i] ? ag2.ksp : ag.ksp; o.nband = 1 << logp;
+    o.logK = logp; o.nterms = 1;
+    o.aux_off = h.zc[i] ? 1 : 0;                       // continued through f = 0, or the plain window of the first class
+    if (h.h2[i]) { o.tab_off = toff2; toff2 += P2; a->rows2.push_back(o); continue; }
+    if (r.mother == MOTHER_DOG) {
+      const bool odd = (int(std::lround(r.param)) & 1) != 0;
+      o.nterms = odd ? 3 : 2;                          // W = 2 Re y | -2 Im y (table scale = the non-zero part of amp)
+      if (odd) o.amp_re = r.amp_im[o.out_row] / double(P);
+      const double pn = host_profile(r.mother, r.param, f->wide[i].a * double(N / 2)) * (odd ? -1.0 : 1.0) / double(N);
+      o.nyq_re = r.amp_re[o.out_row] * pn;             // F_j at the Nyquist bin (w = -pi / dt, wavelet.py:94) / N
+      o.nyq_im = r.amp_im[o.out_row] * pn;
     }
-    bool geom_ok = a_min > 0 || any_zc;
-    if (geom_ok) {
-      ag.z = erfc_arg(std::max(tol.halo * 0.1, 1e-19));
-      if (mother == MOTHER_MORLET) {
-        // the filter of the smallest scale is above the support threshold from f1_lo on (negative: Morlet's Gaussian is
-        // not gated at f = 0, mothers.py:26-28); below it a taper of 1/32 cycle per sample, then the mask ends
-        double s_lo, s_hi;
-        profile_support(mother, param, tol.support, &s_lo, &s_hi);
-        ag.f1_lo = std::min(s_lo / (a_min * double(N)), 0.0);
-        ag.f_s = ag.f1_lo - 1.0 / 32.0;
-        if (0.5 + ag.f_s < 0.12) ag.f_s = ag.f1_lo - 1.0 / 128.0;
-        geom_ok = 0.5 + ag.f_s >= 0.10;                   // room for the taper above Nyquist
-        aols_ks = int(std::ceil(ag.f_s * double(N)));
-      } else if (mother == MOTHER_DOG) {
-        // two-sided profile, smooth through f = 0: the mask is the positive bins 1 .. N/2 - 1 (the negative ones are their
-        // mirror image, added by the kernel's epilogue), the window continues the profile below 0 and tapers it there
-        // (a quarter cycle each side: the profile is NOT small there, so the tapers must be as gentle as the one above Nyquist)
-        ag.f1_lo = 0.0;
-        ag.f_s = -0.25;
-        aols_ks = 1;
-      } else {                                             // Paul: Heaviside -- the mask starts at bin 1
-        ag.f1_lo = ag.f_s = 1.0 / double(N);
-        aols_ks = 1;
-      }
-    }
-    std::vector<int> halos(wide_rows.size(), 0), halos2(wide_rows.size(), 0);
-    std::vector<char> zc_row(wide_rows.size(), 0);
-    int hmax_seen = 0, hmax2_seen = 0, cnt = 0, cnt2 = 0;
-    const int rps = rows_per_signal > 0 ? rows_per_signal : nrows;
-    if (geom_ok) {
-      const double eps = std::max(tol.halo, p->prec == 64 ? 2e-14 : 5e-7);
-      std::vector<int> halo_of_scale(size_t(rps), -1);     // (a numeric tail search each: once per scale, not per signal)
-      const std::vector<double> window = aols_window_grid(ag, 512);
-      std::vector<double> window2;                          // ... on the grid of the long-halo search (made when a row asks for it)
-      ag.zc_c = ag2.zc_c = zc_c;
-      ag.zc_w = ag2.zc_w = zc_c / 6.0;
-      double zc_f_safe = 0, zc_factor = 0, zc_dummy = 0;
-      if (zc_c > 0) {
-        profile_support(MOTHER_PAUL, param, eps * 1e-3, &zc_dummy, &zc_f_safe);
-        zc_factor = zc_halo_factor(paul_m, ag.zc_c, ag.zc_w, eps);
-      }
-      for (size_t i = 0; i < wide_rows.size(); ++i) {
-        const bool zc_clipped = zc_c > 0 && wide_clipped[i] && wide_rows[i].a * double(N) > 4.0 * (ag.zc_c + 6.0 * ag.zc_w);
-        if (zc_clipped) {                                  // filter alive at Nyquist AND room for both continuations
-          double amp = 0;
-          const int h = aols_halo_zc(paul_m, wide_rows[i].a * double(N), ag.zc_c, ag.zc_w, eps, 2048, &amp, nullptr, ag.z);
-          if (h > 0 && h <= 512) { halos[i] = h; zc_row[i] = 1; ++cnt; hmax_seen = std::max(hmax_seen, h); continue; }
-          if (h > 512) { halos2[i] = h; zc_row[i] = 1; ++cnt2; hmax2_seen = std::max(hmax2_seen, h); continue; }
-        }
-        if (zc_c > 0 && wide_unclipped[i]) {               // continued through f = 0: 4096-point tiles up to a halo of 512,
-          double amp = 0;                                  // 8192-point tiles up to 2048 (a second class, below)
-          // scale-invariant halo where the filter has died out far below eps long before Nyquist, the numeric search otherwise
-          int h = 0;
-          const double aN = wide_rows[i].a * double(N);
-          if (0.5 * aN > zc_f_safe && zc_factor > 0) {
-            const double want = zc_factor * aN / (2.0 * 3.14159265358979323846) * 1.01 + 2.0;
-            h = want <= 2048.0 ? std::max(64, int((int64_t(std::ceil(want)) + 63) / 64 * 64)) : 0;
-          } else {
-            h = aols_halo_zc(paul_m, aN, ag.zc_c, ag.zc_w, eps, 2048, &amp);
-          }
-          if (h > 0 && h <= 512) { halos[i] = h; zc_row[i] = 1; ++cnt; hmax_seen = std::max(hmax_seen, h); }
-          else if (h > 512) { halos2[i] = h; zc_row[i] = 1; ++cnt2; hmax2_seen = std::max(hmax2_seen, h); }
-          continue;
-        }
-        if (!wide_clipped[i]) continue;
-        int& h = halo_of_scale[size_t(wide_rows[i].out_row % rps)];
-        if (h < 0) h = aols_halo(mother, param, wide_rows[i].a * double(N), ag, eps, 512, window);
-        halos[i] = h;
-        if (halos[i]) { ++cnt; hmax_seen = std::max(hmax_seen, halos[i]); }
-        else if (p->aols_long && p->prec == 64 && rows_per_signal == 0 && mother != MOTHER_DOG && p->logN >= 16) {
-          // clipped rows whose kernel is longer than the 4096-point tile allows (fp64 Paul, s = 2.2 ... 11: the kink of f^m H(f) at
-          // f = 0 with no room for the continuation through it): the second class, 8192-point tiles, halos up to 2048
-          if (window2.empty()) window2 = aols_window_grid(ag, 2048);
-          const int h2 = aols_halo(mother, param, wide_rows[i].a * double(N), ag, eps, 2048, window2);
-          if (h2 > 512) { halos2[i] = h2; ++cnt2; hmax2_seen = std::max(hmax2_seen, h2); }
-        }
-      }
-      if (cnt2 && !cnt) {                                  // (the second class rides on the first one's band-passed signal: keep
-        cnt2 = 0;                                          // the layout simple -- no first class, no second)
-        std::fill(halos2.begin(), halos2.end(), 0);
-      }
-    }
-    if (geom_ok && cnt % aols_nbatch == 0 && (cnt + cnt2) / aols_nbatch >= std::max(1, p->aols_min_rows) && cnt > 0) {
-      aols_logp = 12;                                      // 4096-point tiles: four block transforms in flight per CU
-      const int P = 1 << aols_logp, L = P - 2 * hmax_seen;
-      ag.halo = hmax_seen;
-      ag.nrows = cnt / aols_nbatch;                         // per signal
-      ag.nblocks = int((out_ncols + L - 1) / L);
-      ag.ksp = int(std::ceil(ag.f_s * double(P)));
-      std::vector<RowDesc> keep;
-      long toff = 0;
-      std::vector<long> tab_of_scale(size_t(rps), -1);     // one filter table per scale, shared by the signals
-      // the second class: 8192-point tiles, its own halo / block grid, its tables behind the first class's
-      const int P2 = 1 << 13, L2 = P2 - 2 * hmax2_seen;
-      ag2.f_s = ag.f_s; ag2.f1_lo = ag.f1_lo; ag2.z = ag.z;
-      ag2.halo = hmax2_seen;
-      ag2.nrows = cnt2;
-      ag2.nblocks = cnt2 ? int((out_ncols + L2 - 1) / L2) : 0;
-      ag2.ksp = int(std::ceil(ag2.f_s * double(P2)));
-      long toff2 = long(ag.nrows) << aols_logp;
-      for (size_t i = 0; i < wide_rows.size(); ++i) {
-        if (halos2[i]) {
-          RowDesc o = wide_rows[i];
-          o.a = wide_rows[i].a * double(N >> 13);
-          o.amp_re = amp_re[o.out_row] / double(P2);
-          o.amp_im = 0.0;
-          o.k_lo = ag2.ksp; o.nband = P2;
-          o.logK = 13; o.nterms = 1;
-          o.nyq_re = o.nyq_im = 0.0;
-          o.aux_off = zc_row[i] ? 1 : 0;                    // continued through f = 0, or the plain window of the first class
-          o.tab_off = toff2;
-          toff2 += P2;
-          aols2_rows.push_back(o);
-          continue;
-        }
-        if (!halos[i]) { keep.push_back(wide_rows[i]); continue; }
-        RowDesc o = wide_rows[i];
-        o.a = wide_rows[i].a * double(N >> aols_logp);     // profile argument per block bin
-        o.amp_re = amp_re[o.out_row] / double(P);          // 1/P of the block's inverse transform (x_M carries its own 1/N)
-        o.amp_im = 0.0;
-        o.k_lo = ag.ksp; o.nband = P;
-        o.logK = aols_logp; o.nterms = 1;
-        o.nyq_re = o.nyq_im = 0.0;
-        o.aux_off = zc_row[i] ? 1 : 0;
-        if (mother == MOTHER_DOG) {
-          const int mm = int(std::lround(param));
-          const bool odd = (mm & 1) != 0;
-          o.nterms = odd ? 3 : 2;                           // W = 2 Re y | -2 Im y (table scale = the non-zero part of amp)
-          if (odd) o.amp_re = amp_im[o.out_row] / double(P);
-          const double pn = host_profile(mother, param, wide_rows[i].a * double(N / 2)) * (odd ? -1.0 : 1.0) / double(N);
-          o.nyq_re = amp_re[o.out_row] * pn;                // F_j at the Nyquist bin (w = -pi / dt, wavelet.py:94) / N
-          o.nyq_im = amp_im[o.out_row] * pn;
-        }
-        long& t = tab_of_scale[size_t(o.out_row % rps)];
-        if (t < 0) { t = toff; toff += P; }
-        o.tab_off = t;                                      // (spec_off stays the offset of the row's signal in the spectra)
-        aols_rows.push_back(o);
-      }
-      wide_rows.swap(keep);
-    }
+    long& t = tab_of_scale[size_t(o.out_row % rps)];
+    if (t < 0) { t = toff; toff += P; }
+    o.tab_off = t;                                     // (spec_off stays the offset of the row's signal in the spectra)
+    a->rows.push_back(o);
   }
-  // launch classes, in table order: 0 = k_narrow_ct_all (K <= 1024, <= 4 terms), 1 = k_narrow_ct_many (K = 1024,
-  // 5..16 terms), 2 = k_narrow_ct_big (K = 2048)
+  f->wide.swap(keep);
+}
+
+// The table's head: small | band-limited rows by launch class | two-pass.  Launch classes, in table order: 0 = k_narrow_ct_all
+// (K <= 1024, <= 4 terms), 1 = k_narrow_ct_many (K = 1024, 5..16 terms), 2 = k_narrow_ct_big (K = 2048)
+void narrow_layout(const cwt_plan* p, Forms* f, RowLayout* L) {
+  std::vector<RowDesc>& nr = f->narrow;
   auto group_key = [](const RowDesc& x) {
     const int cls = x.logK == 11 ? 2 : (x.nterms > 4 ? 1 : 0);
     return cls * 100000 + x.logK + 100 * x.nterms;
   };
-  std::stable_sort(narrow_rows.begin(), narrow_rows.end(),
-                   [&](const RowDesc& x, const RowDesc& y) { return group_key(x) < group_key(y); });
-  if (p->narrow_mix && p->use_ct && logP == (p->prec == 64 ? 13 : 14)) {   // (the generic kernels launch per (K, terms) group)
+  std::stable_sort(nr.begin(), nr.end(), [&](const RowDesc& x, const RowDesc& y) { return group_key(x) < group_key(y); });
+  if (p->narrow_mix && default_tile_ct(p)) {           // (the generic kernels launch per (K, terms) group)
     // Launch order inside k_narrow_ct_all: the rows are sorted light (K = 16: store bound) to heavy (K = 1024 with three
     // terms: the longest compute phase); consecutive rows share the CUs, so alternate the two ends of the list -- a CU's two
     // tile slots then hold one store-heavy and one compute-heavy tile instead of two of a kind.  (Complex64: the rows
     // that run on half-size tiles, K <= 512 with one term, stay a block of their own at the front.)
     auto zigzag = [&](size_t lo, size_t hi) {
-      std::vector<RowDesc> tmp(narrow_rows.begin() + lo, narrow_rows.begin() + hi);
+      std::vector<RowDesc> tmp(nr.begin() + lo, nr.begin() + hi);
       size_t a = 0, b = tmp.size();
-      for (size_t i = lo; i < hi; ++i) narrow_rows[i] = ((i - lo) & 1) ? tmp[--b] : tmp[a++];
+      for (size_t i = lo; i < hi; ++i) nr[i] = ((i - lo) & 1) ? tmp[--b] : tmp[a++];
     };
     size_t n0 = 0;
-    while (n0 < narrow_rows.size() && group_key(narrow_rows[n0]) < 100000) ++n0;        // class 0: k_narrow_ct_all
+    while (n0 < nr.size() && group_key(nr[n0]) < 100000) ++n0;   // class 0: k_narrow_ct_all
     size_t nh = 0;
     if (p->prec == 32 && p->narrow_small)
-      while (nh < n0 && narrow_rows[nh].logK <= 9 && narrow_rows[nh].nterms == 1) ++nh;
+      while (nh < n0 && nr[nh].logK <= 9 && nr[nh].nterms == 1) ++nh;
     if (nh > 1) zigzag(0, nh);
     if (n0 - nh > 1) zigzag(nh, n0);
   }
-  p->rt->table.clear();
-  p->rt->narrow_groups.clear();
-  p->rt->table.insert(p->rt->table.end(), small_rows.begin(), small_rows.end());
-  for (size_t i = 0; i < narrow_rows.size(); ++i) {
-    const int nt = narrow_rows[i].nterms;
-    if (p->rt->narrow_groups.empty() || p->rt->narrow_groups.back().logK != narrow_rows[i].logK ||
-        p->rt->narrow_groups.back().nterms != nt)
-      p->rt->narrow_groups.push_back({narrow_rows[i].logK, int(p->rt->table.size()), 0, nt});
-    p->rt->narrow_groups.back().count++;
-    p->rt->table.push_back(narrow_rows[i]);
+  L->table = f->small;
+  for (const RowDesc& r : nr) {
+    if (L->narrow_groups.empty() || L->narrow_groups.back().logK != r.logK || L->narrow_groups.back().nterms != r.nterms)
+      L->narrow_groups.push_back({r.logK, int(L->table.size()), 0, r.nterms});
+    L->narrow_groups.back().count++;
+    L->table.push_back(r);
   }
-  p->rt->wide_first = int(p->rt->table.size());
-  p->rt->table.insert(p->rt->table.end(), wide_rows.begin(), wide_rows.end());
-  p->rt->n_small = int(small_rows.size());
-  p->rt->n_narrow = int(narrow_rows.size());
-  p->rt->n_wide = int(wide_rows.size());
-  // Overlap-save rows, grouped into at most OLS_MAX_CLASSES halo classes.  A class of rows i..j (sorted by halo) runs
-  // at the largest halo H_j: every block transform yields P - 2 H_j columns, and the class pays one block spectrum per
-  // block on top of its rows -> cost (rows + w) * P / (P - 2 H_j); dynamic programme over the distinct halos.
-  p->rt->ols_first = int(p->rt->table.size());
-  p->rt->n_ols = int(ols_rows.size());
-  p->rt->ols_xs_elems = p->rt->ols_gt_elems = 0;
-  for (int g = 0; g < 2; ++g) {
-    auto& G = p->rt->ols_grp[g];
-    G.logp = g == 0 ? (ols_logp_s ? ols_logp_s : ols_logp) : ols_logp;
-    G.cls.n = 0; G.wgs = 0; G.wgs_base = 0; G.fwd_blocks[0] = G.fwd_blocks[1] = G.fwd_blocks[2] = 0; G.row_first = G.nrows = 0;
-    for (int i = 0; i < OLS_MAX_CLASSES; ++i) G.cls.wg_first[i] = 0x7fffffff;
+  L->wide_first = int(L->table.size());
+  L->table.insert(L->table.end(), f->wide.begin(), f->wide.end());
+  L->n_small = int(f->small.size()); L->n_narrow = int(nr.size()); L->n_wide = int(f->wide.size());
+}
+
+// Overlap-save rows of one block length, sorted by halo, in at most kmax halo classes.  A class of rows i..j runs at the
+// largest halo H_j: every block transform yields P_b - 2 H_j columns, and the class pays one block spectrum per block (w row
+// transforms) on top of its rows -> cost (rows + w) * P_b / (P_b - 2 H_j); dynamic programme over the distinct halos hv (units
+// of 64), pre[i] = rows with a halo below hv[i].  Returns the end of each class in hv.
+std::vector<int> halo_class_cuts(const std::vector<int>& hv, const std::vector<int>& pre, int kmax, int Pb, double w) {
+  const int nd = int(hv.size());
+  auto cost = [&](int i, int j) {                      // distinct halos i..j-1 as one class
+    return (double(pre[j] - pre[i]) + w) * double(Pb) / double(Pb - 128 * hv[j - 1]);
+  };
+  const double inf = 1e300;
+  std::vector<std::vector<double>> dp(kmax + 1, std::vector<double>(nd + 1, inf));
+  std::vector<std::vector<int>> from(kmax + 1, std::vector<int>(nd + 1, -1));
+  dp[0][0] = 0;
+  for (int k = 1; k <= kmax; ++k)
+    for (int j = 1; j <= nd; ++j)
+      for (int i = 0; i < j; ++i)
+        if (dp[k - 1][i] < inf && dp[k - 1][i] + cost(i, j) < dp[k][j]) { dp[k][j] = dp[k - 1][i] + cost(i, j); from[k][j] = i; }
+  int bestk = 1;
+  for (int k = 2; k <= kmax; ++k) if (dp[k][nd] < dp[bestk][nd]) bestk = k;
+  std::vector<int> cuts;
+  for (int k = bestk, j = nd; k >= 1; --k) { cuts.push_back(j); j = from[k][j]; }
+  std::reverse(cuts.begin(), cuts.end());
+  return cuts;
+}
+
+// Overlap-save rows behind the two-pass rows: by tile group, block length and halo class; the launch geometry of each group,
+// block-spectrum and filter-table offsets
+void ols_layout(const cwt_plan* p, const RowRequest& r, const Gates& g, std::vector<OlsRow>& rows, RowLayout* L) {
+  L->ols_first = int(L->table.size());
+  L->n_ols = int(rows.size());
+  L->ols_nbatch = g.ols_nbatch;
+  for (int gi = 0; gi < 2; ++gi) {
+    L->ols_grp[gi].logp = gi == 0 && g.ols_logp_s ? g.ols_logp_s : kOlsLogp;
+    for (int i = 0; i < OLS_MAX_CLASSES; ++i) L->ols_grp[gi].cls.wg_first[i] = 0x7fffffff;
   }
-  if (!ols_rows.empty()) {
-    // by tile group, then block length, then halo
-    // (batch: then scale by scale, the signals of a scale in order -- k_ols_ct indexes a class's rows that way)
-    const int rps = rows_per_signal > 0 ? rows_per_signal : 1 << 30;
-    std::stable_sort(ols_rows.begin(), ols_rows.end(), [rps](const OlsRow& x, const OlsRow& y) {
-      if (x.grp != y.grp) return x.grp < y.grp;
-      if (x.lb != y.lb) return x.lb < y.lb;
-      if (x.h64 != y.h64) return x.h64 < y.h64;
-      return x.rd.out_row % rps < y.rd.out_row % rps;       // stable: equal scales stay in signal order
-    });
-    long xs = 0;
-    int row0 = 0;                                                  // index into ols_rows
-    for (int g = 0; g < 2; ++g) {
-      auto& grp = p->rt->ols_grp[g];
-      OlsClasses& oc = grp.cls;
-      grp.row_first = row0;
-      long wg = 0;
-      for (int lb = grp.logp; lb <= grp.logp + 2; ++lb) {
-        int nr = 0;
-        while (row0 + nr < int(ols_rows.size()) && ols_rows[row0 + nr].grp == g && ols_rows[row0 + nr].lb == lb) ++nr;
-        if (!nr) continue;
-        const int Pb = 1 << lb, G = 1 << (lb - grp.logp);
-        std::vector<int> hv, cnt;                                   // distinct halos (units of 64) and their row counts
-        for (int i = row0; i < row0 + nr; ++i) {
-          if (hv.empty() || hv.back() != ols_rows[i].h64) { hv.push_back(ols_rows[i].h64); cnt.push_back(0); }
-          cnt.back()++;
-        }
-        const int nd = int(hv.size()), KC = (lb == grp.logp || !ols_big4) ? OLS_MAX_CLASSES / 2 : OLS_MAX_CLASSES / 4;
-        std::vector<int> pre(nd + 1, 0);
-        for (int i = 0; i < nd; ++i) pre[i + 1] = pre[i] + cnt[i];
-        auto cost = [&](int i, int j) {                             // distinct halos i..j-1 as one class
-          return (double(pre[j] - pre[i]) + p->ols_fwd_weight * ols_nbatch) * double(Pb) / double(Pb - 128 * hv[j - 1]);
-        };
-        const double inf = 1e300;
-        std::vector<std::vector<double>> dp(KC + 1, std::vector<double>(nd + 1, inf));
-        std::vector<std::vector<int>> from(KC + 1, std::vector<int>(nd + 1, -1));
-        dp[0][0] = 0;
-        for (int k = 1; k <= KC; ++k)
-          for (int j = 1; j <= nd; ++j)
-            for (int i = 0; i < j; ++i)
-              if (dp[k - 1][i] < inf && dp[k - 1][i] + cost(i, j) < dp[k][j]) { dp[k][j] = dp[k - 1][i] + cost(i, j); from[k][j] = i; }
-        int bestk = 1;
-        for (int k = 2; k <= KC; ++k) if (dp[k][nd] < dp[bestk][nd]) bestk = k;
-        std::vector<int> cuts;                                      // class boundaries in distinct-halo indices
-        for (int k = bestk, j = nd; k >= 1; --k) { cuts.push_back(j); j = from[k][j]; }
-        std::reverse(cuts.begin(), cuts.end());
-        int lo_d = 0;
-        long blk = 0;
-        const long stride = (Pb / 2) + 8;
-        for (size_t ci = 0; ci < cuts.size(); ++ci) {
-          const int hi_d = cuts[ci], H = 64 * hv[hi_d - 1], L = Pb - 2 * H;
-          OlsClass& k = oc.c[oc.n++];
-          k.halo = H;
-          k.logb = lb;
-          k.nsig = ols_nbatch;
-          k.nblocks = int((ols_ncols + L - 1) / L);
-          k.nrows = pre[hi_d] - pre[lo_d];
-          k.row_first = row0 - grp.row_first + pre[lo_d];
-          k.wg_first = int(wg);
-          k.blk_first = int(blk);
-          k.xs_off = xs;
-          // the 8 XCDs share the (signal, block) pairs: nblocks alone can be as few as 17 (N = 2^16), which would leave
-          // one XCD with 3 blocks and seven with 2 + an idle pass (measured: +40 % on that kernel)
-          // (complex64: a workgroup takes two blocks of a row, CWT_PAIR_F32)
-          const long nunits = ols_pairs(p->prec / 8, grp.logp) ? (k.nblocks + 1) / 2 : k.nblocks;
-          wg += ((nunits * ols_nbatch + 7) / 8) * 8 * (k.nrows / ols_nbatch) * G;
-          blk += k.nblocks;
-          xs += long(k.nblocks) * stride;
-          lo_d = hi_d;
-        }
-        grp.fwd_blocks[lb - grp.logp] = blk;
-        row0 += nr;
-        if (lb == grp.logp) grp.wgs_base = wg;
+  if (rows.empty()) return;
+  // by tile group, then block length, then halo
+  // (batch: then scale by scale, the signals of a scale in order -- k_ols_ct indexes a class's rows that way)
+  const int rps = r.rows_per_signal > 0 ? r.rows_per_signal : 1 << 30, nbatch = g.ols_nbatch;
+  std::stable_sort(rows.begin(), rows.end(), [rps](const OlsRow& x, const OlsRow& y) {
+    if (x.grp != y.grp) return x.grp < y.grp;
+    if (x.lb != y.lb) return x.lb < y.lb;
+    if (x.h64 != y.h64) return x.h64 < y.h64;
+    return x.rd.out_row % rps < y.rd.out_row % rps;       // stable: equal scales stay in signal order
+  });
+  long xs = 0; int row0 = 0;                              // (row0: index into rows)
+  for (int gi = 0; gi < 2; ++gi) {
+    auto& grp = L->ols_grp[gi];
+    OlsClasses& oc = grp.cls;
+    grp.row_first = row0;
+    long wg = 0;
+    for (int lb = grp.logp; lb <= grp.logp + 2; ++lb) {
+      int nr = 0;
+      while (row0 + nr < int(rows.size()) && rows[row0 + nr].grp == gi && rows[row0 + nr].lb == lb) ++nr;
+      if (!nr) continue;
+      const int Pb = 1 << lb, G = 1 << (lb - grp.logp);
+      std::vector<int> hv, pre{0};                        // distinct halos (units of 64), rows below each
+      for (int i = row0; i < row0 + nr; ++i) {
+        if (hv.empty() || hv.back() != rows[i].h64) { hv.push_back(rows[i].h64); pre.push_back(pre.back()); }
+        pre.back()++;
       }
-      grp.nrows = row0 - grp.row_first;
-      grp.wgs = wg;
-      for (int i = 0; i < OLS_MAX_CLASSES; ++i) oc.wg_first[i] = i < oc.n ? oc.c[i].wg_first : 0x7fffffff;
-    }
-    long gt_off = 0;                                            // filter tables: 2^logK entries per row (k_ols_gtab)
-    // batch: the table depends on the scale only (one per scale, shared by the signals); the block spectra are per
-    // signal, xs elements apart -- an overlap-save row reads its spectra at xs_dev + spec_off + class offset
-    std::vector<long> tab_of_scale(rows_per_signal > 0 ? rows_per_signal : 0, -1);
-    for (auto& r : ols_rows) {
-      r.rd.nterms = 1 << (r.lb - p->rt->ols_grp[r.grp].logp);   // nterms = workgroups per block
-      if (rows_per_signal > 0) {
-        long& t = tab_of_scale[r.rd.out_row % rows_per_signal];
-        if (t < 0) { t = gt_off; gt_off += 1L << r.rd.logK; }
-        r.rd.tab_off = t;
-        r.rd.spec_off = long(r.rd.out_row / rows_per_signal) * xs;
-      } else {
-        r.rd.tab_off = gt_off;
-        gt_off += 1L << r.rd.logK;
-        r.rd.spec_off = 0;
+      const int kmax = (lb == grp.logp || !g.ols_big4) ? OLS_MAX_CLASSES / 2 : OLS_MAX_CLASSES / 4;
+      const std::vector<int> cuts = halo_class_cuts(hv, pre, kmax, Pb, p->ols_fwd_weight * nbatch);
+      int lo_d = 0; long blk = 0;
+      for (const int hi_d : cuts) {
+        const int H = 64 * hv[hi_d - 1], Lk = Pb - 2 * H;
+        OlsClass& k = oc.c[oc.n++];
+        k.halo = H; k.logb = lb; k.nsig = nbatch;
+        k.nblocks = int((r.ols_ncols + Lk - 1) / Lk);
+        k.nrows = pre[hi_d] - pre[lo_d];
+        k.row_first = row0 - grp.row_first + pre[lo_d];
+        k.wg_first = int(wg); k.blk_first = int(blk); k.xs_off = xs;
+        // the 8 XCDs share the (signal, block) pairs: nblocks alone can be as few as 17 (N = 2^16), which would leave
+        // one XCD with 3 blocks and seven with 2 + an idle pass (measured: +40 % on that kernel)
+        // (complex64: a workgroup takes two blocks of a row, CWT_PAIR_F32)
+        const long nunits = ols_pairs(p->prec / 8, grp.logp) ? (k.nblocks + 1) / 2 : k.nblocks;
+        wg += ((nunits * nbatch + 7) / 8) * 8 * (k.nrows / nbatch) * G;
+        blk += k.nblocks;
+        xs += long(k.nblocks) * ((Pb / 2) + 8);
+        lo_d = hi_d;
       }
-      p->rt->table.push_back(r.rd);
+      grp.fwd_blocks[lb - grp.logp] = blk;
+      row0 += nr;
+      if (lb == grp.logp) grp.wgs_base = wg;
     }
-    p->rt->ols_gt_elems = gt_off;
-    p->rt->ols_xs_sig = xs;
-    p->rt->ols_xs_elems = xs * ols_nbatch;
+    grp.nrows = row0 - grp.row_first; grp.wgs = wg;
+    for (int i = 0; i < oc.n; ++i) oc.wg_first[i] = oc.c[i].wg_first;
   }
-  p->rt->ols_nbatch = ols_nbatch;
-  p->rt->aols_first = int(p->rt->table.size());
-  p->rt->n_aols = int(aols_rows.size());
-  p->rt->aux_first = -1;
-  p->rt->aols_gt_elems = 0;
-  p->rt->n_aols2 = 0;
-  if (!aols_rows.empty()) {
-    p->rt->table.insert(p->rt->table.end(), aols_rows.begin(), aols_rows.end());
-    p->rt->aols_logp = aols_logp;
-    p->rt->aols_geom = ag;
-    const bool pair32 = aols_pairs(p->prec / 8);                // a workgroup of k_aols_rows takes two blocks of a row
-    p->rt->aols_wgs = long(((pair32 ? (ag.nblocks + 1) / 2 : ag.nblocks) + 7) / 8) * 8 * ag.nrows;
-    p->rt->aols_gt_elems = long(ag.nrows) << aols_logp;
-    p->rt->aols_nbatch = aols_nbatch;
-    // second class (Paul rows continued through f = 0 on 8192-point tiles): right behind the first in the table
-    p->rt->aols2_first = int(p->rt->table.size());
-    p->rt->n_aols2 = int(aols2_rows.size());
-    p->rt->n_aols += p->rt->n_aols2;
-    if (!aols2_rows.empty()) {
-      p->rt->table.insert(p->rt->table.end(), aols2_rows.begin(), aols2_rows.end());
-      p->rt->aols2_geom = ag2;
-      p->rt->aols2_wgs = long(((pair32 ? (ag2.nblocks + 1) / 2 : ag2.nblocks) + 7) / 8) * 8 * ag2.nrows;
-      p->rt->aols_gt_elems += long(ag2.nrows) << 13;
+  long gt_off = 0;                                        // filter tables: 2^logK entries per row (k_ols_gtab)
+  // batch: the table depends on the scale only (one per scale, shared by the signals); the block spectra are per
+  // signal, xs elements apart -- an overlap-save row reads its spectra at xs_dev + spec_off + class offset
+  std::vector<long> tab_of_scale(r.rows_per_signal > 0 ? r.rows_per_signal : 0, -1);
+  for (auto& o : rows) {
+    o.rd.nterms = 1 << (o.lb - L->ols_grp[o.grp].logp);  // nterms = workgroups per block
+    if (r.rows_per_signal > 0) {
+      long& t = tab_of_scale[o.rd.out_row % r.rows_per_signal];
+      if (t < 0) { t = gt_off; gt_off += 1L << o.rd.logK; }
+      o.rd.tab_off = t;
+      o.rd.spec_off = long(o.rd.out_row / r.rows_per_signal) * xs;
+    } else {
+      o.rd.tab_off = gt_off; gt_off += 1L << o.rd.logK; o.rd.spec_off = 0;
     }
-    RowDesc m{};                                          // (zero-initialised: no Nyquist term) the mask as a row: profile 1 (DOG m = 0 at a = 0) on [k_s, N/2)
-    m.a = 0.0; m.amp_re = 1.0 / double(N); m.amp_im = 0.0;
-    m.k_lo = aols_ks; m.nband = int(N / 2) - aols_ks;
-    m.logK = 0; m.nterms = 1; m.tab_off = 0;
-    p->rt->aux_first = int(p->rt->table.size());
-    for (int b = 0; b < aols_nbatch; ++b) {               // one per signal
-      m.out_row = b;
-      m.spec_off = rows_per_signal > 0 ? long(spec_ld) * b : 0;
-      p->rt->table.push_back(m);
-    }
+    L->table.push_back(o.rd);
   }
-  // polynomial rows: by K', then by degree; coefficient offsets; the workgroups of k_poly_coef per class
-  p->rt->poly_first = int(p->rt->table.size());
-  p->rt->n_poly = int(poly_rows.size());
-  p->rt->poly_chunks.clear();
-  p->rt->poly_coef_elems = 0;
-  if (!poly_rows.empty()) {
-    // largest K' first (their planes are the bulk and their k_poly_coef tiles the slowest to get going), then by degree
-    std::stable_sort(poly_rows.begin(), poly_rows.end(), [](const RowDesc& x, const RowDesc& y) {
-      return x.logK != y.logK ? x.logK > y.logK : x.nterms < y.nterms;
-    });
-    const size_t esz = p->esize() * 2;
-    size_t cap = ~size_t(0);
-    if (p->poly_chunk_mb > 0) {                             // as few chunks as the limit allows, of about equal volume
-      size_t total = 0;
-      for (const RowDesc& r : poly_rows) total += (size_t(r.nterms) + 1) * (size_t(1) << r.logK) * esz;
-      const size_t limit = size_t(p->poly_chunk_mb) << 20, n = (total + limit - 1) / limit;
-      cap = n > 1 ? (total + n - 1) / n : ~size_t(0);
-    }
-    long off = 0, boff = 0;
-    size_t vol = 0;
-    for (size_t i = 0; i < poly_rows.size(); ++i) {
-      RowDesc& r = poly_rows[i];
-      r.tab_off = off;                                      // planes: (D + 1) K' complex
-      off += (long(r.nterms) + 1) << r.logK;
-      r.aux_off = boff;                                     // band: K' complex
-      boff += 1L << r.logK;
-      const size_t bytes = (size_t(r.nterms) + 1) * (size_t(1) << r.logK) * esz;
-      if (p->rt->poly_chunks.empty() || vol + bytes / 2 > cap) {
-        p->rt->poly_chunks.emplace_back();
-        p->rt->poly_chunks.back().row_first = int(i);
-        vol = 0;
-      }
-      vol += bytes;
-      auto& ch = p->rt->poly_chunks.back();
-      ch.nrows++;
-      ch.max_logk = std::max(ch.max_logk, r.logK);
-      PolyClasses& pc = ch.cls;
-      if (pc.n == 0 || pc.c[pc.n - 1].logK != r.logK) {
-        if (pc.n == POLY_MAX_CLASSES) return fail(CWT_EINVAL, "too many polynomial-row classes");
-        pc.c[pc.n++] = PolyClass{r.logK, int(i) - ch.row_first, 0, 0, 0, 0};
-      }
-      PolyClass& c = pc.c[pc.n - 1];
-      c.nrows++;
-      c.ndeg = std::max(c.ndeg, r.nterms + 1);
-    }
-    for (auto& ch : p->rt->poly_chunks)
-      for (int i = 0; i < ch.cls.n; ++i) {                  // per tile size (launch): classes in table order
-        PolyClass& c = ch.cls.c[i];
-        const int tile = std::max(12, c.logK);                // log2 of the workgroup tile
-        const long tb = 1L << (tile - c.logK);
-        long& wg = ch.wgs[tile - 12];
-        c.wg_first = int(wg);
-        wg += (long(c.nrows) * c.ndeg + tb - 1) / tb;
-        // the single launch on 4096-point tiles: K' > 4096 takes K' / 4096 workgroups per job, in groups of 8 jobs
-        const long jobs = long(c.nrows) * c.ndeg, s = c.logK > 12 ? 1L << (c.logK - 12) : 1;
-        c.wg_first1 = int(ch.wgs_all);
-        ch.wgs_all += c.logK > 12 ? ((jobs + 7) / 8) * 8 * s : (((jobs << c.logK) + 4095) / 4096 + 7) / 8 * 8;
-      }
-    p->rt->poly_coef_elems = off;
-    p->rt->poly_band_elems = boff;
-    // tables of the economised weights: one per (K', D) pair, (D + 1) x (K' + 1) reals (|kappa| = 0 ... K'; the sign of an odd
-    // degree at negative kappa is applied by the kernel)
-    p->rt->poly_rtabs.clear();
-    p->rt->poly_rtab_elems = 0;
-    if (p->poly_cheb)
-      for (RowDesc& r : poly_rows) {
-        long at = -1;
-        for (const auto& t : p->rt->poly_rtabs) if (t.logK == r.logK && t.deg == r.nterms) at = t.off;
-        if (at < 0) {
-          at = p->rt->poly_rtab_elems;
-          p->rt->poly_rtabs.push_back({r.logK, r.nterms, at});
-          p->rt->poly_rtab_elems += (long(r.nterms) + 1) * ((1L << r.logK) + 1);
-        }
-        r.rtab_off = at;
-      }
-    p->rt->table.insert(p->rt->table.end(), poly_rows.begin(), poly_rows.end());
+  L->ols_gt_elems = gt_off; L->ols_xs_sig = xs; L->ols_xs_elems = xs * nbatch;
+}
+
+// Rows of form A behind the overlap-save rows: the first class, the second, then one mask pseudo-row per signal (the mask as
+// a row: profile 1 -- DOG m = 0 at a = 0 -- on [k_s, N/2))
+void aols_layout(const cwt_plan* p, const RowRequest& r, const Gates& g, const AolsForm& a, RowLayout* L) {
+  L->aols_first = int(L->table.size());
+  L->n_aols = int(a.rows.size() + a.rows2.size());
+  if (a.rows.empty()) return;
+  const bool pair32 = aols_pairs(p->prec / 8);            // a workgroup of k_aols_rows takes two blocks of a row
+  const auto wgs = [pair32](const AolsGeom& ag) { return long(((pair32 ? (ag.nblocks + 1) / 2 : ag.nblocks) + 7) / 8) * 8 * ag.nrows; };
+  L->table.insert(L->table.end(), a.rows.begin(), a.rows.end());
+  L->aols_logp = kAolsLogp; L->aols_geom = a.geom; L->aols_wgs = wgs(a.geom);
+  L->aols_gt_elems = long(a.geom.nrows) << kAolsLogp; L->aols_nbatch = g.aols_nbatch;
+  L->aols2_first = int(L->table.size()); L->n_aols2 = int(a.rows2.size());
+  if (!a.rows2.empty()) {
+    L->table.insert(L->table.end(), a.rows2.begin(), a.rows2.end());
+    L->aols2_geom = a.geom2; L->aols2_wgs = wgs(a.geom2);
+    L->aols_gt_elems += long(a.geom2.nrows) << 13;
   }
+  RowDesc m{};                                            // (zero-initialised: no Nyquist term)
+  m.amp_re = 1.0 / double(p->N); m.nterms = 1;
+  m.k_lo = a.ks; m.nband = int(p->N / 2) - a.ks;
+  L->aux_first = int(L->table.size());
+  for (int b = 0; b < g.aols_nbatch; ++b) {
+    m.out_row = b;
+    m.spec_off = r.rows_per_signal > 0 ? long(r.spec_ld) * b : 0;
+    L->table.push_back(m);
+  }
+}
+
+// Polynomial rows at the end of the table: by K', then by degree; chunks, classes and workgroups of k_poly_coef, coefficient
+// and band offsets, the tables of economised weights
+int poly_layout(const cwt_plan* p, std::vector<RowDesc>& rows, RowLayout* L) {
+  L->poly_first = int(L->table.size());
+  L->n_poly = int(rows.size());
+  if (rows.empty()) return CWT_OK;
+  // largest K' first (their planes are the bulk and their k_poly_coef tiles the slowest to get going), then by degree
+  std::stable_sort(rows.begin(), rows.end(), [](const RowDesc& x, const RowDesc& y) {
+    return x.logK != y.logK ? x.logK > y.logK : x.nterms < y.nterms;
+  });
+  const size_t esz = p->esize() * 2;
+  size_t cap = ~size_t(0);
+  if (p->poly_chunk_mb > 0) {                             // as few chunks as the limit allows, of about equal volume
+    size_t total = 0;
+    for (const RowDesc& r : rows) total += (size_t(r.nterms) + 1) * (size_t(1) << r.logK) * esz;
+    const size_t limit = size_t(p->poly_chunk_mb) << 20, n = (total + limit - 1) / limit;
+    cap = n > 1 ? (total + n - 1) / n : ~size_t(0);
+  }
+  long off = 0, boff = 0;
+  size_t vol = 0;
+  for (size_t i = 0; i < rows.size(); ++i) {
+    RowDesc& r = rows[i];
+    r.tab_off = off;                                      // planes: (D + 1) K' complex
+    off += (long(r.nterms) + 1) << r.logK;
+    r.aux_off = boff;                                     // band: K' complex
+    boff += 1L << r.logK;
+    const size_t bytes = (size_t(r.nterms) + 1) * (size_t(1) << r.logK) * esz;
+    if (L->poly_chunks.empty() || vol + bytes / 2 > cap) { L->poly_chunks.push_back({int(i)}); vol = 0; }
+    vol += bytes;
+    auto& ch = L->poly_chunks.back();
+    ch.nrows++;
+    ch.max_logk = std::max(ch.max_logk, r.logK);
+    PolyClasses& pc = ch.cls;
+    if (pc.n == 0 || pc.c[pc.n - 1].logK != r.logK) {
+      if (pc.n == POLY_MAX_CLASSES) return fail(CWT_EINVAL, "too many polynomial-row classes");
+      pc.c[pc.n++] = PolyClass{r.logK, int(i) - ch.row_first, 0, 0, 0, 0};
+    }
+    PolyClass& c = pc.c[pc.n - 1];
+    c.nrows++;
+    c.ndeg = std::max(c.ndeg, r.nterms + 1);
+  }
+  for (auto& ch : L->poly_chunks)
+    for (int i = 0; i < ch.cls.n; ++i) {                  // per tile size (launch): classes in table order
+      PolyClass& c = ch.cls.c[i];
+      const int tile = std::max(12, c.logK);              // log2 of the workgroup tile
+      const long tb = 1L << (tile - c.logK);
+      long& wg = ch.wgs[tile - 12];
+      c.wg_first = int(wg);
+      wg += (long(c.nrows) * c.ndeg + tb - 1) / tb;
+      // the single launch on 4096-point tiles: K' > 4096 takes K' / 4096 workgroups per job, in groups of 8 jobs
+      const long jobs = long(c.nrows) * c.ndeg, s = c.logK > 12 ? 1L << (c.logK - 12) : 1;
+      c.wg_first1 = int(ch.wgs_all);
+      ch.wgs_all += c.logK > 12 ? ((jobs + 7) / 8) * 8 * s : (((jobs << c.logK) + 4095) / 4096 + 7) / 8 * 8;
+    }
+  L->poly_coef_elems = off; L->poly_band_elems = boff;
+  // tables of the economised weights: one per (K', D) pair, (D + 1) x (K' + 1) reals (|kappa| = 0 ... K'; the sign of an odd
+  // degree at negative kappa is applied by the kernel)
+  if (p->poly_cheb)
+    for (RowDesc& r : rows) {
+      long at = -1;
+      for (const auto& t : L->poly_rtabs) if (t.logK == r.logK && t.deg == r.nterms) at = t.off;
+      if (at < 0) {
+        at = L->poly_rtab_elems;
+        L->poly_rtabs.push_back({r.logK, r.nterms, at});
+        L->poly_rtab_elems += (long(r.nterms) + 1) * ((1L << r.logK) + 1);
+      }
+      r.rtab_off = at;
+    }
+  L->table.insert(L->table.end(), rows.begin(), rows.end());
+  return CWT_OK;
+}
+
+}  // namespace
+
+// Classifies the rows of call r (the first form each qualifies for) and lays them out in the current slot, whose previous
+// layout is replaced whole.  Table order: small | narrow | two-pass | overlap-save | A | A2 | mask | polynomial
+// (cwt_plan_row_classes, serial_schedule and the launches rely on it).
+int build_row_table(cwt_plan* p, const RowRequest& r) {
+  if (r.mother < MOTHER_MORLET || r.mother > MOTHER_TABLE) return fail(CWT_EINVAL, "unknown mother id");
+  const Gates g = gates(p, r);
+  Forms f;
+  for (int j = 0; j < r.nrows; ++j)
+    if (const int rc = classify_row(p, r, g, j, &f)) return rc;
+  AolsForm a;
+  aols_pass(p, r, g, &f, &a);
+  RowLayout L;
+  narrow_layout(p, &f, &L);
+  ols_layout(p, r, g, f.ols, &L);
+  aols_layout(p, r, g, a, &L);
+  if (const int rc = poly_layout(p, f.poly, &L)) return rc;
+  *static_cast<RowLayout*>(p->rt) = std::move(L);
   return CWT_OK;
 }
 
