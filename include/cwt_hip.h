@@ -142,6 +142,8 @@ int cwt_plan_set_stream(cwt_plan* plan, void* hip_stream);
  *                  spectra on the caller's stream (their rows follow at a kernel boundary) and the forward FFT on a side
  *                  stream, on half-size tiles ("fft_aside_small"); 3 = 2 with ONE wait on the caller's stream.  Default 2 for
  *                  precision 64 (measured -1 % at config 2, -5.7 % for fp64 Paul), 0 for precision 32 (+-0 / +1.4 %)
+ *   "adjoint_poly" 0 = cwt_adjoint_rows takes every row through its general path (default 1: the polynomial rows through the
+ *                  transpose of their form)
  *   "poly_carrier" 0 = the carrier of a polynomial row is the centre bin of its band (default 1: the bin, of 15 candidates, at which
  *                  the filter-weighted degree bound is lowest -- for a lopsided filter (Paul, DOG) near its peak: half the
  *                  intervals at the same degree; fp64 Paul: coefficient planes 143 -> 73 MB)
@@ -235,6 +237,24 @@ int cwt_forward_fft(cwt_plan* plan, const void* x_dev, int64_t n0, void* xhat_de
 int cwt_transform_rows(cwt_plan* plan, const void* xhat_dev, int mother, double param, double dt,
                        const double* scales_host, int nrows, void* W_dev, int64_t ldw,
                        int64_t ncols);
+
+/* Adjoint (transpose) of the rows above, for nbatch real signals: with A the linear map x -> W of cwt_transform (zero padding to
+ * nfft, the rows of `scales`, the trim to ncols = n0 columns),
+ *   xbar = Re A^H G,   i.e.   xbar[n] = Re (1/nfft) sum_k e^{+2 pi i k n / nfft} sum_j conj(F_j[k]) DFT_nfft(pad G_j)[k],  n < ncols,
+ * so that Re sum_{j,n} conj(G[j, n]) W[j, n](x) = sum_n x[n] xbar[n] for every real x: the vector-Jacobian product of the
+ * transform (what a reverse-mode autodiff needs for dL/dx from dL/dW).  G_dev: nbatch x nrows x ldg complex (signal b at
+ * G_dev + b*g_batch_ld elements), the first ncols columns read; xbar_dev: nbatch x xbar_ld reals of the plan's precision, the first
+ * ncols written, or added to them with accumulate = 1 (partial adjoints of a scale-sharded transform sum in place).
+ * The row table and its cache entry are cwt_transform's for the same arguments (no second classification after a forward call);
+ * every truncation derives from the plan's accuracy target (cwt_plan_set_tolerance), as in the forward: at round-off xbar is the
+ * dense Re A^H G to rounding.  Polynomial rows (form P) go through the exact transpose of that form -- per interval the moments
+ * of the demodulated input, D + 1 short transforms, the forward's weights and filter -- all other rows through the filter on
+ * their support band after an nfft-point transform of the input row (option "adjoint_poly" = 0: every row).  Deterministic: no
+ * floating-point atomics, a signal's result does not depend on the batch around it.  Queued on the plan's stream, no host
+ * synchronisation.  Built-in mothers only.                                                                                     */
+int cwt_adjoint_rows(cwt_plan* plan, const void* G_dev, int nbatch, int64_t g_batch_ld, int64_t ldg, int64_t ncols,
+                     int mother, double param, double dt, const double* scales_host, int nrows,
+                     void* xbar_dev, int64_t xbar_ld, int accumulate);
 
 /* The whole device-resident transform in one call -- wavelet.py:91 (forward FFT, written to xhat_dev: nfft complex, the
  * caller needs it for the 5th return value of wavelet.py:123-124) and :94-106 (rows of W) -- for callers that still hold

@@ -44,6 +44,8 @@ SYMBOLS = [
                                      C.c_int, _P, C.c_int64, C.c_int64]),
     ("cwt_transform", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double),
                                 C.c_int, _P, _P, C.c_int64, C.c_int64]),
+    ("cwt_adjoint_rows", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double,
+                                   C.POINTER(C.c_double), C.c_int, _P, C.c_int64, C.c_int]),
     ("cwt_forward_fft_n", C.c_int, [_P, _P, C.c_int64, _P]),
     ("cwt_transform_rows_n", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double),
                                        C.c_int, _P, C.c_int64]),
@@ -392,6 +394,15 @@ class Plan:
         s = np.ascontiguousarray(scales, dtype=np.float64)
         self.lib.check(self.lib.cwt_transform(self.h, _P(x_dev), n0, mother, float(param), float(dt), _dptr(s), s.size,
                                               _P(xhat_dev) if xhat_dev else None, _P(W_dev), ldw, ncols))
+
+    @_locked
+    def adjoint_rows(self, G_dev: int, nbatch: int, g_batch_ld: int, ldg: int, ncols: int, mother: int, param: float,
+                     dt: float, scales, xbar_dev: int, xbar_ld: int, accumulate: bool = False):
+        """xbar = Re A^H G of the transform's rows (cwt_adjoint_rows): G nbatch x nrows x ldg complex, xbar nbatch x xbar_ld
+        reals, the first ncols columns of each; accumulate=True adds to xbar."""
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        self.lib.check(self.lib.cwt_adjoint_rows(self.h, _P(G_dev), nbatch, g_batch_ld, ldg, ncols, mother, float(param),
+                                                 float(dt), _dptr(s), s.size, _P(xbar_dev), xbar_ld, int(bool(accumulate))))
 
     @_locked
     def forward_fft_n(self, x_dev: int, n0: int, xhat_dev: int):

@@ -397,7 +397,7 @@ int cwt_plan_destroy(cwt_plan* p) {
   for (auto& t : p->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   for (auto e : p->free_events) (void)hipEventDestroy(e);
   void* bufs[] = {p->tw_all, p->twn_lo, p->weights_dev, p->Z, p->xs, p->xm, p->xsa, p->pcoef, p->pband, p->range_dev, p->hx, p->hxhat, p->hW,
-                  p->bs_khat[0], p->bs_khat[1], p->bs_a, p->bs_spec, p->bs_par};
+                  p->bs_khat[0], p->bs_khat[1], p->bs_a, p->bs_spec, p->bs_par, p->adj_spec, p->adj_acc};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (auto& t : p->slots) {
     if (t.gt_dev) (void)hipFree(t.gt_dev);
@@ -406,6 +406,9 @@ int cwt_plan_destroy(cwt_plan* p) {
     if (t.rows_dev) (void)hipFree(t.rows_dev);
     if (t.rows_pinned) (void)hipHostFree(t.rows_pinned);
     if (t.uploaded) (void)hipEventDestroy(t.uploaded);
+    if (t.adj_dev) (void)hipFree(t.adj_dev);
+    if (t.adj_pinned) (void)hipHostFree(t.adj_pinned);
+    if (t.adj_uploaded) (void)hipEventDestroy(t.adj_uploaded);
   }
   if (p->hstage) (void)hipHostFree(p->hstage);
   for (int i = 0; i < 2; ++i) {
@@ -466,6 +469,7 @@ int cwt_plan_set_option(cwt_plan* p, const char* key, int64_t value) {
   else if (k == "poly_cheb") p->poly_cheb = value != 0;
   else if (k == "poly_degree") { if (value < 2 || value > POLY_MAX_DEGREE) return fail(CWT_EINVAL, "poly_degree in [2, 24]"); p->poly_degree = int(value); }
   else if (k == "queue_probe") { p->queue_probe = value != 0; }
+  else if (k == "adjoint_poly") p->adjoint_poly = value != 0;
   else if (k == "poly_chunk_mb") { if (value < 0 || value > 4096) return fail(CWT_EINVAL, "poly_chunk_mb in [0, 4096] (0 = one chunk)"); p->poly_chunk_mb = int(value); }
   else if (k == "poly_max_logk") { if (value < 8 || value > 14) return fail(CWT_EINVAL, "poly_max_logk in [8, 14]"); p->poly_max_logk = int(value); }
   else if (k == "poly_min_logn") { if (value < 14 || value > 24) return fail(CWT_EINVAL, "poly_min_logn in [14, 24]"); p->poly_min_logn = int(value); }
@@ -643,6 +647,24 @@ int cwt_transform_rows(cwt_plan* p, const void* xhat_dev, int mother, double par
   if (!rc && p->logN >= 18 && !p->profile) rc = ensure_distinct_queues(p);
   if (rc) return rc;
   return queue_rows(p, xhat_dev, mother_of(mother, param), nrows, W_dev, ldw, ncols);
+}
+
+// The transpose of cwt_transform_rows.  The row table is the one cwt_transform builds for the same scales and ncols (the forward of a
+// training step has classified and cached it already); the rows of form P may go through the transpose of that form.
+int cwt_adjoint_rows(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld, int64_t ldg, int64_t ncols, int mother,
+                     double param, double dt, const double* scales, int nrows, void* xbar_dev, int64_t xbar_ld, int accumulate) {
+  if (!p || !G_dev || !scales || !xbar_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (mother == MOTHER_TABLE) return fail(CWT_EINVAL, "adjoint: a built-in mother is needed (a filter bank has no adjoint here)");
+  if (nbatch < 1) return fail(CWT_EINVAL, "nbatch must be >= 1");
+  if (ncols < 1 || ncols > p->N || ldg < ncols || xbar_ld < ncols) return fail(CWT_EINVAL, "need 1 <= ncols <= nfft, ldg >= ncols, xbar_ld >= ncols");
+  if (nbatch > 1 && (g_batch_ld < int64_t(nrows) * ldg)) return fail(CWT_EINVAL, "g_batch_ld must be >= nrows * ldg");
+  HIPCHECK(hipSetDevice(p->device));
+  const int rc = prepare_rows_table(p, true, mother, param, dt, scales, nrows, ncols, ncols);
+  if (rc) return rc;
+  return by_precision(p, [&](auto t) {
+    return adjoint_impl<decltype(t)>(p, G_dev, nbatch, g_batch_ld, ldg, ncols, mother_of(mother, param), nrows, xbar_dev, xbar_ld,
+                                     accumulate);
+  });
 }
 
 int cwt_transform(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double param, double dt,

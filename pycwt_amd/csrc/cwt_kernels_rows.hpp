@@ -753,7 +753,8 @@ k_poly_band(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ rows, 
 // Transform `job` of the class = (row, degree): job = row * ndeg + d; its input is the row's band times (i theta)^d / d!.
 // Tiles of 4096 points (256 threads, four workgroups per CU) wherever K' allows: these launches sit on the critical path of the
 // step (k_poly_rows waits for them) and are latency bound -- one 16384-point workgroup per CU for everything measured 67 us.
-template <typename T, int LOGK, int LOGP>
+// ADJ (cwt_adjoint_rows): the input of a job is its own plane, in place, and is not weighted (the transpose weighs the results).
+template <typename T, int LOGK, int LOGP, bool ADJ = false>
 __device__ __forceinline__ void poly_coef_body(const cplx<T>* __restrict__ yb, const RowDesc* __restrict__ rows,
                                                const cplx<T>* __restrict__ tw_all, const PolyClass& pc,
                                                unsigned local_wg, cplx<T>* __restrict__ coef, T* lds, const T* __restrict__ rtab) {
@@ -770,12 +771,14 @@ __device__ __forceinline__ void poly_coef_body(const cplx<T>* __restrict__ yb, c
   live = live && d <= rd.nterms;                              // nterms = the row's degree D
   T re[16], im[16];
   if (live) {
-    const cplx<T>* y = yb + rd.aux_off + f.j;
+    const cplx<T>* y = ADJ ? coef + rd.tab_off + (long(d) << LOGK) + f.j : yb + rd.aux_off + f.j;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {                            // all loads first
       const cplx<T> v = y[e * NT];
       re[e] = v.x; im[e] = v.y;
     }
+  }
+  if (live && !ADJ) {
     const int klo = -rd.kc_off;                               // kappa of the first band bin
     const T tscale = T(3.14159265358979323846 / double(K));
     const T ifact = T(inv_factorial(d));
@@ -789,7 +792,7 @@ __device__ __forceinline__ void poly_coef_body(const cplx<T>* __restrict__ yb, c
       if (d & 2) { vr = -vr; vi = -vi; }
       re[e] = vr; im[e] = vi;
     }
-  } else {
+  } else if (!live) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) { re[e] = T(0); im[e] = T(0); }
   }
@@ -800,7 +803,7 @@ __device__ __forceinline__ void poly_coef_body(const cplx<T>* __restrict__ yb, c
   for (int e = 0; e < 16; ++e) out[e * NT] = mk<T>(re[e], im[e]);
 }
 
-template <typename T, int LOGP>
+template <typename T, int LOGP, bool ADJ = false>
 __global__ void __launch_bounds__(1 << (LOGP - 4), 4)
 k_poly_coef(const cplx<T>* __restrict__ yb, const RowDesc* __restrict__ rows, const cplx<T>* __restrict__ tw_all,
             PolyClasses cls, cplx<T>* __restrict__ coef, const T* __restrict__ rtab) {
@@ -816,7 +819,7 @@ k_poly_coef(const cplx<T>* __restrict__ yb, const RowDesc* __restrict__ rows, co
   if (!found) return;
   const unsigned local = blockIdx.x - unsigned(pc.wg_first);
 #define CWT_POLY_CASE(LK) \
-  case LK: if constexpr (LK >= LK_LO && LK <= LK_HI) poly_coef_body<T, LK, LOGP>(yb, rows, tw_all, pc, local, coef, lds, rtab); break;
+  case LK: if constexpr (LK >= LK_LO && LK <= LK_HI) poly_coef_body<T, LK, LOGP, ADJ>(yb, rows, tw_all, pc, local, coef, lds, rtab); break;
   switch (pc.logK) {
     CWT_POLY_CASE(8) CWT_POLY_CASE(9) CWT_POLY_CASE(10) CWT_POLY_CASE(11) CWT_POLY_CASE(12) CWT_POLY_CASE(13)
     CWT_POLY_CASE(14)
@@ -1133,6 +1136,145 @@ k_poly_rows(const RowDesc* __restrict__ rows, const cplx<T>* __restrict__ coef, 
     default: break;
   }
 #undef CWT_POLYR_CASE
+}
+
+
+// ---- adjoint of the row transform (cwt_adjoint_rows): xbar = Re A^H G ----------------------------------------------------------
+// With Y_j = xhat F_j / N (RowDesc::amp carries the 1/N) the forward is W_j = IDFT_N(Y_j) unnormalised; its transpose, in the
+// conjugated form every kernel below accumulates, is
+//     acc[k] = sum_j (F_j[k] / N) conj(DFT_N(G_j)[k]),     xbar[n] = Re DFT_N(acc)[n]   (= Re DFT_N^H(conj acc)[n]),
+// so the forward's own filter_value(x, rd, mo, k) = x F_j[k] / N serves unchanged.  Every sum over rows runs in a fixed order
+// inside one thread: no atomics, the same bits on every run.
+
+// General path, one chunk of rows: acc[k] += sum_r F_r[k]/N conj(spec[r][k]) over the chunk's rows in table order, bins inside
+// a row's support only.  grid = N / 256, 256 threads.
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_adj_accum(const cplx<T>* __restrict__ spec, const RowDesc* __restrict__ rows, int cnt, Mother mo, int logN,
+            cplx<T>* __restrict__ acc) {
+  const int N = 1 << logN, k = int(blockIdx.x) * 256 + int(threadIdx.x);
+  if (k >= N) return;
+  const int ks = signed_bin(k, N);
+  T sr = T(0), si = T(0);
+  for (int r = 0; r < cnt; ++r) {
+    const RowDesc rd = rows[r];
+    if (unsigned(ks - rd.k_lo) >= unsigned(rd.nband)) continue;
+    const cplx<T> x = spec[(long(r) << logN) + k];
+    const cplx<T> v = filter_value<T>(mk<T>(x.x, -x.y), rd, mo, ks);
+    sr += v.x; si += v.y;
+  }
+  const cplx<T> a = acc[k];
+  acc[k] = mk<T>(a.x + sr, a.y + si);
+}
+
+// xbar[n] (+)= Re y[n], n < n0
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_adj_out(const cplx<T>* __restrict__ y, long n0, T* __restrict__ xbar, int accumulate) {
+  const long n = long(blockIdx.x) * 256 + threadIdx.x;
+  if (n >= n0) return;
+  xbar[n] = accumulate ? xbar[n] + y[n].x : y[n].x;
+}
+
+// Transpose of form P, step 1 (the mirror of k_poly_rows): per interval m of a polynomial row the moments of the demodulated,
+// conjugated input row,  nu_d[m] = sum_r u_r^d e^{2 pi i k_c n / N} conj(G[out_row][n]),  n = R m + r < n0,  d = 0 ... D,
+// written as the row's coefficient planes (the same place and layout as the forward's a_d).  A thread sums L = max(64, R / 256)
+// consecutive samples in order (its loads independent of one another), the g = R / L threads of an interval -- adjacent lanes of
+// one workgroup -- then add their partial sums in a fixed binary tree through LDS, degree by degree: no atomics, no shuffles.
+// grid = (N / (256 * 64), rows) x 256 threads, 256 complex of LDS (a workgroup covers 256 L samples; the ones beyond a row's N samples leave at once).
+template <typename T, int D>
+__device__ __forceinline__ void poly_moments_body(const cplx<T>* __restrict__ G, long n0, const RowDesc& rd, const TwN<T>& twn,
+                                                  int logN, cplx<T>* __restrict__ coef, cplx<T>* red) {
+  const int logR = logN - rd.logK, logL = logR - 8 > 6 ? logR - 8 : 6, logg = logR - logL;
+  const int t = int(threadIdx.x), L = 1 << logL;
+  const long nb = (long(blockIdx.x) << (logL + 8)) + (long(t) << logL);       // this thread's first sample
+  if ((long(blockIdx.x) << (logL + 8)) >= (1L << logN)) return;                // (uniform: the whole workgroup)
+  const unsigned nmask = unsigned((1 << logN) - 1);
+  const unsigned kc = unsigned(rd.k_lo + rd.kc_off);
+  const T scale = T(2) / T(1 << logR);
+  T ar[D + 1], ai[D + 1];
+#pragma unroll
+  for (int d = 0; d <= D; ++d) { ar[d] = T(0); ai[d] = T(0); }
+  const int r0 = int(nb & ((1L << logR) - 1));                                 // position inside the interval
+  const int rend = n0 - nb < long(L) ? int(n0 - nb > 0 ? n0 - nb : 0) : L;
+  for (int i = 0; i < rend; ++i) {
+    const unsigned n = unsigned(nb + i);
+    const cplx<T> g = G[n];
+    const cplx<T> w = twn((kc * n) & nmask);
+    T vr = g.x * w.x + g.y * w.y, vi = g.x * w.y - g.y * w.x;                  // conj(g) e^{2 pi i k_c n / N}
+    const T u = T(r0 + i) * scale - T(1);
+#pragma unroll
+    for (int d = 0; d <= D; ++d) {
+      ar[d] += vr; ai[d] += vi;
+      vr *= u; vi *= u;
+    }
+  }
+  const long m = nb >> logR;
+  const int g = 1 << logg;
+  cplx<T>* out = coef + rd.tab_off + m;
+#pragma unroll
+  for (int d = 0; d <= D; ++d) {
+    red[t] = mk<T>(ar[d], ai[d]);
+    __syncthreads();
+    for (int s = 1; s < g; s <<= 1) {
+      if ((t & (2 * s - 1)) == 0) { const cplx<T> a = red[t], b = red[t + s]; red[t] = mk<T>(a.x + b.x, a.y + b.y); }
+      __syncthreads();
+    }
+    if ((t & (g - 1)) == 0) out[long(d) << rd.logK] = red[t];
+    __syncthreads();
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_poly_moments(const cplx<T>* __restrict__ G, long ldg, long n0, const RowDesc* __restrict__ rows, TwN<T> twn, int logN,
+               cplx<T>* __restrict__ coef) {
+  HIP_DYNAMIC_SHARED(double2, lds_raw)
+  cplx<T>* red = reinterpret_cast<cplx<T>*>(lds_raw);             // 256 complex
+  const RowDesc rd = rows[blockIdx.y];
+  const cplx<T>* g = G + long(rd.out_row) * ldg;
+#define CWT_POLYM_CASE(DD) case DD: poly_moments_body<T, DD>(g, n0, rd, twn, logN, coef, red); break;
+  switch (rd.nterms) {
+    CWT_POLYM_CASE(2) CWT_POLYM_CASE(4) CWT_POLYM_CASE(6) CWT_POLYM_CASE(8) CWT_POLYM_CASE(10) CWT_POLYM_CASE(12)
+    CWT_POLYM_CASE(14) CWT_POLYM_CASE(16) CWT_POLYM_CASE(18) CWT_POLYM_CASE(20) CWT_POLYM_CASE(22) CWT_POLYM_CASE(24)
+    default: break;
+  }
+#undef CWT_POLYM_CASE
+}
+
+// Transpose of form P, step 3 (after the K'-point transforms of the planes, k_poly_coef<..., true>): per bin k = k_c + kappa of a
+// row's support,  acc[k] += F[k]/N e^{i pi kappa / K'} sum_d i^d r_d(theta_kappa) P_d[kappa mod K']  -- the forward's weights
+// w_d(kappa) and filter; P_d = sum_m nu_d[m] e^{2 pi i kappa m / K'} is conj(DFT_K'(mu_d)) of the unconjugated moments.  Rows of
+// the chunk in table order.  Signed bins [ks0, ks0 + nbins) (the union of the chunk's bands): grid = nbins / 256.
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_poly_adj_accum(const cplx<T>* __restrict__ coef, const RowDesc* __restrict__ rows, int cnt, Mother mo, TwN<T> twn, int logN,
+                 const T* __restrict__ rtab, int ks0, int nbins, cplx<T>* __restrict__ acc) {
+  const int N = 1 << logN, i = int(blockIdx.x) * 256 + int(threadIdx.x);
+  if (i >= nbins) return;
+  const int ks = ks0 + i, k = ks & (N - 1);
+  T sr = T(0), si = T(0);
+  for (int r = 0; r < cnt; ++r) {
+    const RowDesc rd = rows[r];
+    if (unsigned(ks - rd.k_lo) >= unsigned(rd.nband)) continue;
+    const int K = 1 << rd.logK, kap = ks - (rd.k_lo + rd.kc_off);
+    const cplx<T>* pl = coef + rd.tab_off + (kap & (K - 1));
+    const T tscale = T(3.14159265358979323846 / double(K));
+    T br = T(0), bi = T(0);
+    for (int d = 0; d <= rd.nterms; ++d) {
+      const T pw = poly_weight<T>(rtab, rd, K, kap, d, tscale, T(inv_factorial(d)));
+      const cplx<T> v = pl[long(d) << rd.logK];
+      T vr = v.x * pw, vi = v.y * pw;
+      if (d & 1) { const T tmp = vr; vr = -vi; vi = tmp; }        // times i^d
+      if (d & 2) { vr = -vr; vi = -vi; }
+      br += vr; bi += vi;
+    }
+    const cplx<T> ph = twn((unsigned(kap) << (logN - rd.logK - 1)) & unsigned(N - 1));   // e^{i pi kappa / K'}
+    const cplx<T> v = filter_value<T>(cmul<T>(mk<T>(br, bi), ph), rd, mo, ks);
+    sr += v.x; si += v.y;
+  }
+  const cplx<T> a = acc[k];
+  acc[k] = mk<T>(a.x + sr, a.y + si);
 }
 
 }  // namespace cwt

@@ -986,6 +986,123 @@ int launch_ols_early(cwt_plan* p, const void* x_dev, int64_t n0) {
   return CWT_OK;
 }
 
+// ---- adjoint of the rows (cwt_adjoint_rows) ---------------------------------------------------------------------------------
+// The rows of the current table that take the general path -- every row, or (option "adjoint_poly") every row but those of form P --
+// in out_row order, on their plain supports: uploaded once per row table and option value through the slot's own staging buffer.
+inline int upload_adjoint_rows(cwt_plan* p, int nrows, bool use_poly) {
+  cwt_plan::RowTable* t = p->rt;
+  if (t->adj_poly == int(use_poly)) return CWT_OK;
+  if (int(t->base.size()) != nrows) return fail(CWT_EINVAL, "adjoint: the row table does not describe this call");
+  std::vector<char> skip(size_t(nrows), 0);
+  if (use_poly)
+    for (int i = 0; i < t->n_poly; ++i) skip[size_t(t->table[size_t(t->poly_first + i)].out_row)] = 1;
+  t->adj_rows.clear();
+  for (int j = 0; j < nrows; ++j) if (!skip[size_t(j)]) t->adj_rows.push_back(j);
+  const size_t cap = size_t(p->max_rows) * sizeof(RowDesc);
+  if (!t->adj_dev && hipMalloc(reinterpret_cast<void**>(&t->adj_dev), cap) != hipSuccess) return fail(CWT_ENOMEM, "device allocation failed");
+  if (!t->adj_pinned && hipHostMalloc(reinterpret_cast<void**>(&t->adj_pinned), cap) != hipSuccess)
+    return fail(CWT_ENOMEM, "pinned allocation failed");
+  if (!t->adj_uploaded) HIPCHECK(hipEventCreateWithFlags(&t->adj_uploaded, hipEventDisableTiming));
+  else HIPCHECK(hipEventSynchronize(t->adj_uploaded));        // (the slot's previous copy: long done unless tables flip back to back)
+  for (size_t i = 0; i < t->adj_rows.size(); ++i) t->adj_pinned[i] = t->base[size_t(t->adj_rows[i])];
+  if (!t->adj_rows.empty())
+    HIPCHECK(hipMemcpyAsync(t->adj_dev, t->adj_pinned, t->adj_rows.size() * sizeof(RowDesc), hipMemcpyHostToDevice, p->stream));
+  HIPCHECK(hipEventRecord(t->adj_uploaded, p->stream));
+  t->adj_poly = int(use_poly);
+  return CWT_OK;
+}
+
+// xbar_b (+)= Re A^H G_b for every signal b (cwt_hip.h).  Per signal: the accumulator is zeroed; the general rows go in chunks of
+// chunk_rows_of rows through the forward transform of their zero-padded inputs (cwt_fft_rows' kernels) and k_adj_accum; the
+// polynomial rows chunk by chunk through k_poly_moments, the K'-point transforms of k_poly_coef (in place) and k_poly_adj_accum;
+// one N-point transform of the accumulator gives xbar.  Fixed order throughout: a signal's bits do not depend on the batch.
+template <typename T>
+int adjoint_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld, int64_t ldg, int64_t ncols, const Mother& mo,
+                 int nrows, void* xbar_dev, int64_t xbar_ld, int accumulate) {
+  cwt_plan::RowTable* rt = p->rt;
+  const int logN = p->logN;
+  const int64_t N = p->N;
+  const bool use_poly = p->adjoint_poly && rt->n_poly > 0;
+  int rc = check_geometry(p);
+  if (!rc) rc = upload_adjoint_rows(p, nrows, use_poly);
+  if (rc) return rc;
+  const int ngen = int(rt->adj_rows.size());
+  const int chunk = ngen ? balanced_chunk(p, ngen) : 1;
+  rc = grow(&p->adj_spec, &p->adj_spec_bytes, size_t(chunk) * size_t(N) * sizeof(cplx<T>), p->stream);
+  if (!rc) rc = grow(&p->adj_acc, &p->adj_acc_bytes, size_t(N) * sizeof(cplx<T>), p->stream);
+  if (!rc && use_poly) rc = grow(&p->pcoef, &p->pcoef_bytes, size_t(rt->poly_coef_elems) * sizeof(cplx<T>), p->stream);
+  if (rc) return rc;
+  const T* rtab = static_cast<const T*>(rt->prt_dev);
+  if (use_poly && rt->poly_rtab_elems > 0 && (!rtab || rt->prt_bytes < size_t(rt->poly_rtab_elems) * sizeof(T)))
+    return fail(CWT_EINVAL, "polynomial rows without their weight tables (fill_poly_tables was not run for this row table)");
+  static const bool once = (allow_big_lds(&k_poly_coef<T, 13, true>), allow_big_lds(&k_poly_coef<T, 14, true>), true);
+  (void)once;
+  cplx<T>* spec = static_cast<cplx<T>*>(p->adj_spec);
+  cplx<T>* acc = static_cast<cplx<T>*>(p->adj_acc);
+  cplx<T>* coef = static_cast<cplx<T>*>(p->pcoef);
+  const cplx<T>* tw = static_cast<const cplx<T>*>(p->tw_all);
+  const unsigned bins = unsigned((N + 255) / 256);
+  auto lds_of = [](int lp) { return ((size_t(1) << lp) + (size_t(1) << (lp - 4))) * sizeof(T); };
+  for (int b = 0; b < nbatch; ++b) {
+    const cplx<T>* G = static_cast<const cplx<T>*>(G_dev) + size_t(b) * size_t(g_batch_ld);
+    HIPCHECK(hipMemsetAsync(acc, 0, size_t(N) * sizeof(cplx<T>), p->stream));
+    for (int first = 0; first < ngen; first += chunk) {
+      const int cnt = std::min(chunk, ngen - first);
+      for (int i = 0; i < cnt;) {                       // runs of consecutive rows of G: one forward transform call each
+        const int j0 = rt->adj_rows[size_t(first + i)];
+        int run = 1;
+        while (i + run < cnt && rt->adj_rows[size_t(first + i + run)] == j0 + run) ++run;
+        rc = fft_rows_impl<T, IN_CPLX>(p, G + size_t(j0) * size_t(ldg), ldg, run, ncols, spec + size_t(i) * size_t(N));
+        if (rc) return rc;
+        i += run;
+      }
+      rc = timed_launch(p, KC_ADJOINT, [&] {
+        hipLaunchKernelGGL((k_adj_accum<T>), dim3(bins), dim3(256), 0, p->stream, static_cast<const cplx<T>*>(spec),
+                           rt->adj_dev + first, cnt, mo, logN, acc);
+      });
+      if (rc) return rc;
+    }
+    for (size_t c = 0; use_poly && c < rt->poly_chunks.size(); ++c) {
+      const auto& ch = rt->poly_chunks[c];
+      const RowDesc* rows = rt->rows_dev + rt->poly_first + ch.row_first;
+      rc = timed_launch(p, KC_ADJOINT, [&] {
+        for (int r0 = 0; r0 < ch.nrows; r0 += kMaxGridY)
+          hipLaunchKernelGGL((k_poly_moments<T>), dim3(unsigned(std::max<int64_t>(1, N >> 14)), std::min(kMaxGridY, ch.nrows - r0)), dim3(256),
+                             256 * sizeof(cplx<T>), p->stream, G, long(ldg), long(ncols), rows + r0, twn_of<T>(p), logN, coef);
+      });
+      if (!rc && ch.wgs[2]) rc = timed_launch(p, KC_POLY_COEF, [&] {
+        hipLaunchKernelGGL((k_poly_coef<T, 14, true>), dim3(unsigned(ch.wgs[2])), dim3(1024), lds_of(14), p->stream,
+                           static_cast<const cplx<T>*>(nullptr), rows, tw, ch.cls, coef, rtab); });
+      if (!rc && ch.wgs[1]) rc = timed_launch(p, KC_POLY_COEF, [&] {
+        hipLaunchKernelGGL((k_poly_coef<T, 13, true>), dim3(unsigned(ch.wgs[1])), dim3(512), lds_of(13), p->stream,
+                           static_cast<const cplx<T>*>(nullptr), rows, tw, ch.cls, coef, rtab); });
+      if (!rc && ch.wgs[0]) rc = timed_launch(p, KC_POLY_COEF, [&] {
+        hipLaunchKernelGGL((k_poly_coef<T, 12, true>), dim3(unsigned(ch.wgs[0])), dim3(256), lds_of(12), p->stream,
+                           static_cast<const cplx<T>*>(nullptr), rows, tw, ch.cls, coef, rtab); });
+      int ks0 = int(N / 2), ks1 = -int(N / 2);            // the union of the chunk's bands (narrow rows: a few thousand bins)
+      for (int i = 0; i < ch.nrows; ++i) {
+        const RowDesc& r = rt->table[size_t(rt->poly_first + ch.row_first + i)];
+        ks0 = std::min(ks0, r.k_lo);
+        ks1 = std::max(ks1, r.k_lo + r.nband);
+      }
+      if (!rc && ks1 > ks0) rc = timed_launch(p, KC_ADJOINT, [&] {
+        hipLaunchKernelGGL((k_poly_adj_accum<T>), dim3(unsigned((ks1 - ks0 + 255) / 256)), dim3(256), 0, p->stream,
+                           static_cast<const cplx<T>*>(coef), rows, ch.nrows, mo, twn_of<T>(p), logN, rtab, ks0, ks1 - ks0, acc);
+      });
+      if (rc) return rc;
+    }
+    rc = fft_rows_impl<T, IN_CPLX>(p, acc, N, 1, N, spec);
+    if (rc) return rc;
+    rc = timed_launch(p, KC_ADJOINT, [&] {
+      hipLaunchKernelGGL((k_adj_out<T>), dim3(unsigned((ncols + 255) / 256)), dim3(256), 0, p->stream,
+                         static_cast<const cplx<T>*>(spec), long(ncols), static_cast<T*>(xbar_dev) + size_t(b) * size_t(xbar_ld),
+                         accumulate);
+    });
+    if (rc) return rc;
+  }
+  return CWT_OK;
+}
+
 template <typename T>
 int upload_reals(cwt_plan* p, const double* v, int n) {          // -> p->weights_dev as T[n]
   // two staging buffers used in turn; the only wait is for the copy that left this buffer two calls ago
@@ -1211,7 +1328,8 @@ int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g
   X int random_normal_impl<T>(cwt_plan*, uint64_t, uint64_t, int64_t, double, void*);                                             \
   X int ar1_filter_impl<T>(cwt_plan*, const void*, int64_t, int64_t, double, void*);                                               \
   X int forward_fft_n_impl<T>(cwt_plan*, const void*, int64_t, void*);                                                              \
-  X int transform_rows_n_impl<T>(cwt_plan*, const void*, int64_t, int, double, double, const double*, int, void*, int64_t);
+  X int transform_rows_n_impl<T>(cwt_plan*, const void*, int64_t, int, double, double, const double*, int, void*, int64_t);        \
+  X int adjoint_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int64_t, const Mother&, int, void*, int64_t, int);
 
 #ifndef CWT_LAUNCH_TU
 CWT_LAUNCH_TEMPLATES(extern template, double)

@@ -45,7 +45,7 @@ int fail(int code, const std::string& msg);
 
 enum KernelClass { KC_FWD_SMALL, KC_FWD_A, KC_FWD_B, KC_SMALL, KC_DIRECT, KC_NARROW, KC_NARROW_MANY, KC_NARROW_BIG,
                    KC_PASS_A, KC_PASS_B, KC_ICWT, KC_ELEMENTWISE, KC_OLS_FWD, KC_OLS, KC_OLS_SMALL, KC_AOLS_PRE, KC_AOLS,
-                   KC_POLY_COEF, KC_POLY, KC_COUNT };
+                   KC_POLY_COEF, KC_POLY, KC_ADJOINT, KC_COUNT };
 extern const char* const kClassNames[KC_COUNT];
 
 int ilog2(int64_t v);
@@ -121,6 +121,7 @@ struct cwt_plan {
   int poly_min_logn = 16;  // shortest transform that takes the form
   int poly_max_logk = 14;  // largest log2 K' (tuning: 13 keeps the rows that need 16384 intervals out of the form)
   int coef_small = 0;      // interval coefficients of every K' in one launch of 256-thread workgroups (K' = 8192 / 16384 split in 2 / 4); measured slower (EXPERIMENTS R6.2)
+  int adjoint_poly = 1;    // cwt_adjoint_rows: the rows of form P through its transpose (k_poly_moments); 0 = every row through the general path
   int poly_chunk_mb = 96;  // coefficient planes computed and consumed per chunk of polynomial rows (MiB; 0 = all rows at once)
   int host_direct = 1;     // cwt_execute_host, transforms that fit one workgroup: the kernels read the signal from / write W into page-locked host memory
   int aols = 1;            // rows clipped at Nyquist as overlap-save rows on the band-passed complex signal (k_aols_*)
@@ -168,6 +169,10 @@ struct cwt_plan {
   size_t pcoef_bytes = 0;
   void* pband = nullptr;    // their filtered bands in transform-input order
   size_t pband_bytes = 0;
+  void* adj_spec = nullptr; // cwt_adjoint_rows: spectra of a chunk of rows of the adjoint's input (chunk x N complex) ...
+  size_t adj_spec_bytes = 0;
+  void* adj_acc = nullptr;  // ... and the per-signal accumulator conj(sum_j conj(F_j) DFT(G_j)) (N complex)
+  size_t adj_acc_bytes = 0;
   void* xm = nullptr;       // band-passed complex signal x_M of the k_aols rows (N complex)
   size_t xm_bytes = 0;
   void* xsa = nullptr;      // its block spectra (nblocks x (P + 8) complex)
@@ -185,6 +190,7 @@ struct cwt_plan {
   // The host side of a row table: its rows and how the launches cut them.  build_row_table replaces it whole.
   struct RowLayout {
     std::vector<cwt::RowDesc> table;     // small | narrow by launch class | two-pass | overlap-save | A | A2 | masks | polynomial
+    std::vector<cwt::RowDesc> base;      // every row on its plain support (row_support), by out_row: the adjoint's general path
     std::vector<Group> narrow_groups;
     int n_small = 0, n_narrow = 0, n_wide = 0, wide_first = 0;
     int n_ols = 0, ols_first = 0;        // overlap-save rows (after the wide rows), sorted by halo class
@@ -240,6 +246,13 @@ struct cwt_plan {
     cwt::RowDesc* rows_pinned = nullptr;
     hipEvent_t uploaded = nullptr;
     uint64_t used = 0;
+    // rows of the adjoint's general path (cwt_adjoint_rows): `base` without the rows it takes through the transpose of form P,
+    // uploaded once per table and value of "adjoint_poly" (-1: not uploaded since the table was built)
+    cwt::RowDesc* adj_dev = nullptr;
+    cwt::RowDesc* adj_pinned = nullptr;
+    hipEvent_t adj_uploaded = nullptr;
+    int adj_poly = -1;
+    std::vector<int> adj_rows;           // their out_rows
   };
   RowTable slots[4];
   RowTable* rt = &slots[0];

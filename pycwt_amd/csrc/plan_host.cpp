@@ -16,7 +16,8 @@ int fail(int code, const std::string& msg) {
 
 const char* const kClassNames[KC_COUNT] = {"fwd_small", "fwd_pass_a",  "fwd_pass_b", "small",  "direct", "narrow",
                                            "narrow_many", "narrow_big", "pass_a",     "pass_b", "icwt",   "elementwise",
-                                           "ols_fwd", "ols", "ols_small", "aols_pre", "aols", "poly_coef", "poly"};
+                                           "ols_fwd", "ols", "ols_small", "aols_pre", "aols", "poly_coef", "poly",
+                                           "adjoint"};
 
 int ilog2(int64_t v) {
   int l = 0;
@@ -721,6 +722,7 @@ bool poly_candidate(const cwt_plan* p, const RowRequest& r, const Gates& g, cons
 
 // The rows of a call by form, in the order they were classified
 struct Forms {
+  std::vector<RowDesc> base;                          // every row on its plain support, in classification (= out_row) order
   std::vector<RowDesc> small, narrow, wide, poly;
   std::vector<char> wide_clipped, wide_unclipped;   // per two-pass row: a candidate of the band-passed form (aols_pass)
   std::vector<OlsRow> ols;
@@ -731,6 +733,7 @@ struct Forms {
 int classify_row(const cwt_plan* p, const RowRequest& r, const Gates& g, int j, Forms* f) {
   RowSupport s;
   if (const int rc = row_support(p, r, g, j, &s)) return rc;
+  f->base.push_back(s.rd);
   RowDesc rd = s.rd;
   if (g.use_small) { f->small.push_back(rd); return CWT_OK; }
   const int need = std::max(4, ilog2(std::max(rd.nband, 1)));
@@ -1200,6 +1203,7 @@ int build_row_table(cwt_plan* p, const RowRequest& r) {
   ols_layout(p, r, g, f.ols, &L);
   aols_layout(p, r, g, a, &L);
   if (const int rc = poly_layout(p, f.poly, &L)) return rc;
+  L.base = std::move(f.base);
   *static_cast<RowLayout*>(p->rt) = std::move(L);
   return CWT_OK;
 }
@@ -1353,6 +1357,7 @@ int upload_row_table(cwt_plan* p, const std::vector<double>& key) {
   HIPCHECK(hipMemcpyAsync(t->rows_dev, t->rows_pinned, t->table.size() * sizeof(RowDesc), hipMemcpyHostToDevice,
                           p->stream));
   HIPCHECK(hipEventRecord(t->uploaded, p->stream));
+  t->adj_poly = -1;
   t->key = key;
   return CWT_OK;
 }
