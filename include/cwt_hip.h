@@ -110,10 +110,8 @@ int cwt_plan_set_stream(cwt_plan* plan, void* hip_stream);
  *   "ols"          0 = no overlap-save rows in cwt_transform / cwt_execute_host (default 1)
  *   "ols_max_halo" largest halo H (samples, multiple of 64) of an overlap-save row; 0 = a quarter of the workgroup tile
  *   "ols_big"      1 = rows with halo >= "ols_big_min_halo" (default 1536) and a block support <= 1/8 tile use blocks
- *                  of two workgroup tiles; 2 = also blocks of FOUR tiles for halos in ["ols_big4_min_halo" (2048),
- *                  "ols_big4_max_halo" (8192)]: their block spectra are one 16384-point packed transform per block
- *                  (default: 1 for precision 32, 0 for 64; 2 measured -1 ... +3 % depending on the thresholds: the rows
- *                  gain what the extra block-spectra launch costs, EXPERIMENTS.md)
+ *                  of two workgroup tiles (default: 1 for precision 32, 0 for 64; 2, blocks of four tiles, has left the sources:
+ *                  setting it fails)
  *   "ols_small_max_halo" overlap-save rows with a halo up to this many samples (multiple of 64, default 512) run on
  *                  half-size workgroup tiles -- four block transforms in flight per CU instead of two; 0 = none
  *   "ols_small_big" 0 = rows with a halo in ("ols_small_max_halo", 1024] on the default tile (default 1: on 8192-point blocks of TWO
@@ -137,11 +135,11 @@ int cwt_plan_set_stream(cwt_plan* plan, void* hip_stream);
  *                  nfft >= 2^18, once per caller's stream: the last eight are remembered; never while the stream is being
  *                  captured into a graph); at most 16 streams are ever parked
  *   "serial_rows"  long transforms with polynomial rows: 0 = overlap-save chain, band-passed rows and polynomial rows side by
- *                  side on the plan's streams (the schedule of rounds 4-5); 1 = every kernel that WRITES W on the caller's
- *                  stream, one after the other, everything they need prepared on the side streams; 2 = also the first block
- *                  spectra on the caller's stream (their rows follow at a kernel boundary) and the forward FFT on a side
- *                  stream, on half-size tiles ("fft_aside_small"); 3 = 2 with ONE wait on the caller's stream.  Default 2 for
- *                  precision 64 (measured -1 % at config 2, -5.7 % for fp64 Paul), 0 for precision 32 (+-0 / +1.4 %)
+ *                  side on the plan's streams (the schedule of rounds 4-5); 2 = the serial schedule: every kernel that WRITES W
+ *                  on the caller's stream, one after the other, everything they need prepared on the side streams, the first
+ *                  block spectra on the caller's stream (their rows follow at a kernel boundary) and the forward FFT on a side
+ *                  stream, on half-size tiles.  Default 2 for precision 64 (measured -1 % at config 2, -5.7 % for fp64 Paul),
+ *                  0 for precision 32 (+-0 / +1.4 %).  1 and 3 have left the sources: setting them fails
  *   "adjoint_poly" 0 = cwt_adjoint_rows takes every row through its general path (default 1: the polynomial rows through the
  *                  transpose of their form)
  *   "poly_carrier" 0 = the carrier of a polynomial row is the centre bin of its band (default 1: the bin, of 15 candidates, at which
@@ -151,13 +149,10 @@ int cwt_plan_set_stream(cwt_plan* plan, void* hip_stream);
  *                  e^{i theta u} cut at the same degree and re-expanded in monomials -- error 2 (theta/2)^(D+1) / (D+1)! instead of
  *                  theta^(D+1) / (D+1)!, so fewer intervals at the same degree: planes -25 % at 2^20 x 256 Morlet scales; one table
  *                  of (D + 1) x (K' + 1) reals per (K', D) pair of the scale grid, written when the grid is first seen)
- *   "serial_s1_once" 0 = under "serial_rows" the caller's stream waits for side stream 1 once per consumer (second overlap-save
- *                  launch, band-passed rows); default 1: once, for the end of that in-order chain
- *   "coef_small"   1 = the interval coefficients of every K' in one launch of 256-thread workgroups (K' = 8192 / 16384 as 2 / 4
- *                  decimated 4096-point transforms per job); default 0: measured +5 % on the step (strided plane stores)
- *   "aols_small_b" 0 = the band-passed signal's second pass on the default tile under "serial_rows" (default 1: 4096-point
- *                  tiles, 256-thread workgroups, which find a CU beside the overlap-save rows)
  *   "graph"        removed (HIP graph replay of repeated calls: measured +-0.5 % on the step); setting it fails
+ *   "serial_s1_once", "fft_aside_small", "aols_small_b", "coef_small", "ols_big4_min_halo", "ols_big4_max_halo"
+ *                  removed (measured-and-rejected variants of the serial schedule, the coefficient launch and the overlap-save
+ *                  blocks; EXPERIMENTS.md has the measurements); setting them fails
  *   "ct"           0 = never use the compile-time specialised kernels (generic engine only)
  *   "profile"      1 = time every kernel class with HIP events (cwt_plan_timings) */
 int cwt_plan_set_option(cwt_plan* plan, const char* key, int64_t value);

@@ -112,40 +112,6 @@ int queue_rows(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, v
   return scope.done(by_precision(p, [&](auto t) { return rows_impl<decltype(t)>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols); }));
 }
 
-// The spectrum of cwt_transform, inside its CallScope.  The overlap-save rows need the signal only: their block spectra are
-// queued on side stream 1 BEFORE the forward FFT, so that they run beside it and beside the two-pass chain; rows_impl then
-// skips them and joins the stream at its end.
-int queue_spectrum(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev) {
-  if (p->rt->n_ols && p->ols_early && !p->profile) {
-    p->call.ols_first_on_main = p->serial_rows >= 2 && serial_schedule(p, true) && p->rt->ols_grp[0].nrows > 0;
-    const int rc = by_precision(p, [&](auto t) { return launch_ols_early<decltype(t)>(p, x_dev, n0); });
-    if (rc) return rc;
-    p->call.ols_launched = 1;
-  }
-  // serial_rows = 2: the forward FFT on side stream 0 (the bands + coefficients of the polynomial rows follow it there), so that
-  // the first overlap-save rows start on the caller's stream as soon as their block spectra exist
-  const bool fft_aside = p->serial_rows >= 2 && serial_schedule(p, p->call.ols_launched != 0);
-  int rc = CWT_OK;
-  {
-    StreamGuard caller(p);
-    if (fft_aside) {
-      if (!p->call.ols_launched) HIPCHECK(hipEventRecord(p->ev_fork, p->stream));
-      HIPCHECK(hipStreamWaitEvent(p->side[0], p->ev_fork, 0));
-      p->stream = p->side[0];
-      p->call.fft_small = p->fft_aside_small;
-    }
-    rc = by_precision(p, [&](auto t) { return fft_rows_impl<decltype(t), IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev); });
-  }
-  p->call.fft_small = 0;
-  if (rc) return rc;
-  if (fft_aside) {
-    HIPCHECK(hipEventRecord(p->ev_a[1], p->side[0]));
-    p->call.spectrum_ready = p->ev_a[1];
-  }
-  return CWT_OK;
-}
-
-
 std::mutex g_pinned_mutex;
 std::map<uintptr_t, size_t> g_pinned;
 
@@ -430,11 +396,15 @@ int cwt_plan_set_option(cwt_plan* p, const char* key, int64_t value) {
   if (!p || !key) return fail(CWT_EINVAL, "plan/key is NULL");
   const std::string k(key);
   auto pow2 = [](int64_t v) { return v > 0 && (v & (v - 1)) == 0; };
+  const std::string left = " belonged to a measured-and-rejected variant or a diagnostic that has left the sources "
+                           "(EXPERIMENTS.md has its measurements)";
   for (const char* gone : {"overlap", "pass_b_prefetch", "pass_b_small", "stamps", "ols_tile", "ols_fwd_real", "sched", "narrow_wave",
-                           "graph"})
-    if (k == gone)
-      return fail(CWT_EINVAL, "option " + k + " belonged to a measured-and-rejected variant or a diagnostic that has left the sources "
-                              "(EXPERIMENTS.md has its measurements)");
+                           "graph", "serial_s1_once", "fft_aside_small", "aols_small_b", "coef_small", "ols_big4_min_halo",
+                           "ols_big4_max_halo"})
+    if (k == gone) return fail(CWT_EINVAL, "option " + k + left);
+  // (values of kept options that selected such a variant fail the same way: an old script must not change schedule silently)
+  if ((k == "serial_rows" && (value == 1 || value == 3)) || (k == "ols_big" && value == 2))
+    return fail(CWT_EINVAL, k + " = " + std::to_string(value) + left);
   for (auto& t : p->slots) t.key.clear();   // the classification depends on the options
   struct Restore {   // a rejected geometry leaves every geometry-affecting field as it was
     cwt_plan* p; int lmax, wg, logk, nmax;
@@ -464,7 +434,6 @@ int cwt_plan_set_option(cwt_plan* p, const char* key, int64_t value) {
   else if (k == "aols_zc") p->aols_zc = value != 0;
   else if (k == "aols_long") p->aols_long = value != 0;
   else if (k == "poly") p->poly = value != 0;
-  else if (k == "coef_small") p->coef_small = value != 0;
   else if (k == "poly_carrier") p->poly_carrier = value != 0;
   else if (k == "poly_cheb") p->poly_cheb = value != 0;
   else if (k == "poly_degree") { if (value < 2 || value > POLY_MAX_DEGREE) return fail(CWT_EINVAL, "poly_degree in [2, 24]"); p->poly_degree = int(value); }
@@ -475,18 +444,13 @@ int cwt_plan_set_option(cwt_plan* p, const char* key, int64_t value) {
   else if (k == "poly_min_logn") { if (value < 14 || value > 24) return fail(CWT_EINVAL, "poly_min_logn in [14, 24]"); p->poly_min_logn = int(value); }
   else if (k == "aols_min_rows") { if (value < 1 || value > 65536) return fail(CWT_EINVAL, "aols_min_rows >= 1"); p->aols_min_rows = int(value); }
   else if (k == "ols_side") p->ols_side = value != 0;
-  else if (k == "ols_big") { if (value < 0 || value > 2) return fail(CWT_EINVAL, "ols_big: 0, 1 (blocks of two tiles) or 2 (also of four)"); p->ols_big = int(value); }
-  else if (k == "ols_big4_max_halo") { if (value < 2048 || value > 8192 || (value & 63)) return fail(CWT_EINVAL, "ols_big4_max_halo: multiple of 64 in [2048, 8192]"); p->ols_big4_max_halo = int(value); }
-  else if (k == "ols_big4_min_halo") { if (value < 64 || value > 8192) return fail(CWT_EINVAL, "ols_big4_min_halo in [64, 8192]"); p->ols_big4_min_halo = int(value); }
+  else if (k == "ols_big") { if (value < 0 || value > 1) return fail(CWT_EINVAL, "ols_big: 0 or 1 (blocks of two tiles)"); p->ols_big = int(value); }
   else if (k == "ols_min_logn") { if (value < 15 || value > 24) return fail(CWT_EINVAL, "ols_min_logn in [15, 24]"); p->ols_min_logn = int(value); }
   else if (k == "ols_small_max_halo") { if (value < 0 || value > 1024 || (value & 63)) return fail(CWT_EINVAL, "ols_small_max_halo: multiple of 64 in [0, 1024]"); p->ols_small_max_halo = int(value); }
   else if (k == "ols_small_big") p->ols_small_big = value != 0;
-  else if (k == "serial_s1_once") p->serial_s1_once = value != 0;
   else if (k == "ols_big_min_halo") { if (value < 64 || value > 8192) return fail(CWT_EINVAL, "ols_big_min_halo in [64, 8192]"); p->ols_big_min_halo = int(value); }
   else if (k == "ols_early") p->ols_early = value != 0;
-  else if (k == "aols_small_b") p->aols_small_b = value != 0;
-  else if (k == "fft_aside_small") p->fft_aside_small = value != 0;
-  else if (k == "serial_rows") { if (value < 0 || value > 3) return fail(CWT_EINVAL, "serial_rows: 0 ... 3"); p->serial_rows = int(value); }
+  else if (k == "serial_rows") { if (value != 0 && value != 2) return fail(CWT_EINVAL, "serial_rows: 0 or 2"); p->serial_rows = int(value); }
   else if (k == "ols_max_halo") { if (value < 0 || value > 4096 || (value & 63)) return fail(CWT_EINVAL, "ols_max_halo: multiple of 64 in [0, 4096]"); p->ols_max_halo = int(value); }
   else if (k == "ols_fwd_weight") { if (value < 0 || value > 1000) return fail(CWT_EINVAL, "ols_fwd_weight: percent of a row, 0..1000"); p->ols_fwd_weight = double(value) / 100.0; }
   else if (k == "tolerance_neglog10") {   // integer alias of cwt_plan_set_tolerance for option sweeps: 10^-value; 0 = default
@@ -684,10 +648,8 @@ int cwt_transform(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double
   }
   const Mother mo = mother_of(mother, param);
   CallScope scope(p);
-  if (!only_ols) rc = queue_spectrum(p, x_dev, n0, xhat_dev);
-  if (rc) return rc;
   return scope.done(by_precision(p, [&](auto t) {
-    return rows_impl<decltype(t)>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0);
+    return transform_impl<decltype(t)>(p, x_dev, n0, xhat_dev, mo, nrows, W_dev, ldw, ncols);
   }));
 }
 

@@ -187,7 +187,7 @@ void launch_pass_a_ct(cwt_plan* p, const void* in, const RowDesc* rows, int cnt,
     }
   }
   if constexpr (MODE == IN_REAL && LOGR <= LOGP - 1 && LOGR >= 8) {
-    if (p->call.fft_small) { // the forward FFT beside the overlap-save rows (serial_rows = 2): half-size tiles get their turn on the CUs
+    if (p->call.fft_small) { // the serial schedule's forward FFT beside the overlap-save rows: half-size tiles get their turn on the CUs
       constexpr int LP = LOGP - 1;
       hipLaunchKernelGGL((k_pass_a_ct<T, LOGR, LP, MODE>), dim3(1u << (p->logN - LP), cnt), dim3(1 << (LP - 4)),
                          (size_t(1) << LP) * sizeof(T), st, in, rows, mo, tw_table<T>(p, LOGR), twn_of<T>(p), p->logN, n0, in_ld, Z);
@@ -348,29 +348,24 @@ int launch_ols_fwd_r(cwt_plan* p, const void* x_dev, int64_t n0, long blocks, co
                        long(p->call.ols_x_ld), p->rt->ols_xs_sig);
   }, st);
 }
-// (g_only / d_only >= 0: only that tile group / only its blocks of 2^d tiles; d_only = -2: every block length but one tile)
+// (g_only / d_only >= 0: only that tile group / only its blocks of 2^d tiles)
 template <typename T>
-int launch_ols_fwd(cwt_plan* p, const void* x_dev, int64_t n0, hipStream_t st, hipEvent_t after_first = nullptr, int g_only = -1,
-                   int d_only = -1) {
+int launch_ols_fwd(cwt_plan* p, const void* x_dev, int64_t n0, hipStream_t st, int g_only = -1, int d_only = -1) {
   int rc = CWT_OK;
-  {
-    for (int g = 0; g < 2 && !rc; ++g) {
-      if (g == 1 && after_first) HIPCHECK(hipEventRecord(after_first, st));     // the half-size tiles' spectra exist
-      const auto& G = p->rt->ols_grp[g];
-      if (!G.nrows || (g_only >= 0 && g != g_only)) continue;
-      for (int d = 0; d < 3 && !rc; ++d) {
-        if (!G.fwd_blocks[d] || (d_only >= 0 && d != d_only) || (d_only == -2 && d == 0)) continue;
-        switch (G.logp + d) {                                   // log2 of the block length
-          case 12: rc = launch_ols_fwd_r<T, 11>(p, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
-          case 13: rc = launch_ols_fwd_r<T, 12>(p, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
-          case 14: rc = launch_ols_fwd_r<T, 13>(p, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
-          case 15: rc = launch_ols_fwd_r<T, 14>(p, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
-          default: return fail(CWT_EINVAL, "overlap-save block length");
-        }
+  for (int g = 0; g < 2 && !rc; ++g) {
+    const auto& G = p->rt->ols_grp[g];
+    if (!G.nrows || (g_only >= 0 && g != g_only)) continue;
+    for (int d = 0; d < 2 && !rc; ++d) {
+      if (!G.fwd_blocks[d] || (d_only >= 0 && d != d_only)) continue;
+      switch (G.logp + d) {                                   // log2 of the block length
+        case 12: rc = launch_ols_fwd_r<T, 11>(p, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
+        case 13: rc = launch_ols_fwd_r<T, 12>(p, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
+        case 14: rc = launch_ols_fwd_r<T, 13>(p, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
+        default: return fail(CWT_EINVAL, "overlap-save block length");
       }
     }
-    return rc;
   }
+  return rc;
 }
 // ... and the rows themselves (k_ols_ct)
 // part: -1 = every class of the group in one launch, 0 = the classes on blocks of one tile, 1 = the classes on longer blocks
@@ -409,13 +404,11 @@ int launch_ols_rows(cwt_plan* p, cplx<T>* W, int64_t ldw, int64_t ncols, hipStre
 
 // Rows clipped at Nyquist (k_aols_*): band-passed complex signal x_M = IFFT_N(xhat mask) through the two-pass kernels
 // (the mask is the pseudo-row at aux_first: profile 1), its block spectra, then every (block, row) pair.
-// ready != nullptr (one signal only): the band-passed signal and its block spectra on st, `ready` recorded behind them,
-// the rows on st_rows behind that event.
-// phase (one signal, ready != nullptr): 0 = everything, 1 = the band-passed signal and its block spectra on st + `ready` recorded,
-// 2 = the rows on st_rows, which the CALLER has made wait for `ready`
+// phase: 0 = everything on st; the serial schedule (one signal) splits it in two: 1 = the band-passed signal and its block
+// spectra on st, `ready` recorded behind them, 2 = the rows on st, which the caller has made wait for `ready`
 template <typename T, int LOGP>
-int launch_aols_p(cwt_plan* p, const void* xhat_dev, cplx<T>* W, int64_t ldw, int64_t ncols, hipStream_t st,
-                  hipStream_t st_rows = nullptr, hipEvent_t ready = nullptr, int phase = 0) {      // (ready == nullptr: everything on st; the caller's stream may be the null stream)
+int launch_aols_p(cwt_plan* p, const void* xhat_dev, cplx<T>* W, int64_t ldw, int64_t ncols, hipStream_t st, int phase = 0,
+                  hipEvent_t ready = nullptr) {
   const cwt_plan::RowTable* rt = p->rt;
   const AolsGeom& g = rt->aols_geom;
   constexpr int P = 1 << LOGP;
@@ -444,9 +437,9 @@ int launch_aols_p(cwt_plan* p, const void* xhat_dev, cplx<T>* W, int64_t ldw, in
     }, st);
     if (!rc && !ok) rc = fail(CWT_EINVAL, "k_aols rows need the default geometry");
     if (!rc && phase != 2) rc = timed_launch(p, KC_AOLS_PRE, [&] {
-      // (beside the overlap-save rows the default tile's 512-thread workgroups do not find a CU before those drain: 170-250 us
-      // for 16; 256-thread workgroups get their turn)
-      if (p->aols_small_b && ready && logK == 10 && default_logp<T>() == 13 && p->use_ct) { launch_pass_b_ct_lp<T, 10, 12, false>(p, nullptr, cnt, xm, p->N, p->N, Z, st); ok = true; }
+      // (serial schedule, beside the overlap-save rows: the default tile's 512-thread workgroups do not find a CU before those
+      // drain, 170-250 us for 16; 256-thread workgroups get their turn)
+      if (phase == 1 && logK == 10 && default_logp<T>() == 13 && p->use_ct) { launch_pass_b_ct_lp<T, 10, 12, false>(p, nullptr, cnt, xm, p->N, p->N, Z, st); ok = true; }
       else ok = try_pass_b_ct<T, false>(p, logK, nullptr, cnt, xm, p->N, p->N, Z, st);
     }, st);
     if (!rc && !ok) rc = fail(CWT_EINVAL, "k_aols rows need the default geometry");
@@ -454,19 +447,16 @@ int launch_aols_p(cwt_plan* p, const void* xhat_dev, cplx<T>* W, int64_t ldw, in
       hipLaunchKernelGGL((k_aols_fwd<T, LOGP>), dim3(unsigned(g.nblocks), unsigned(cnt)), dim3(1 << (LOGP - 4)), lds, st, xm,
                          p->logN, g.halo, static_cast<const cplx<T>*>(p->tw_all), static_cast<cplx<T>*>(p->xsa));
     }, st);
-    hipStream_t sr = st;
-    if (!rc && ready && nb == 1) {
-      if (phase != 2) HIPCHECK(hipEventRecord(ready, st));
-      if (phase == 0) HIPCHECK(hipStreamWaitEvent(st_rows, ready, 0));
-      sr = st_rows;
+    if (phase == 1) {
+      if (!rc) HIPCHECK(hipEventRecord(ready, st));
+      return rc;
     }
-    if (phase == 1) return rc;
     if (!rc) rc = timed_launch(p, KC_AOLS, [&] {
-      hipLaunchKernelGGL((k_aols_rows<T, LOGP>), dim3(unsigned(rt->aols_wgs), unsigned(cnt)), dim3(1 << (LOGP - 4)), lds_rows, sr,
+      hipLaunchKernelGGL((k_aols_rows<T, LOGP>), dim3(unsigned(rt->aols_wgs), unsigned(cnt)), dim3(1 << (LOGP - 4)), lds_rows, st,
                          static_cast<const cplx<T>*>(p->xsa), rt->rows_dev + rt->aols_first + long(b0) * g.nrows,
                          static_cast<const T*>(rt->agt_dev), static_cast<const cplx<T>*>(p->tw_all), g,
                          static_cast<const cplx<T>*>(xhat_dev), long(p->N >> 1), W, long(ldw), long(ncols));
-    }, sr);
+    }, st);
     if (rc) return rc;
   }
   return CWT_OK;
@@ -498,14 +488,14 @@ int launch_aols_second(cwt_plan* p, const void* xhat_dev, cplx<T>* W, int64_t ld
   return rc;
 }
 template <typename T>
-int launch_aols(cwt_plan* p, const void* xhat_dev, cplx<T>* W, int64_t ldw, int64_t ncols, hipStream_t st,
-                hipStream_t st_rows = nullptr, hipEvent_t ready = nullptr, int phase = 0) {
+int launch_aols(cwt_plan* p, const void* xhat_dev, cplx<T>* W, int64_t ldw, int64_t ncols, hipStream_t st, int phase = 0,
+                hipEvent_t ready = nullptr) {
   int rc = CWT_OK;
   switch (p->rt->aols_logp) {
-    case 12: rc = launch_aols_p<T, 12>(p, xhat_dev, W, ldw, ncols, st, st_rows, ready, phase); break;
+    case 12: rc = launch_aols_p<T, 12>(p, xhat_dev, W, ldw, ncols, st, phase, ready); break;
     default: return fail(CWT_EINVAL, "k_aols tile size");
   }
-  if (!rc && p->rt->n_aols2 && phase != 1) rc = launch_aols_second<T>(p, xhat_dev, W, ldw, ncols, ready ? st_rows : st);
+  if (!rc && p->rt->n_aols2 && phase != 1) rc = launch_aols_second<T>(p, xhat_dev, W, ldw, ncols, st);
   return rc;
 }
 
@@ -534,10 +524,6 @@ int launch_poly_coef(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, int chu
   const T* rtab = static_cast<const T*>(rt->prt_dev);       // economised weights of the (K', D) pairs (rows with rtab_off >= 0)
   if (rt->poly_rtab_elems > 0 && (!rtab || rt->prt_bytes < size_t(rt->poly_rtab_elems) * sizeof(T)))
     return fail(CWT_EINVAL, "polynomial rows without their weight tables (fill_poly_tables was not run for this row table)");
-  if (p->coef_small)         // every class on 256-thread workgroups, one launch (k_poly_coef_all)
-    return timed_launch(p, KC_POLY_COEF, [&] {
-      hipLaunchKernelGGL((k_poly_coef_all<T>), dim3(unsigned(ch.wgs_all)), dim3(256), ((size_t(1) << 12) + (size_t(1) << 8)) * sizeof(T), st,
-                         static_cast<const cplx<T>*>(band), rows, tw, ch.cls, coef, rtab); }, st);
   // largest tiles first: the 16384-point workgroups take a whole CU each and should find the chip as empty as it gets
   auto lds_of = [](int lp) { return ((size_t(1) << lp) + (size_t(1) << (lp - 4))) * sizeof(T); };
   const bool split = st2 && ch.wgs[2] && (ch.wgs[1] || ch.wgs[0]);
@@ -609,93 +595,6 @@ int launch_wide_rows(cwt_plan* p, const void* xhat_dev, const Mother& mo, cplx<T
   return CWT_OK;
 }
 
-// The schedule of a long transform with polynomial rows (option "serial_rows", default): every kernel that WRITES W runs
-// on the caller's stream, one after the other -- overlap-save rows (half-size tiles, then the default tile), rows on the
-// band-passed signal, two-pass rows, polynomial rows -- and everything they need is prepared on the side streams beside the
-// first of them: block spectra on side stream 1 (queued before the forward FFT by cwt_transform), behind them the band-passed
-// signal and its block spectra; bands + interval coefficients on side stream 0 (+ side2).  Why: heavy kernels side by side cost
-// more than one after the other (EXPERIMENTS R5.2), a stream-to-stream hand-over costs 15-20 us where the waiting stream is idle
-// -- so the hand-overs sit where the event completed long before the wait is reached, and the step ends on the caller's stream
-// (the next call, or whatever the caller queues, follows at a kernel boundary instead of a join).
-template <typename T>
-int rows_launch_serial(cwt_plan* p, const void* xhat_dev, const Mother& mo, void* W_dev, int64_t ldw, int64_t ncols,
-                       hipEvent_t spectrum_ready) {
-  const cwt_plan::RowTable* rt = p->rt;
-  const cplx<T>* xhat = static_cast<const cplx<T>*>(xhat_dev);
-  cplx<T>* W = static_cast<cplx<T>*>(W_dev);
-  hipStream_t M = p->stream, S0 = p->side[0], S1 = p->side[1];
-  int rc = CWT_OK;
-  // the one intermediate buffer serves the band-passed signal (side stream 1) and the two-pass rows (caller's stream): sized
-  // for both before either is queued
-  if (rt->n_aols || rt->n_wide) rc = ensure_z(p, rt->n_wide ? balanced_chunk(p, rt->n_wide) : 1);
-  if (rc) return rc;
-  if (!spectrum_ready) {                                  // the forward FFT ran on the caller's stream
-    spectrum_ready = p->ev_a[1];
-    HIPCHECK(hipEventRecord(spectrum_ready, M));
-  }
-  if (rt->n_poly) {
-    HIPCHECK(hipStreamWaitEvent(S0, spectrum_ready, 0));
-    rc = launch_poly_coef<T>(p, xhat, mo, 0, S0, p->side2);
-    if (rc) return rc;
-    HIPCHECK(hipEventRecord(p->ev_a[0], S0));
-  }
-  // side stream 1 is ONE in-order chain -- block spectra of the longer blocks / of the default tile (queued by cwt_transform), then
-  // the band-passed signal and its block spectra -- so the caller's stream waits for its END once, behind the first overlap-save
-  // launch (the chain is long done then: 130 of 250 us), instead of once per consumer: a wait costs the stream 7-8 us, a kernel
-  // boundary 2 [measured]
-  const bool s1_once = rt->n_aols && p->serial_rows != 3 && p->serial_s1_once;
-  if (rt->n_aols) HIPCHECK(hipStreamWaitEvent(S1, spectrum_ready, 0));   // (the rows wait for the band-passed signal, made from the spectrum)
-  if (s1_once) {
-    rc = launch_aols<T>(p, xhat_dev, W, ldw, ncols, S1, M, p->ev_b[1], 1);
-    if (rc) return rc;
-  }
-  const bool g0_split = p->call.ols_first_on_main && rt->ols_grp[0].wgs > rt->ols_grp[0].wgs_base;   // longer blocks on the half-size tiles:
-  if (rt->n_ols) {                                        // block spectra queued by cwt_transform on side stream 1
-    if (!p->call.ols_first_on_main) HIPCHECK(hipStreamWaitEvent(M, p->ev_b[0], 0));
-    rc = launch_ols_rows<T>(p, W, ldw, ncols, M, 0, g0_split ? 0 : -1);   // their spectra come from side stream 1, behind ev_ols
-    if (rc) return rc;
-  }
-  // serial_rows = 3: ONE wait on the caller's stream for everything the side streams prepare (each wait is a barrier packet that
-  // costs the stream 5-8 us even when its event completed long ago): side stream 1 = block spectra of the default tile, then
-  // (behind the coefficients' event) the band-passed signal, then the event the rows of that signal wait for -- which therefore
-  // come before the default tile's rows.
-  const bool one_wait = p->serial_rows == 3 && rt->n_aols && rt->n_poly;
-  if (one_wait) {
-    HIPCHECK(hipStreamWaitEvent(S1, p->ev_a[0], 0));
-    rc = launch_aols<T>(p, xhat_dev, W, ldw, ncols, S1, M, p->ev_b[1]);
-    if (rc) return rc;
-  }
-  if (s1_once) HIPCHECK(hipStreamWaitEvent(M, p->ev_b[1], 0));
-  if (rt->n_ols && (rt->ols_grp[1].nrows || g0_split)) {
-    if (!one_wait && !s1_once) HIPCHECK(hipStreamWaitEvent(M, p->ev_ols, 0));
-    if (g0_split) rc = launch_ols_rows<T>(p, W, ldw, ncols, M, 0, 1);
-    if (!rc && rt->ols_grp[1].nrows) rc = launch_ols_rows<T>(p, W, ldw, ncols, M, 1);
-    if (rc) return rc;
-  }
-  if (rt->n_aols && !one_wait) {   // band-passed signal + block spectra on side stream 1 (behind the block spectra of the signal: they
-                                   // have the two overlap-save launches to get done), the rows on the caller's stream
-    rc = launch_aols<T>(p, xhat_dev, W, ldw, ncols, S1, M, p->ev_b[1], s1_once ? 2 : 0);
-    if (rc) return rc;
-  }
-  // The polynomial rows BEFORE the two-pass rows: k_poly_rows starts every workgroup with a fetch of its coefficient sets and runs
-  // at the store rate only while the planes sit in the Infinity Cache; a two-pass chunk in between moves ~200 MB through it
-  // (fp64 Paul, 73 MB of planes, [measured]: 4.65 us per row behind the two-pass rows, 2.9 in front of them).
-  if (rt->n_poly) {
-    if (!one_wait) HIPCHECK(hipStreamWaitEvent(M, p->ev_a[0], 0));
-    const int nchunks = int(rt->poly_chunks.size());
-    for (int c = 0; c < nchunks && !rc; ++c) {            // chunk c's rows, then chunk c + 1's coefficients
-      rc = launch_poly_rows<T>(p, c, W, ldw, ncols, M);
-      if (!rc && c + 1 < nchunks) rc = launch_poly_coef<T>(p, xhat, mo, c + 1, M, nullptr);
-    }
-    if (rc) return rc;
-  }
-  if (rt->n_wide) {
-    HIPCHECK(hipStreamWaitEvent(M, spectrum_ready, 0));
-    rc = launch_wide_rows<T>(p, xhat_dev, mo, W, ldw, ncols);
-  }
-  return rc;
-}
-
 // Restores the plan's stream when a scope that redirected launches to a side stream is left on any path.
 struct StreamGuard {
   cwt_plan* p;
@@ -726,15 +625,146 @@ struct CallScope {
   }
 };
 
-// Queues every row of the current row table (inside a CallScope).
+// ---- the serial schedule (option "serial_rows" = 2, complex128 default) ----------------------------------------------------
+// A long transform with polynomial rows: every kernel that WRITES W runs on the caller's stream, one after the other --
+// overlap-save rows (half-size tiles, then the default tile), rows on the band-passed signal, polynomial rows, two-pass rows --
+// and everything they need is prepared on the side streams beside the first of them.  In the order a call of cwt_transform
+// queues it:
+//   1. launch_ols_early: the block spectra of the half-size tiles' one-tile blocks on the caller's stream (their rows follow at
+//      a kernel boundary), the rest on side stream 1;
+//   2. transform_serial: the forward FFT on side stream 0, on half-size tiles;
+//   3. rows_launch_serial: bands + interval coefficients on side stream 0 (+ side2) behind the FFT; the band-passed signal and
+//      its block spectra on side stream 1 behind the block spectra; the rows on the caller's stream.
+// Why: heavy kernels side by side cost more than one after the other (EXPERIMENTS R5.2), a stream-to-stream hand-over costs
+// 15-20 us where the waiting stream is idle -- so the hand-overs sit where the event completed long before the wait is reached,
+// and the step ends on the caller's stream (the next call, or whatever the caller queues, follows at a kernel boundary instead
+// of a join).  The other entry points have the spectrum on the caller's stream already and no early block spectra: they take
+// step 3 alone, for tables without overlap-save rows (serial_schedule).
+
+// Block spectra of the overlap-save rows, queued by cwt_transform before the forward FFT (option "ols_early"): they need the
+// signal only.  first_on_main (serial schedule): those of the half-size tiles' one-tile blocks on the caller's stream; the
+// rest, or all, on side stream 1, with ev_ols recorded behind them.
 template <typename T>
-int rows_impl(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw,
-              int64_t ncols, const void* x_dev = nullptr, int64_t n0 = 0) {
+int launch_ols_early(cwt_plan* p, const void* x_dev, int64_t n0, bool first_on_main) {
+  int rc = grow(&p->xs, &p->xs_bytes, size_t(p->rt->ols_xs_elems) * sizeof(cplx<T>), p->stream);
+  if (rc) return rc;
+  HIPCHECK(hipEventRecord(p->ev_fork, p->stream));        // after the previous call's work and the row-table upload
+  HIPCHECK(hipStreamWaitEvent(p->side[1], p->ev_fork, 0));
+  if (first_on_main) {
+    rc = launch_ols_fwd<T>(p, x_dev, n0, p->stream, 0, 0);
+    if (!rc) rc = launch_ols_fwd<T>(p, x_dev, n0, p->side[1], 0, 1);    // (the half-size tiles' longer blocks)
+    if (!rc) rc = launch_ols_fwd<T>(p, x_dev, n0, p->side[1], 1);
+  } else {
+    rc = launch_ols_fwd<T>(p, x_dev, n0, p->side[1]);
+  }
+  if (rc) return rc;
+  HIPCHECK(hipEventRecord(p->ev_ols, p->side[1]));      // (the round-5 schedule records it again behind the rows there)
+  return CWT_OK;
+}
+
+// Step 3.  spectrum_ready: recorded behind a forward FFT on side stream 0; nullptr: the spectrum is on the caller's stream.
+template <typename T>
+int rows_launch_serial(cwt_plan* p, const void* xhat_dev, const Mother& mo, void* W_dev, int64_t ldw, int64_t ncols,
+                       hipEvent_t spectrum_ready) {
+  const cwt_plan::RowTable* rt = p->rt;
+  const cplx<T>* xhat = static_cast<const cplx<T>*>(xhat_dev);
+  cplx<T>* W = static_cast<cplx<T>*>(W_dev);
+  hipStream_t M = p->stream, S0 = p->side[0], S1 = p->side[1];
+  int rc = CWT_OK;
+  // the one intermediate buffer serves the band-passed signal (side stream 1) and the two-pass rows (caller's stream): sized
+  // for both before either is queued
+  if (rt->n_aols || rt->n_wide) rc = ensure_z(p, rt->n_wide ? balanced_chunk(p, rt->n_wide) : 1);
+  if (rc) return rc;
+  if (!spectrum_ready) {
+    spectrum_ready = p->ev_a[1];
+    HIPCHECK(hipEventRecord(spectrum_ready, M));
+  }
+  if (rt->n_poly) {
+    HIPCHECK(hipStreamWaitEvent(S0, spectrum_ready, 0));
+    rc = launch_poly_coef<T>(p, xhat, mo, 0, S0, p->side2);
+    if (rc) return rc;
+    HIPCHECK(hipEventRecord(p->ev_a[0], S0));
+  }
+  // side stream 1 is ONE in-order chain -- block spectra of the longer blocks / of the default tile, then the band-passed signal
+  // and its block spectra -- so the caller's stream waits for its END once, behind the first overlap-save launch (the chain is
+  // long done then: 130 of 250 us), instead of once per consumer: a wait costs the stream 7-8 us, a kernel boundary 2 [measured]
+  if (rt->n_aols) {
+    HIPCHECK(hipStreamWaitEvent(S1, spectrum_ready, 0));   // (the band-passed signal is made from the spectrum)
+    rc = launch_aols<T>(p, xhat_dev, W, ldw, ncols, S1, 1, p->ev_b[1]);
+    if (rc) return rc;
+  }
+  // the rows of the half-size tiles' one-tile blocks first, behind their block spectra on this stream; those of the longer blocks
+  // (block spectra on side stream 1) in a second launch
+  const bool g0_split = rt->ols_grp[0].wgs > rt->ols_grp[0].wgs_base;
+  if (rt->ols_grp[0].nrows) {
+    rc = launch_ols_rows<T>(p, W, ldw, ncols, M, 0, g0_split ? 0 : -1);
+    if (rc) return rc;
+  }
+  if (rt->n_aols) HIPCHECK(hipStreamWaitEvent(M, p->ev_b[1], 0));
+  if (rt->n_ols && (rt->ols_grp[1].nrows || g0_split)) {
+    if (!rt->n_aols) HIPCHECK(hipStreamWaitEvent(M, p->ev_ols, 0));
+    if (g0_split) rc = launch_ols_rows<T>(p, W, ldw, ncols, M, 0, 1);
+    if (!rc && rt->ols_grp[1].nrows) rc = launch_ols_rows<T>(p, W, ldw, ncols, M, 1);
+    if (rc) return rc;
+  }
+  if (rt->n_aols) {
+    rc = launch_aols<T>(p, xhat_dev, W, ldw, ncols, M, 2);
+    if (rc) return rc;
+  }
+  // The polynomial rows BEFORE the two-pass rows: k_poly_rows starts every workgroup with a fetch of its coefficient sets and runs
+  // at the store rate only while the planes sit in the Infinity Cache; a two-pass chunk in between moves ~200 MB through it
+  // (fp64 Paul, 73 MB of planes, [measured]: 4.65 us per row behind the two-pass rows, 2.9 in front of them).
+  if (rt->n_poly) {
+    HIPCHECK(hipStreamWaitEvent(M, p->ev_a[0], 0));
+    const int nchunks = int(rt->poly_chunks.size());
+    for (int c = 0; c < nchunks && !rc; ++c) {            // chunk c's rows, then chunk c + 1's coefficients
+      rc = launch_poly_rows<T>(p, c, W, ldw, ncols, M);
+      if (!rc && c + 1 < nchunks) rc = launch_poly_coef<T>(p, xhat, mo, c + 1, M, nullptr);
+    }
+    if (rc) return rc;
+  }
+  if (rt->n_wide) {
+    HIPCHECK(hipStreamWaitEvent(M, spectrum_ready, 0));
+    rc = launch_wide_rows<T>(p, xhat_dev, mo, W, ldw, ncols);
+  }
+  return rc;
+}
+
+// Steps 1-3 for cwt_transform
+template <typename T>
+int transform_serial(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev, const Mother& mo, void* W_dev, int64_t ldw,
+                     int64_t ncols) {
+  if (p->rt->n_ols) {
+    const int rc = launch_ols_early<T>(p, x_dev, n0, p->rt->ols_grp[0].nrows > 0);
+    if (rc) return rc;
+  } else {
+    HIPCHECK(hipEventRecord(p->ev_fork, p->stream));
+  }
+  // the forward FFT on side stream 0, so that the first overlap-save rows start on the caller's stream as soon as their block
+  // spectra exist (the bands + coefficients of the polynomial rows follow it there)
+  HIPCHECK(hipStreamWaitEvent(p->side[0], p->ev_fork, 0));
+  int rc;
+  {
+    StreamGuard caller(p);
+    p->stream = p->side[0];
+    p->call.fft_small = 1;
+    rc = fft_rows_impl<T, IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev);
+    p->call.fft_small = 0;
+  }
+  if (rc) return rc;
+  HIPCHECK(hipEventRecord(p->ev_a[1], p->side[0]));
+  return rows_launch_serial<T>(p, xhat_dev, mo, W_dev, ldw, ncols, p->ev_a[1]);
+}
+
+// ---- the round-5 schedule (serial_rows = 0, complex64 default; and every call the serial schedule does not take) ---------------
+// ols_early: cwt_transform has queued the block spectra of the overlap-save rows (launch_ols_early)
+template <typename T>
+int rows_launch(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw, int64_t ncols,
+                const void* x_dev, int64_t n0, bool ols_early) {
   const int logN = p->logN;
   const cplx<T>* xhat = static_cast<const cplx<T>*>(xhat_dev);
   cplx<T>* W = static_cast<cplx<T>*>(W_dev);
-  int rc = check_geometry(p);
-  if (rc) return rc;
+  int rc = CWT_OK;
   if (p->rt->n_small) {
     if (logN <= 3) {
       const int total = nrows << logN;
@@ -763,14 +793,11 @@ int rows_impl(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, vo
   const bool side_narrow = p->overlap_narrow && !p->profile && (p->rt->n_wide || p->rt->n_ols || p->rt->n_aols) &&
                            (p->rt->n_narrow || p->rt->n_poly) && logN >= 18;
   // block spectra of the overlap-save rows: beside the two-pass chain on side stream 1 (they only need the signal)
-  const bool ols_early = p->rt->n_ols && p->call.ols_launched;  // already queued on side stream 1 by cwt_transform
   const bool ols_side = p->rt->n_ols && !ols_early && p->ols_side && !p->profile && p->rt->n_wide;
   if (p->rt->n_ols && !ols_early) {
     rc = grow(&p->xs, &p->xs_bytes, size_t(p->rt->ols_xs_elems) * sizeof(cplx<T>), p->stream);
     if (rc) return rc;
   }
-  if (serial_schedule(p, ols_early))
-    return rows_launch_serial<T>(p, xhat_dev, mo, W_dev, ldw, ncols, p->call.spectrum_ready);
   if (side_narrow || ols_side) HIPCHECK(hipEventRecord(p->ev_fork, p->stream));
   if (side_narrow) HIPCHECK(hipStreamWaitEvent(p->side[0], p->ev_fork, 0));   // starts after the spectrum exists
   if (ols_side) {
@@ -880,6 +907,32 @@ int rows_impl(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, vo
   return CWT_OK;
 }
 
+// Every row of the current row table from a spectrum on the caller's stream (inside a CallScope): every entry point but
+// cwt_transform.  No block spectra were queued early, so only a table without overlap-save rows takes the serial schedule.
+template <typename T>
+int rows_impl(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw, int64_t ncols,
+              const void* x_dev = nullptr, int64_t n0 = 0) {
+  if (int rc = check_geometry(p)) return rc;
+  if (serial_schedule(p, false)) return rows_launch_serial<T>(p, xhat_dev, mo, W_dev, ldw, ncols, nullptr);
+  return rows_launch<T>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0, false);
+}
+
+// cwt_transform after its row table (inside its CallScope): the call decides here, once, before anything is queued, whether
+// the block spectra go early and whether it takes the serial schedule.  xhat_dev == nullptr: every row is an overlap-save row
+// and no spectrum is computed.
+template <typename T>
+int transform_impl(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev, const Mother& mo, int nrows, void* W_dev,
+                   int64_t ldw, int64_t ncols) {
+  if (int rc = check_geometry(p)) return rc;
+  // the overlap-save rows need the signal only: their block spectra are queued on side stream 1 BEFORE the forward FFT, so that
+  // they run beside it and beside the two-pass chain
+  const bool ols_early = xhat_dev && p->rt->n_ols && p->ols_early && !p->profile;
+  if (serial_schedule(p, ols_early)) return transform_serial<T>(p, x_dev, n0, xhat_dev, mo, W_dev, ldw, ncols);
+  int rc = ols_early ? launch_ols_early<T>(p, x_dev, n0, false) : CWT_OK;
+  if (!rc && xhat_dev) rc = fft_rows_impl<T, IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev);
+  return rc ? rc : rows_launch<T>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0, ols_early);
+}
+
 template <typename T>
 int set_func_attrs() {
   // Workgroups use up to wg_points*sizeof(T) = 128 KiB of dynamic LDS; above 64 KiB HIP wants the
@@ -965,24 +1018,6 @@ int fill_poly_tables(cwt_plan* p) {
     hipLaunchKernelGGL((k_poly_rtab<T>), dim3(((1u << e.logK) + 256u) / 256u, unsigned(e.deg + 1)), dim3(256), 0, p->stream, e.logK, e.deg,
                        out + e.off);
   HIPCHECK(hipGetLastError());
-  return CWT_OK;
-}
-
-template <typename T>
-int launch_ols_early(cwt_plan* p, const void* x_dev, int64_t n0) {
-  int rc = grow(&p->xs, &p->xs_bytes, size_t(p->rt->ols_xs_elems) * sizeof(cplx<T>), p->stream);
-  if (rc) return rc;
-  HIPCHECK(hipEventRecord(p->ev_fork, p->stream));        // after the previous call's work and the row-table upload
-  HIPCHECK(hipStreamWaitEvent(p->side[1], p->ev_fork, 0));
-  if (p->call.ols_first_on_main) {                      // serial_rows = 2: the first rows' spectra where the rows will follow
-    rc = launch_ols_fwd<T>(p, x_dev, n0, p->stream, nullptr, 0, 0);
-    if (!rc) rc = launch_ols_fwd<T>(p, x_dev, n0, p->side[1], nullptr, 0, -2);    // (the half-size tiles' longer blocks)
-    if (!rc) rc = launch_ols_fwd<T>(p, x_dev, n0, p->side[1], nullptr, 1);
-  } else {
-    rc = launch_ols_fwd<T>(p, x_dev, n0, p->side[1], p->ev_b[0]);     // (the rows follow in rows_launch)
-  }
-  if (rc) return rc;
-  HIPCHECK(hipEventRecord(p->ev_ols, p->side[1]));      // serial schedule: all block spectra exist (the other one records it again behind the rows)
   return CWT_OK;
 }
 
@@ -1316,10 +1351,10 @@ int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g
   X int fft_rows_impl<T, IN_REAL>(cwt_plan*, const void*, int64_t, int, int64_t, void*);                                            \
   X int fft_rows_impl<T, IN_CPLX>(cwt_plan*, const void*, int64_t, int, int64_t, void*);                                            \
   X int rows_impl<T>(cwt_plan*, const void*, const Mother&, int, void*, int64_t, int64_t, const void*, int64_t);                    \
+  X int transform_impl<T>(cwt_plan*, const void*, int64_t, void*, const Mother&, int, void*, int64_t, int64_t);                \
   X int fill_ols_tables<T>(cwt_plan*, const Mother&);                                                                               \
   X int fill_aols_tables<T>(cwt_plan*, const Mother&);                                                                              \
   X int fill_poly_tables<T>(cwt_plan*);                                                                                             \
-  X int launch_ols_early<T>(cwt_plan*, const void*, int64_t);                                                                       \
   X int wct_products_impl<T>(cwt_plan*, const void*, const void*, const double*, int, int64_t, int64_t, void*, void*, void*);       \
   X int boxcar_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, const double*, int, void*);                                   \
   X int coherence_impl<T>(cwt_plan*, const void*, const void*, int, int64_t, int64_t, void*);                                       \

@@ -78,13 +78,10 @@ struct cwt_plan {
   int prec = 64;
   int max_rows = 0;
   hipStream_t stream = nullptr;
-  // State of the one cwt_transform / cwt_transform_batch in progress, read by the launches of launch_impl.hpp.  Written only
+  // State of the one cwt_transform / cwt_transform_batch in progress, read by launches deep in launch_impl.hpp.  Written only
   // inside that call's CallScope (launch_impl.hpp), which clears it again on every way out.
   struct Call {
-    hipEvent_t spectrum_ready = nullptr;   // recorded behind the forward FFT when that ran on side stream 0
-    int fft_small = 0;                     // the forward FFT being queued on side stream 0 (serial_rows = 2) takes half-size tiles
-    int ols_launched = 0;                  // the block spectra of the overlap-save rows are queued already (launch_ols_early)
-    int ols_first_on_main = 0;             // serial_rows = 2: ... those of the half-size tiles on the caller's stream
+    int fft_small = 0;                     // the serial schedule's forward FFT, queued on side stream 0, takes half-size tiles
     int64_t ols_x_ld = 0;                  // cwt_transform_batch: elements between the signals of the batch
   };
   Call call;
@@ -120,7 +117,6 @@ struct cwt_plan {
   int poly_degree = 8;     // preferred largest degree: the interval count K' of a row is the smallest that needs no more
   int poly_min_logn = 16;  // shortest transform that takes the form
   int poly_max_logk = 14;  // largest log2 K' (tuning: 13 keeps the rows that need 16384 intervals out of the form)
-  int coef_small = 0;      // interval coefficients of every K' in one launch of 256-thread workgroups (K' = 8192 / 16384 split in 2 / 4); measured slower (EXPERIMENTS R6.2)
   int adjoint_poly = 1;    // cwt_adjoint_rows: the rows of form P through its transpose (k_poly_moments); 0 = every row through the general path
   int poly_chunk_mb = 96;  // coefficient planes computed and consumed per chunk of polynomial rows (MiB; 0 = all rows at once)
   int host_direct = 1;     // cwt_execute_host, transforms that fit one workgroup: the kernels read the signal from / write W into page-locked host memory
@@ -128,13 +124,8 @@ struct cwt_plan {
   int aols_zc = 1;         // Paul rows not clipped at Nyquist on the band-passed signal too, their profile continued through f = 0
   int aols_long = 1;       // complex128: clipped rows with halos of 512 ... 2048 samples in the second (8192-point) class of the band-passed rows
   int aols_min_rows = 3;   // ... if at least this many rows qualify (the band-passed signal costs about one two-pass row)
-  int serial_rows = 2;     // (complex128; complex64 plans start at 0: measured +-0 ... +1.5 % there) long transforms with polynomial rows: every kernel that writes W on the caller's stream, one after the
-                           // other, the preparation on the side streams (rows_launch_serial); 2 = also the first block spectra on the
-                           // caller's stream (its rows follow at a kernel boundary) and the forward FFT on side stream 0
-  int serial_s1_once = 1;  // serial schedule: the caller's stream waits ONCE for side stream 1 (block spectra of the longer blocks, band-passed signal
-                           // and its block spectra: one in-order chain) instead of once per consumer
-  int fft_aside_small = 1; // serial_rows = 2: the forward FFT (on side stream 0 beside the first overlap-save rows) on half-size tiles
-  int aols_small_b = 1;    // serial schedule, complex128: the band-passed signal's second pass on 4096-point tiles (256-thread workgroups)
+  int serial_rows = 2;     // 2 = the serial schedule for long transforms with polynomial rows (rows_launch_serial), 0 = the round-5
+                           // schedule (complex128; complex64 plans start at 0: measured +-0 ... +1.5 % there)
   int ols_min_logn = 18;   // shortest transform that takes the form (measured: 2^18 +12 %, 2^17 -10 %, 2^16 -13 %)
   int ols_small_max_halo = 512;   // rows with a halo up to this many samples run on half-size tiles (0 = none)
   int ols_small_big = 1;   // half-size tiles: rows with a halo in (ols_small_max_halo, 1024] and a block support <= 1/8 tile
@@ -142,8 +133,6 @@ struct cwt_plan {
                            // tile (one 512-thread workgroup per 8192-point block: two per CU, the slowest row kernel of the step)
   int ols_big = 1;         // tile 8192: blocks of 2P points for rows with long halos (two workgroups per block)
   int ols_big_min_halo = 1536;   // measured: equal cost below (strided segments + twice the twiddle range against the kept fraction)
-  int ols_big4_min_halo = 2048;  // ols_big = 2: rows with a halo from here on use blocks of 4P points (four workgroups per block)
-  int ols_big4_max_halo = 8192;  // ... up to this halo (a quarter of the block at most)
   int ols_max_halo = 0;    // largest halo H of such a row in samples; 0 = a quarter of the workgroup tile (L >= P/2)
   double ols_fwd_weight = 1.0;   // cost of one block spectrum in units of one row's block transform (class grouping)
   // Accuracy target of a row, max|dW| / max|W| against the exact transform (cwt_plan_set_tolerance; 0 = the precision's
@@ -201,7 +190,7 @@ struct cwt_plan {
       cwt::OlsClasses cls{};                  // halo classes of this group (wg_first / row_first relative to the group)
       long wgs = 0;                      // workgroups of its k_ols_ct launch
       long wgs_base = 0;                 // ... of which the classes on blocks of ONE tile come first (their block spectra are the first to exist)
-      long fwd_blocks[3] = {0, 0, 0};    // blocks of P, 2P, 4P points (k_ols_fwd_r launches)
+      long fwd_blocks[2] = {0, 0};       // blocks of P, 2P points (k_ols_fwd_r launches)
       int row_first = 0, nrows = 0;      // its rows inside [ols_first, ols_first + n_ols)
     };
     OlsGroup ols_grp[2];
@@ -219,7 +208,6 @@ struct cwt_plan {
       int row_first = 0, nrows = 0, max_logk = 8;   // rows relative to poly_first
       cwt::PolyClasses cls{};                            // (row_first of a class relative to the chunk)
       long wgs[3] = {0, 0, 0};                      // workgroups of the k_poly_coef launches on 4096- / 8192- / 16384-point tiles
-      long wgs_all = 0;                             // ... of the single launch of k_poly_coef_all (option "coef_small")
     };
     std::vector<PolyChunk> poly_chunks;
     long poly_coef_elems = 0, poly_band_elems = 0;

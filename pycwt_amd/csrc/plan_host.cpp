@@ -508,7 +508,7 @@ struct Gates {
   Tolerances tol;                // (tolerances(p))
   double f_lo = 0, f_hi = 0;     // the mother's support (profile argument) at tol.support
   double fc_lo = 0, fc_hi = 0;   // ... at tol.clip: a row whose bins at Nyquist lie outside it vanishes there
-  bool use_small, multi_ok, big_ok, band_pass_a, ols_ok, ols_big, ols_big4, aols_ok, poly_ok;
+  bool use_small, multi_ok, big_ok, band_pass_a, ols_ok, ols_big, aols_ok, poly_ok;
   int narrow_cap, tp_logk, ols_logp_s, ols_hmax, ols_nbatch, aols_nbatch;
   double ols_ch;                 // halo of an overlap-save row in scales (time_halo_factor)
 };
@@ -536,7 +536,6 @@ Gates gates(const cwt_plan* p, const RowRequest& r) {
   g.ols_logp_s = p->ols_small_max_halo > 0 ? kOlsLogp - 1 : 0;     // half-size tiles for short halos
   g.ols_hmax = p->ols_max_halo > 0 ? std::min(p->ols_max_halo, (1 << kOlsLogp) / 4) : (1 << kOlsLogp) / 4;
   g.ols_big = g.ols_ok && p->ols_big && p->logN >= kOlsLogp + 3;   // blocks of 2P points
-  g.ols_big4 = g.ols_big && p->ols_big >= 2 && p->logN >= kOlsLogp + 4;   // ... and of 4P points
   g.ols_ch = g.ols_ok ? time_halo_factor(r.mother, r.param, g.tol.halo) : 0.0;
   // rows clipped at Nyquist as overlap-save rows on the band-passed complex signal (k_aols_*): needs the spectrum only;
   // Morlet and Paul (a real mother constant and nothing to keep on the masked-out bins), one shared spectrum
@@ -641,15 +640,14 @@ RowDesc block_row(const cwt_plan* p, const RowRequest& r, const Gates& g, const 
 }
 
 // The overlap-save form of a row (see k_ols_ct), false if it has none: halo H = c_H * (scale in samples), a multiple of 64 so
-// that whole wavefronts fall inside or outside the kept part of a block.  Block length P_b = P, or 2P / 4P where that keeps a
+// that whole wavefronts fall inside or outside the kept part of a block.  Block length P_b = P, or 2P where that keeps a
 // larger fraction of every block transform and the stores stay >= 128-byte segments (K <= P/8).
 bool ols_candidate(const cwt_plan* p, const RowRequest& r, const Gates& g, const RowSupport& s, OlsRow* o) {
   const RowDesc& rd = s.rd;
   if (!g.ols_ok || !s.vanishes || rd.nband == 0) return false;
   const double s_samples = rd.a * double(p->N) / 6.283185307179586476925;
   const double hh = std::ceil(g.ols_ch * s_samples / 64.0) * 64.0;
-  const double cap = g.ols_big4 ? std::max(double(std::min(p->ols_big4_max_halo, 4 * g.ols_hmax)), 2.0 * g.ols_hmax)
-                                : double(g.ols_hmax) * (g.ols_big ? 2.0 : 1.0);
+  const double cap = double(g.ols_hmax) * (g.ols_big ? 2.0 : 1.0);
   if (hh > cap) return false;
   const int halo = std::max(64, int(hh)), ls = g.ols_logp_s;
   if (ls && p->ols_small_big && halo > p->ols_small_max_halo && halo <= (1 << (ls + 1)) / 8 && p->logN >= ls + 3) {
@@ -659,10 +657,6 @@ bool ols_candidate(const cwt_plan* p, const RowRequest& r, const Gates& g, const
     if (two.logK <= ls - 3) { *o = {two, 0, ls + 1, halo / 64}; return true; }
   }
   if (ls && halo <= p->ols_small_max_halo) { *o = {block_row(p, r, g, rd, ls, ls), 0, ls, halo / 64}; return true; }
-  if (g.ols_big4 && halo >= p->ols_big4_min_halo) {           // blocks of 4P points: the stores stay >= 128-byte segments
-    const RowDesc big = block_row(p, r, g, rd, kOlsLogp + 2, kOlsLogp);   // while K <= P/8, as for 2P
-    if (big.logK <= kOlsLogp - 3) { *o = {big, 1, kOlsLogp + 2, halo / 64}; return true; }
-  }
   if (g.ols_big && halo >= p->ols_big_min_halo && halo <= 2 * g.ols_hmax) {
     const RowDesc big = block_row(p, r, g, rd, kOlsLogp + 1, kOlsLogp);
     if (big.logK <= kOlsLogp - 3) { *o = {big, 1, kOlsLogp + 1, halo / 64}; return true; }
@@ -1029,7 +1023,7 @@ void ols_layout(const cwt_plan* p, const RowRequest& r, const Gates& g, std::vec
     OlsClasses& oc = grp.cls;
     grp.row_first = row0;
     long wg = 0;
-    for (int lb = grp.logp; lb <= grp.logp + 2; ++lb) {
+    for (int lb = grp.logp; lb <= grp.logp + 1; ++lb) {
       int nr = 0;
       while (row0 + nr < int(rows.size()) && rows[row0 + nr].grp == gi && rows[row0 + nr].lb == lb) ++nr;
       if (!nr) continue;
@@ -1039,8 +1033,7 @@ void ols_layout(const cwt_plan* p, const RowRequest& r, const Gates& g, std::vec
         if (hv.empty() || hv.back() != rows[i].h64) { hv.push_back(rows[i].h64); pre.push_back(pre.back()); }
         pre.back()++;
       }
-      const int kmax = (lb == grp.logp || !g.ols_big4) ? OLS_MAX_CLASSES / 2 : OLS_MAX_CLASSES / 4;
-      const std::vector<int> cuts = halo_class_cuts(hv, pre, kmax, Pb, p->ols_fwd_weight * nbatch);
+      const std::vector<int> cuts = halo_class_cuts(hv, pre, OLS_MAX_CLASSES / 2, Pb, p->ols_fwd_weight * nbatch);
       int lo_d = 0; long blk = 0;
       for (const int hi_d : cuts) {
         const int H = 64 * hv[hi_d - 1], Lk = Pb - 2 * H;
@@ -1148,7 +1141,7 @@ int poly_layout(const cwt_plan* p, std::vector<RowDesc>& rows, RowLayout* L) {
     PolyClasses& pc = ch.cls;
     if (pc.n == 0 || pc.c[pc.n - 1].logK != r.logK) {
       if (pc.n == POLY_MAX_CLASSES) return fail(CWT_EINVAL, "too many polynomial-row classes");
-      pc.c[pc.n++] = PolyClass{r.logK, int(i) - ch.row_first, 0, 0, 0, 0};
+      pc.c[pc.n++] = PolyClass{r.logK, int(i) - ch.row_first, 0, 0, 0};
     }
     PolyClass& c = pc.c[pc.n - 1];
     c.nrows++;
@@ -1162,10 +1155,6 @@ int poly_layout(const cwt_plan* p, std::vector<RowDesc>& rows, RowLayout* L) {
       long& wg = ch.wgs[tile - 12];
       c.wg_first = int(wg);
       wg += (long(c.nrows) * c.ndeg + tb - 1) / tb;
-      // the single launch on 4096-point tiles: K' > 4096 takes K' / 4096 workgroups per job, in groups of 8 jobs
-      const long jobs = long(c.nrows) * c.ndeg, s = c.logK > 12 ? 1L << (c.logK - 12) : 1;
-      c.wg_first1 = int(ch.wgs_all);
-      ch.wgs_all += c.logK > 12 ? ((jobs + 7) / 8) * 8 * s : (((jobs << c.logK) + 4095) / 4096 + 7) / 8 * 8;
     }
   L->poly_coef_elems = off; L->poly_band_elems = boff;
   // tables of the economised weights: one per (K', D) pair, (D + 1) x (K' + 1) reals (|kappa| = 0 ... K'; the sign of an odd
@@ -1208,9 +1197,10 @@ int build_row_table(cwt_plan* p, const RowRequest& r) {
   return CWT_OK;
 }
 
-// Does the current row table take the serial schedule of rows_launch_serial (launch_impl.hpp)?  Long transforms whose rows are
-// polynomial rows plus any of overlap-save / band-passed / two-pass rows, one signal, not while profiling (every timed kernel
-// runs alone on the plan's stream then).
+// Does the current row table take the serial schedule (launch_impl.hpp)?  Long transforms whose rows are polynomial rows plus
+// any of overlap-save / band-passed / two-pass rows, one signal, not while profiling (every timed kernel runs alone on the plan's
+// stream then).  ols_early: the call queues the block spectra of its overlap-save rows early (only cwt_transform does); without
+// that, a table with overlap-save rows keeps the round-5 schedule.  Each call asks once, before it queues anything.
 bool serial_schedule(const cwt_plan* p, bool ols_early) {
   const auto* rt = p->rt;
   return p->serial_rows && p->overlap_narrow && !p->profile && p->logN >= 18 && rt->n_poly && !rt->n_narrow && !rt->n_small &&

@@ -184,11 +184,20 @@ def test_k2048_single_pass_rows(emu_library, kind, param):
 
 def test_lab_only_options_are_refused_by_the_product_sources(emu_library):
     """The options of measured-and-rejected variants and diagnostics that have left the sources (EXPERIMENTS.md has their
-    measurements) are refused by name: those of rounds 1-3, which left in round 4, and "graph" (HIP graph replay)."""
+    measurements) are refused by name: those of rounds 1-3, which left in round 4, "graph" (HIP graph replay) and the
+    launch variants of round 6.  The values of kept options that selected such a variant are refused the same way, so that
+    an old script fails instead of taking another schedule."""
     plan = _hip.Plan(1 << 12, 64, max_rows=4, lib=emu_library)
-    for key in ("overlap", "pass_b_prefetch", "pass_b_small", "stamps", "ols_tile", "ols_fwd_real", "sched", "narrow_wave", "graph"):
+    for key in ("overlap", "pass_b_prefetch", "pass_b_small", "stamps", "ols_tile", "ols_fwd_real", "sched", "narrow_wave", "graph",
+                "serial_s1_once", "fft_aside_small", "aols_small_b", "coef_small", "ols_big4_min_halo", "ols_big4_max_halo"):
+        for value in (0, 1):
+            with pytest.raises(_hip.HipError, match="EXPERIMENTS.md"):
+                plan.set_option(key, value)
+    for key, value in (("serial_rows", 1), ("serial_rows", 3), ("ols_big", 2)):
         with pytest.raises(_hip.HipError, match="EXPERIMENTS.md"):
-            plan.set_option(key, 1)
+            plan.set_option(key, value)
+    for key, value in (("serial_rows", 0), ("serial_rows", 2), ("ols_big", 0), ("ols_big", 1)):
+        plan.set_option(key, value)
     plan.close()
 
 
@@ -349,11 +358,11 @@ def test_overlap_save_needs_the_signal_and_follows_its_options(emu_library):
     (orc.MORLET, 6, 64, {"ols_big": 1, "ols_big_min_halo": 256}),   # fp64: double-length blocks are opt-in
     (orc.MORLET, 6, 64, {"ols_big": 0}),
     (orc.PAUL, 4, 32, {"ols_big_min_halo": 512}),
-    (orc.MORLET, 6, 64, {"ols_big": 2, "ols_big4_min_halo": 1024}),   # blocks of four tiles (one 16384-point packed block spectrum)
-    (orc.MORLET, 6, 64, {"ols_small_big": 0}),             # no 8192-point blocks on pairs of half-size tiles
-    (orc.MORLET, 6, 64, {"ols_small_max_halo": 0}),        # every row on the default tile
-    (orc.DOG, 2, 32, {"ols_small_max_halo": 1024}),        # half-size tiles up to their limit (half the block is halo)
-])
+    # (the ids of the cases below stay those they had before the case of blocks of four tiles, opts3, left with ols_big = 2)
+    pytest.param(orc.MORLET, 6, 64, {"ols_small_big": 0}, id="0-6-64-opts4"),      # no 8192-point blocks on pairs of half-size tiles
+    pytest.param(orc.MORLET, 6, 64, {"ols_small_max_halo": 0}, id="0-6-64-opts5"),  # every row on the default tile
+    pytest.param(orc.DOG, 2, 32, {"ols_small_max_halo": 1024}, id="2-2-32-opts6"),  # half-size tiles up to their limit (half the
+])                                                                                  # block is halo)
 def test_overlap_save_block_and_tile_options(emu_library, kind, param, prec, opts):
     N = 1 << 17
     x = np.random.default_rng(8).standard_normal(N - 77)
@@ -367,10 +376,7 @@ def test_overlap_save_block_and_tile_options(emu_library, kind, param, prec, opt
     if opts == {"ols_big": 0}:     # default tiles: short halos on half-size tiles, the rest on the default tile, in ONE transform
         assert any(c.endswith("/half") for c in classes) and any(c.startswith("ols/") and not c.endswith("/half") for c in classes)
     big = [c for c in classes if c.startswith("ols2/")]
-    if opts.get("ols_big", 0) == 2:
-        assert any(c.startswith("ols4/") for c in classes), sorted(set(classes))
-    else:
-        assert bool(big) == (opts.get("ols_big", int(prec == 32)) == 1), sorted(set(classes))
+    assert bool(big) == (opts.get("ols_big", int(prec == 32)) == 1), sorted(set(classes))
     if "ols_small_max_halo" in opts:
         assert any(c.endswith("/half") for c in classes) == (opts["ols_small_max_halo"] > 0)
     if opts == {"ols_small_big": 0}:
@@ -410,7 +416,6 @@ def test_launch_order_of_the_band_limited_rows_does_not_change_a_bit(emu_library
     (orc.DOG, 2, 32, 15, 8, 16, 0, None),
     (orc.MORLET, 6, 64, 15, 8, 40, 777, None),              # padded signals; scales that share a halo class and a halo
     (orc.DOG, 2, 64, 15, 9, 20, 5, {"ols_small_max_halo": 0}),
-    (orc.MORLET, 6, 64, 16, 5, 18, 0, {"ols_big": 2, "ols_big4_min_halo": 1024}),
 ])
 def test_batch_of_signals_takes_the_overlap_save_form(emu_library, kind, param, prec, logn, nb, rows, n0_off, opts):
     """cwt_transform_batch: forward transforms + rows of a batch from the SIGNALS.  The batch counts towards the length

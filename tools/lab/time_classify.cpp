@@ -54,8 +54,8 @@ void dump_table(const char* name, const cwt_plan* p, int rc) {
   for (const auto& g : t->narrow_groups) printf("narrow_group %d %d %d %d\n", g.logK, g.first, g.count, g.nterms);
   for (int g = 0; g < 2; ++g) {
     const auto& G = t->ols_grp[g];
-    printf("ols_grp %d logp %d n %d wgs %ld wgs_base %ld fwd %ld %ld %ld rows %d %d wg_first", g, G.logp, G.cls.n, G.wgs, G.wgs_base,
-           G.fwd_blocks[0], G.fwd_blocks[1], G.fwd_blocks[2], G.row_first, G.nrows);
+    printf("ols_grp %d logp %d n %d wgs %ld wgs_base %ld fwd %ld %ld rows %d %d wg_first", g, G.logp, G.cls.n, G.wgs, G.wgs_base,
+           G.fwd_blocks[0], G.fwd_blocks[1], G.row_first, G.nrows);
     for (int i = 0; i < OLS_MAX_CLASSES; ++i) printf(" %d", G.cls.wg_first[i]);
     printf("\n");
     for (int i = 0; i < G.cls.n; ++i) {
@@ -70,10 +70,10 @@ void dump_table(const char* name, const cwt_plan* p, int rc) {
     printf("aols_geom %d %d %d %d %a %a %a %a %a\n", g->nrows, g->nblocks, g->halo, g->ksp, g->f_s, g->f1_lo, g->z, g->zc_c, g->zc_w);
   printf("aols logp %d nbatch %d wgs %ld wgs2 %ld gt %ld\n", t->aols_logp, t->aols_nbatch, t->aols_wgs, t->aols2_wgs, t->aols_gt_elems);
   for (const auto& ch : t->poly_chunks) {
-    printf("poly_chunk %d %d %d wgs %ld %ld %ld all %ld\n", ch.row_first, ch.nrows, ch.max_logk, ch.wgs[0], ch.wgs[1], ch.wgs[2], ch.wgs_all);
+    printf("poly_chunk %d %d %d wgs %ld %ld %ld\n", ch.row_first, ch.nrows, ch.max_logk, ch.wgs[0], ch.wgs[1], ch.wgs[2]);
     for (int i = 0; i < ch.cls.n; ++i) {
       const PolyClass& c = ch.cls.c[i];
-      printf("  poly_class %d %d %d %d %d %d\n", c.logK, c.row_first, c.nrows, c.ndeg, c.wg_first, c.wg_first1);
+      printf("  poly_class %d %d %d %d %d\n", c.logK, c.row_first, c.nrows, c.ndeg, c.wg_first);
     }
   }
   for (const auto& r : t->poly_rtabs) printf("poly_rtab %d %d %ld\n", r.logK, r.deg, r.off);
@@ -87,7 +87,7 @@ int dump() {
     {"base", [](cwt_plan*) {}},
     {"poly=0", [](cwt_plan* p) { p->poly = 0; }}, {"ols=0", [](cwt_plan* p) { p->ols = 0; }},
     {"aols_zc=0", [](cwt_plan* p) { p->aols_zc = 0; }}, {"aols_long=0", [](cwt_plan* p) { p->aols_long = 0; }},
-    {"ols_big=2", [](cwt_plan* p) { p->ols_big = 2; }}, {"ols_small_max_halo=0", [](cwt_plan* p) { p->ols_small_max_halo = 0; }},
+    {"ols_small_max_halo=0", [](cwt_plan* p) { p->ols_small_max_halo = 0; }},
     {"poly_cheb=0", [](cwt_plan* p) { p->poly_cheb = 0; }}, {"poly_chunk_mb=0", [](cwt_plan* p) { p->poly_chunk_mb = 0; }},
     {"narrow_mix^", [](cwt_plan* p) { p->narrow_mix = !p->narrow_mix; }}};
   char name[256];
