@@ -271,6 +271,33 @@ int cwt_transform(cwt_plan* plan, const void* x_dev, int64_t n0, int mother, dou
                   const double* scales_host, int nrows, void* xhat_dev, void* W_dev, int64_t ldw,
                   int64_t ncols);
 
+/* ---- power output: |W|^2 instead of W ----------------------------------------------------------------------------------
+ * What nearly every caller of the reference does next (sample/simple_sample.py:64: power = (numpy.abs(wave)) ** 2), fused
+ * into the row kernels: P[j, n] = Re(W[j, n])^2 + Im(W[j, n])^2 as ONE real of the plan's precision, half the bytes of W
+ * written and downloaded.  Each *_power function mirrors its sibling -- the same arguments, checks, row table (the output is
+ * not part of the row-table key: a power call after a transform call of the same scales hits the cached table), schedule
+ * and NaN behaviour -- with P_dev / P_host an nrows x ldp matrix of reals of the plan's precision in place of W (ldp >=
+ * ncols; columns ncols .. ldp - 1 and rows not asked for are left untouched).  Fused in every row form of the built-in
+ * mothers: single-workgroup, band-limited single pass, two-pass, overlap-save (both precisions, paired complex64 blocks),
+ * overlap-save on the band-passed signal (DOG's Nyquist-corrected rows included), polynomial (which skip the carrier
+ * rotation: |e^{i phi} v| = |v|, so P differs from |W|^2 at rounding level).  Not fused: filter banks of the caller's
+ * (cwt_transform_rows_table) and the Bluestein path (cwt_transform_rows_n); compute W and square it with cwt_abs2.
+ * The output mode is state of the call only: calls of either kind may alternate on one plan.                              */
+int cwt_transform_power(cwt_plan* plan, const void* x_dev, int64_t n0, int mother, double param, double dt,
+                        const double* scales_host, int nrows, void* xhat_dev, void* P_dev, int64_t ldp,
+                        int64_t ncols);
+/* cwt_transform_rows with the power output: the rows from a spectrum already on the device (the path of the Python shim for
+ * non-finite samples: every element NaN, as in the reference).                                                           */
+int cwt_transform_rows_power(cwt_plan* plan, const void* xhat_dev, int mother, double param, double dt,
+                             const double* scales_host, int nrows, void* P_dev, int64_t ldp, int64_t ncols);
+/* cwt_transform_batch with the power output: P_dev is nbatch x nrows x ldp reals, P[b, j, :] = power of row j of signal b. */
+int cwt_transform_batch_power(cwt_plan* plan, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother,
+                              double param, double dt, const double* scales_host, int nrows, void* xhat_dev, void* P_dev,
+                              int64_t ldp, int64_t ncols);
+/* P[j, n] = |W[j, n]|^2 of a complex matrix already on the device, n < ncols: the power of the paths that are not fused (a
+ * filter bank of the caller's, Bluestein).  W_dev: nrows x ldw complex, P_dev: nrows x ldp reals (may not alias W_dev).   */
+int cwt_abs2(cwt_plan* plan, const void* W_dev, int64_t ldw, int64_t ncols, int nrows, void* P_dev, int64_t ldp);
+
 /* The same two steps at a transform length n0 that is NOT a power of two -- what the reference computes when pyfftw is
  * installed: helpers.py:15-19 then passes n = len(signal), i.e. no zero padding and circular edges -- by Bluestein's
  * chirp-z identity on this plan's power-of-two engine.  The plan must have nfft >= 2*n0 - 1.  xhat_dev: n0 complex
@@ -358,13 +385,18 @@ int cwt_icwt_reduce(cwt_plan* plan, const void* W_dev, int64_t ldw, int64_t ncol
 /* Weighted reduction over scales with explicit weights:
  *   out[n] = coeff * sum_j g(W[j, n]) * weights[j],  g = Re (power = 0) or |.|^2 (power = 1).
  * power = 1 with weights 1/s_j on the selected scales (0 elsewhere) and coeff = dj*dt/cdelta is the
- * scale-averaged power of TC98 eq. 24 (sample/simple_sample.py:87-91).  out_dev: ncols reals.       */
+ * scale-averaged power of TC98 eq. 24 (sample/simple_sample.py:87-91).  out_dev: ncols reals.
+ * power = 2: W_dev is a REAL power matrix (nrows x ldw reals of the plan's precision, as the *_power
+ * functions write it) and g = identity: out[n] = coeff * sum_j P[j, n] * weights[j].               */
 int cwt_reduce_scales(cwt_plan* plan, const void* W_dev, int64_t ldw, int64_t ncols, int nrows,
                       const double* weights_host, int power, double coeff, void* out_dev);
 /* Global wavelet spectrum: out[j] = mean_n |W[j, n]|^2 (power.mean(axis=1), simple_sample.py:79).
  * out_dev: nrows reals.                                                                            */
 int cwt_time_mean_power(cwt_plan* plan, const void* W_dev, int64_t ldw, int64_t ncols, int nrows,
                         void* out_dev);
+/* The same global spectrum from a real power matrix: out[j] = mean_n P[j, n], n < ncols (fp64 accumulation).
+ * P_dev: nrows x ldp reals of the plan's precision (the *_power functions); out_dev: nrows reals.  */
+int cwt_time_mean_real(cwt_plan* plan, const void* P_dev, int64_t ldp, int64_t ncols, int nrows, void* out_dev);
 
 /* Monte-Carlo significance of the coherence (pycwt/wavelet.py:609-630, the `wlc` counter):
  *   hist[j, b] += #{ n in [lo[j], hi[j]) : floor(R2[j, n] * nbins) == b },  0 <= b < nbins,
@@ -398,6 +430,12 @@ int cwt_ar1_filter(cwt_plan* plan, const void* e_dev, int64_t tau, int64_t n, do
 int cwt_execute_host(cwt_plan* plan, const void* x_host, int64_t n0, int mother, double param,
                      double dt, const double* scales_host, int nrows, void* W_host,
                      void* xhat_host);
+/* cwt_execute_host with the power output: P_host is nrows x n0 reals of the plan's precision (may be NULL),
+ * through the same two host paths (page-locked direct writes for single-workgroup transforms; the staged or
+ * copied download otherwise) at half the bytes.                                                    */
+int cwt_execute_host_power(cwt_plan* plan, const void* x_host, int64_t n0, int mother, double param,
+                           double dt, const double* scales_host, int nrows, void* P_host,
+                           void* xhat_host);
 
 /* ---- measurement --------------------------------------------------------
  * With option "profile"=1 every kernel class launched since the last call is

@@ -44,6 +44,13 @@ SYMBOLS = [
                                      C.c_int, _P, C.c_int64, C.c_int64]),
     ("cwt_transform", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double),
                                 C.c_int, _P, _P, C.c_int64, C.c_int64]),
+    ("cwt_transform_power", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double),
+                                      C.c_int, _P, _P, C.c_int64, C.c_int64]),
+    ("cwt_transform_rows_power", C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double),
+                                           C.c_int, _P, C.c_int64, C.c_int64]),
+    ("cwt_transform_batch_power", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double,
+                                            C.POINTER(C.c_double), C.c_int, _P, _P, C.c_int64, C.c_int64]),
+    ("cwt_abs2", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64]),
     ("cwt_adjoint_rows", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double,
                                    C.POINTER(C.c_double), C.c_int, _P, C.c_int64, C.c_int]),
     ("cwt_forward_fft_n", C.c_int, [_P, _P, C.c_int64, _P]),
@@ -67,9 +74,12 @@ SYMBOLS = [
     ("cwt_reduce_scales", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_int,
                                     C.c_double, _P]),
     ("cwt_time_mean_power", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
+    ("cwt_time_mean_real", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
     ("cwt_coherence_histogram", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, C.c_int64, C.c_int, _P]),
     ("cwt_execute_host", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_double,
                                    C.POINTER(C.c_double), C.c_int, _P, _P]),
+    ("cwt_execute_host_power", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_double,
+                                         C.POINTER(C.c_double), C.c_int, _P, _P]),
     ("cwt_plan_timings", C.c_int, [_P, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ("cwt_plan_row_classes", C.c_int, [_P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
@@ -395,6 +405,37 @@ class Plan:
         self.lib.check(self.lib.cwt_transform(self.h, _P(x_dev), n0, mother, float(param), float(dt), _dptr(s), s.size,
                                               _P(xhat_dev) if xhat_dev else None, _P(W_dev), ldw, ncols))
 
+    # -- power output: nrows x ldp reals of the plan's precision (|W|^2) in place of W --
+    @_locked
+    def transform_power(self, x_dev: int, n0: int, mother: int, param: float, dt: float, scales, xhat_dev, P_dev: int,
+                        ldp: int, ncols: int):
+        """`transform` writing |W|^2 (cwt_transform_power)."""
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        self.lib.check(self.lib.cwt_transform_power(self.h, _P(x_dev), n0, mother, float(param), float(dt), _dptr(s), s.size,
+                                                    _P(xhat_dev) if xhat_dev else None, _P(P_dev), ldp, ncols))
+
+    @_locked
+    def transform_rows_power(self, xhat_dev: int, mother: int, param: float, dt: float, scales, P_dev: int, ldp: int,
+                             ncols: int):
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        self.lib.check(self.lib.cwt_transform_rows_power(self.h, _P(xhat_dev), mother, float(param), float(dt),
+                                                         _dptr(s), s.size, _P(P_dev), ldp, ncols))
+
+    @_locked
+    def transform_batch_power(self, x_dev: int, nbatch: int, x_ld: int, n0: int, mother: int, param: float, dt: float,
+                              scales, xhat_dev: int, P_dev: int, ldp: int, ncols: int):
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        self.lib.check(self.lib.cwt_transform_batch_power(self.h, _P(x_dev), nbatch, x_ld, n0, mother, float(param),
+                                                          float(dt), _dptr(s), s.size, _P(xhat_dev), _P(P_dev), ldp, ncols))
+
+    @_locked
+    def abs2(self, W_dev: int, ldw: int, ncols: int, nrows: int, P_dev: int, ldp: int):
+        self.lib.check(self.lib.cwt_abs2(self.h, _P(W_dev), ldw, ncols, nrows, _P(P_dev), ldp))
+
+    @_locked
+    def time_mean_real(self, P_dev: int, ldp: int, ncols: int, nrows: int, out_dev: int):
+        self.lib.check(self.lib.cwt_time_mean_real(self.h, _P(P_dev), ldp, ncols, nrows, _P(out_dev)))
+
     @_locked
     def adjoint_rows(self, G_dev: int, nbatch: int, g_batch_ld: int, ldg: int, ncols: int, mother: int, param: float,
                      dt: float, scales, xbar_dev: int, xbar_ld: int, accumulate: bool = False):
@@ -477,7 +518,8 @@ class Plan:
                                                 float(coeff), _P(out_dev)))
 
     @_locked
-    def reduce_scales(self, W_dev: int, ldw: int, ncols: int, weights, power: bool, coeff: float, out_dev: int):
+    def reduce_scales(self, W_dev: int, ldw: int, ncols: int, weights, power, coeff: float, out_dev: int):
+        """power: False / True (complex W: Re or |.|^2), or 2 (W_dev is a real power matrix)."""
         w = np.ascontiguousarray(weights, dtype=np.float64)
         self.lib.check(self.lib.cwt_reduce_scales(self.h, _P(W_dev), ldw, ncols, w.size, _dptr(w), int(power),
                                                   float(coeff), _P(out_dev)))
@@ -515,6 +557,24 @@ class Plan:
         if rc:
             self.lib.check(rc)
         return W, xhat
+
+    @_locked
+    def execute_host_power(self, x, mother: int, param: float, dt: float, scales, want_xhat=True):
+        """`execute_host` with the power output: (P rows x n0 reals of the plan's precision, xhat)."""
+        x = np.ascontiguousarray(x, dtype=self.real)
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        n0 = x.size
+        P = None
+        if self.nfft <= 4096:
+            P = self.lib.pinned.empty((s.size, n0), self.real)
+        if P is None:
+            P = np.empty((s.size, n0), dtype=self.real)
+        xhat = np.empty(self.nfft, dtype=self.cplx) if want_xhat else None
+        rc = self.lib.cwt_execute_host_power(self.h, x.ctypes.data, n0, mother, param, dt, _dptr(s), s.size, P.ctypes.data,
+                                             xhat.ctypes.data if want_xhat else None)
+        if rc:
+            self.lib.check(rc)
+        return P, xhat
 
     @_locked
     def timings(self):

@@ -106,9 +106,11 @@ int prepare_rows_table(cwt_plan* p, bool have_signal, int mother, double param, 
   return prepare_table(p, c);
 }
 
-// Every row of the current row table, as a call of its own (no per-call state)
-int queue_rows(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw, int64_t ncols) {
+// Every row of the current row table, as a call of its own; power: the rows' power instead of W (the call's only state)
+int queue_rows(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw, int64_t ncols,
+               int power = 0) {
   CallScope scope(p);
+  p->call.power = power;
   return scope.done(by_precision(p, [&](auto t) { return rows_impl<decltype(t)>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols); }));
 }
 
@@ -603,14 +605,25 @@ int cwt_forward_fft(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev) 
 
 
 
-int cwt_transform_rows(cwt_plan* p, const void* xhat_dev, int mother, double param, double dt,
-                       const double* scales, int nrows, void* W_dev, int64_t ldw, int64_t ncols) {
+// cwt_transform_rows and cwt_transform_rows_power: one row table (the output is not part of its key)
+static int transform_rows_entry(cwt_plan* p, const void* xhat_dev, int mother, double param, double dt, const double* scales,
+                                int nrows, void* W_dev, int64_t ldw, int64_t ncols, int power) {
   if (!p || !xhat_dev || !scales || !W_dev) return fail(CWT_EINVAL, "NULL argument");
   HIPCHECK(hipSetDevice(p->device));
   int rc = prepare_rows_table(p, false, mother, param, dt, scales, nrows, ldw, ncols);
   if (!rc && p->logN >= 18 && !p->profile) rc = ensure_distinct_queues(p);
   if (rc) return rc;
-  return queue_rows(p, xhat_dev, mother_of(mother, param), nrows, W_dev, ldw, ncols);
+  return queue_rows(p, xhat_dev, mother_of(mother, param), nrows, W_dev, ldw, ncols, power);
+}
+
+int cwt_transform_rows(cwt_plan* p, const void* xhat_dev, int mother, double param, double dt,
+                       const double* scales, int nrows, void* W_dev, int64_t ldw, int64_t ncols) {
+  return transform_rows_entry(p, xhat_dev, mother, param, dt, scales, nrows, W_dev, ldw, ncols, 0);
+}
+
+int cwt_transform_rows_power(cwt_plan* p, const void* xhat_dev, int mother, double param, double dt,
+                             const double* scales, int nrows, void* P_dev, int64_t ldp, int64_t ncols) {
+  return transform_rows_entry(p, xhat_dev, mother, param, dt, scales, nrows, P_dev, ldp, ncols, 1);
 }
 
 // The transpose of cwt_transform_rows.  The row table is the one cwt_transform builds for the same scales and ncols (the forward of a
@@ -631,8 +644,8 @@ int cwt_adjoint_rows(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch
   });
 }
 
-int cwt_transform(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double param, double dt,
-                  const double* scales, int nrows, void* xhat_dev, void* W_dev, int64_t ldw, int64_t ncols) {
+static int transform_entry(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double param, double dt,
+                           const double* scales, int nrows, void* xhat_dev, void* W_dev, int64_t ldw, int64_t ncols, int power) {
   if (!p || !x_dev || !scales || !W_dev) return fail(CWT_EINVAL, "NULL argument");
   if (n0 < 1 || n0 > p->N) return fail(CWT_EINVAL, "n0 must be in [1, nfft]");
   HIPCHECK(hipSetDevice(p->device));
@@ -648,9 +661,20 @@ int cwt_transform(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double
   }
   const Mother mo = mother_of(mother, param);
   CallScope scope(p);
+  p->call.power = power;
   return scope.done(by_precision(p, [&](auto t) {
     return transform_impl<decltype(t)>(p, x_dev, n0, xhat_dev, mo, nrows, W_dev, ldw, ncols);
   }));
+}
+
+int cwt_transform(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double param, double dt,
+                  const double* scales, int nrows, void* xhat_dev, void* W_dev, int64_t ldw, int64_t ncols) {
+  return transform_entry(p, x_dev, n0, mother, param, dt, scales, nrows, xhat_dev, W_dev, ldw, ncols, 0);
+}
+
+int cwt_transform_power(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double param, double dt,
+                        const double* scales, int nrows, void* xhat_dev, void* P_dev, int64_t ldp, int64_t ncols) {
+  return transform_entry(p, x_dev, n0, mother, param, dt, scales, nrows, xhat_dev, P_dev, ldp, ncols, 1);
 }
 
 int cwt_transform_rows_batch(cwt_plan* p, const void* xhat_dev, int nbatch, int64_t xhat_ld, int mother,
@@ -672,9 +696,9 @@ int cwt_transform_rows_batch(cwt_plan* p, const void* xhat_dev, int nbatch, int6
   return queue_rows(p, xhat_dev, mother_of(mother, param), nbatch * nrows, W_dev, ldw, ncols);
 }
 
-int cwt_transform_batch(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother,
-                        double param, double dt, const double* scales, int nrows, void* xhat_dev, void* W_dev,
-                        int64_t ldw, int64_t ncols) {
+static int transform_batch_entry(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother,
+                                 double param, double dt, const double* scales, int nrows, void* xhat_dev, void* W_dev,
+                                 int64_t ldw, int64_t ncols, int power) {
   if (!p || !x_dev || !scales || !xhat_dev || !W_dev) return fail(CWT_EINVAL, "NULL argument");
   if (nbatch < 1 || nrows < 1 || int64_t(nbatch) * nrows > p->max_rows)
     return fail(CWT_EINVAL, "need nbatch*nrows <= max_rows");
@@ -694,9 +718,22 @@ int cwt_transform_batch(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld
   rc = by_precision(p, [&](auto t) { return fft_rows_impl<decltype(t), IN_REAL>(p, x_dev, x_ld, nbatch, n0, xhat_dev); });
   if (rc) return rc;
   p->call.ols_x_ld = x_ld;
+  p->call.power = power;
   return scope.done(by_precision(p, [&](auto t) {
     return rows_impl<decltype(t)>(p, xhat_dev, mo, nbatch * nrows, W_dev, ldw, ncols, x_dev, n0);
   }));
+}
+
+int cwt_transform_batch(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother,
+                        double param, double dt, const double* scales, int nrows, void* xhat_dev, void* W_dev,
+                        int64_t ldw, int64_t ncols) {
+  return transform_batch_entry(p, x_dev, nbatch, x_ld, n0, mother, param, dt, scales, nrows, xhat_dev, W_dev, ldw, ncols, 0);
+}
+
+int cwt_transform_batch_power(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother,
+                              double param, double dt, const double* scales, int nrows, void* xhat_dev, void* P_dev,
+                              int64_t ldp, int64_t ncols) {
+  return transform_batch_entry(p, x_dev, nbatch, x_ld, n0, mother, param, dt, scales, nrows, xhat_dev, P_dev, ldp, ncols, 1);
 }
 
 int cwt_transform_rows_table(cwt_plan* p, const void* xhat_dev, const void* table_dev, const int* k_lo,
@@ -795,9 +832,19 @@ int cwt_reduce_scales(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols
   if (!p || !W_dev || !weights || !out_dev) return fail(CWT_EINVAL, "NULL argument");
   if (nrows < 1 || nrows > p->max_rows) return fail(CWT_EINVAL, "nrows must be in [1, max_rows]");
   if (ncols < 1 || ldw < ncols) return fail(CWT_EINVAL, "need ncols >= 1 and ldw >= ncols");
+  if (power < 0 || power > 2) return fail(CWT_EINVAL, "power must be 0, 1 or 2");
   HIPCHECK(hipSetDevice(p->device));
   return by_precision(p, [&](auto t) {
     using T = decltype(t);
+    if (power == 2) {                                  // W_dev is a real power matrix (cwt_transform_power)
+      int rc = upload_reals<T>(p, weights, nrows);
+      if (rc) return rc;
+      return timed_launch(p, KC_ICWT, [&] {
+        hipLaunchKernelGGL((k_icwt_real<T>), dim3(unsigned((ncols + ICWT_THREADS - 1) / ICWT_THREADS)), dim3(ICWT_THREADS), 0,
+                           p->stream, static_cast<const T*>(W_dev), long(ldw), long(ncols), nrows,
+                           static_cast<const T*>(p->weights_dev), T(coeff), static_cast<T*>(out_dev));
+      });
+    }
     return power ? reduce_scales_impl<T, true>(p, W_dev, ldw, ncols, nrows, weights, coeff, out_dev)
                  : reduce_scales_impl<T, false>(p, W_dev, ldw, ncols, nrows, weights, coeff, out_dev);
   });
@@ -824,6 +871,34 @@ int cwt_time_mean_power(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t nco
     return timed_launch(p, KC_ICWT, [&] {
       hipLaunchKernelGGL((k_time_mean<T>), dim3(nrows), dim3(256), 256 * sizeof(double), p->stream,
                          static_cast<const cplx<T>*>(W_dev), long(ldw), long(ncols), static_cast<T*>(out_dev));
+    });
+  });
+}
+
+int cwt_time_mean_real(cwt_plan* p, const void* P_dev, int64_t ldp, int64_t ncols, int nrows, void* out_dev) {
+  if (!p || !P_dev || !out_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (nrows < 1 || ncols < 1 || ldp < ncols) return fail(CWT_EINVAL, "bad shape");
+  HIPCHECK(hipSetDevice(p->device));
+  return by_precision(p, [&](auto t) {
+    using T = decltype(t);
+    return timed_launch(p, KC_ICWT, [&] {
+      hipLaunchKernelGGL((k_time_mean_real<T>), dim3(nrows), dim3(256), 256 * sizeof(double), p->stream,
+                         static_cast<const T*>(P_dev), long(ldp), long(ncols), static_cast<T*>(out_dev));
+    });
+  });
+}
+
+int cwt_abs2(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols, int nrows, void* P_dev, int64_t ldp) {
+  if (!p || !W_dev || !P_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (nrows < 1 || ncols < 1 || ldw < ncols || ldp < ncols) return fail(CWT_EINVAL, "bad shape");
+  HIPCHECK(hipSetDevice(p->device));
+  return by_precision(p, [&](auto t) {
+    using T = decltype(t);
+    return timed_launch(p, KC_ELEMENTWISE, [&] {
+      for (int r0 = 0; r0 < nrows; r0 += 32768)
+        hipLaunchKernelGGL((k_abs2<T>), dim3(unsigned((ncols + 255) / 256), unsigned(std::min(32768, nrows - r0))), dim3(256), 0,
+                           p->stream, static_cast<const cplx<T>*>(W_dev) + size_t(r0) * size_t(ldw), long(ldw), long(ncols),
+                           static_cast<T*>(P_dev) + size_t(r0) * size_t(ldp), long(ldp));
     });
   });
 }
@@ -917,12 +992,13 @@ int cwt_host_free(void* ptr_host) {
   return CWT_OK;
 }
 
-int cwt_execute_host(cwt_plan* p, const void* x_host, int64_t n0, int mother, double param, double dt,
-                     const double* scales, int nrows, void* W_host, void* xhat_host) {
+// cwt_execute_host and cwt_execute_host_power: the same two host paths, for an output of ow = 2 (W) or 1 (power) reals per element
+static int execute_host_entry(cwt_plan* p, const void* x_host, int64_t n0, int mother, double param, double dt,
+                              const double* scales, int nrows, void* W_host, void* xhat_host, int power) {
   if (!p || !x_host || !scales) return fail(CWT_EINVAL, "NULL argument");
   if (n0 < 1 || n0 > p->N) return fail(CWT_EINVAL, "n0 must be in [1, nfft]");
   HIPCHECK(hipSetDevice(p->device));
-  const size_t es = p->esize();
+  const size_t es = p->esize(), ow = power ? 1 : 2;
   // A transform that fits one workgroup per row (the reference's canonical 504-point call: 4 KB in, 0.8 MB out) is all
   // latency, and copy operations are the larger part of it.  Here it has none: the forward FFT reads the signal from the
   // plan's page-locked staging buffer, the row kernel writes W over PCIe itself -- into W_host when that is a
@@ -930,7 +1006,7 @@ int cwt_execute_host(cwt_plan* p, const void* x_host, int64_t n0, int mother, do
   // copied.  45 us against 83 at 504 x 97, fp64 [measured, profiles/r04_latency.txt; tools/microbench/host_latency.cpp].
   if (W_host && p->host_direct && !p->profile && p->logN > 3 && p->logN <= p->loglmax) {
     const size_t in_b = (size_t(n0) * es + 255) & ~size_t(255), xh_b = size_t(p->N) * 2 * es;
-    const size_t w_b = size_t(nrows) * size_t(n0) * 2 * es;
+    const size_t w_b = size_t(nrows) * size_t(n0) * ow * es;
     const bool w_direct = is_pinned(W_host, w_b);
     if (in_b + xh_b + (w_direct ? 0 : w_b) <= kHostStage) {
       int rc = ensure_hstage(p);
@@ -941,7 +1017,7 @@ int cwt_execute_host(cwt_plan* p, const void* x_host, int64_t n0, int mother, do
       char* stage = static_cast<char*>(p->hstage);
       std::memcpy(stage, x_host, size_t(n0) * es);
       void* W_out = w_direct ? W_host : stage + in_b + xh_b;
-      rc = cwt_transform(p, stage, n0, mother, param, dt, scales, nrows, p->hxhat, W_out, n0, n0);
+      rc = transform_entry(p, stage, n0, mother, param, dt, scales, nrows, p->hxhat, W_out, n0, n0, power);
       if (rc) return rc;
       if (xhat_host) HIPCHECK(hipMemcpyAsync(stage + in_b, p->hxhat, xh_b, hipMemcpyDeviceToHost, p->stream));
       HIPCHECK(hipStreamSynchronize(p->stream));
@@ -952,13 +1028,13 @@ int cwt_execute_host(cwt_plan* p, const void* x_host, int64_t n0, int mother, do
   }
   int rc = grow(&p->hx, &p->hx_bytes, size_t(n0) * es, p->stream);
   if (!rc) rc = grow(&p->hxhat, &p->hxhat_bytes, size_t(p->N) * 2 * es, p->stream);
-  if (!rc && W_host) rc = grow(&p->hW, &p->hW_bytes, size_t(nrows) * size_t(n0) * 2 * es, p->stream);
+  if (!rc && W_host) rc = grow(&p->hW, &p->hW_bytes, size_t(nrows) * size_t(n0) * ow * es, p->stream);
   if (rc) return rc;
   // Small calls (the reference's canonical 504-point series: 4 KB in, 0.7 MB out) are all latency: a copy to or from pageable
   // memory makes the runtime stage and synchronise on its own, once per copy.  They go through ONE page-locked buffer of the
   // plan instead -- memcpy in, three asynchronous copies, one synchronisation, memcpy out.
   const size_t in_b = size_t(n0) * es, xh_b = xhat_host ? size_t(p->N) * 2 * es : 0;
-  const size_t w_b = W_host ? size_t(nrows) * size_t(n0) * 2 * es : 0;
+  const size_t w_b = W_host ? size_t(nrows) * size_t(n0) * ow * es : 0;
   const bool staged = in_b + xh_b + w_b <= kHostStage;
   char* stage = nullptr;
   if (staged) {
@@ -982,7 +1058,7 @@ int cwt_execute_host(cwt_plan* p, const void* x_host, int64_t n0, int mother, do
     if (rc) return rc;
     p->tolerance = tol;
   }
-  if (W_host) rc = cwt_transform(p, p->hx, n0, mother, param, dt, scales, nrows, p->hxhat, p->hW, n0, n0);
+  if (W_host) rc = transform_entry(p, p->hx, n0, mother, param, dt, scales, nrows, p->hxhat, p->hW, n0, n0, power);
   else rc = cwt_forward_fft(p, p->hx, n0, p->hxhat);
   if (rc) return rc;
   if (staged) {
@@ -995,9 +1071,19 @@ int cwt_execute_host(cwt_plan* p, const void* x_host, int64_t n0, int mother, do
   }
   if (xhat_host)
     HIPCHECK(hipMemcpyAsync(xhat_host, p->hxhat, size_t(p->N) * 2 * es, hipMemcpyDeviceToHost, p->stream));
-  if (W_host) return copy_d2h(p, W_host, p->hW, size_t(nrows) * size_t(n0) * 2 * es);
+  if (W_host) return copy_d2h(p, W_host, p->hW, size_t(nrows) * size_t(n0) * ow * es);
   HIPCHECK(hipStreamSynchronize(p->stream));
   return CWT_OK;
+}
+
+int cwt_execute_host(cwt_plan* p, const void* x_host, int64_t n0, int mother, double param, double dt,
+                     const double* scales, int nrows, void* W_host, void* xhat_host) {
+  return execute_host_entry(p, x_host, n0, mother, param, dt, scales, nrows, W_host, xhat_host, 0);
+}
+
+int cwt_execute_host_power(cwt_plan* p, const void* x_host, int64_t n0, int mother, double param, double dt,
+                           const double* scales, int nrows, void* P_host, void* xhat_host) {
+  return execute_host_entry(p, x_host, n0, mother, param, dt, scales, nrows, P_host, xhat_host, 1);
 }
 
 int cwt_plan_timings(cwt_plan* p, int cap, const char** names, double* total_ms, int* launches, int* n) {

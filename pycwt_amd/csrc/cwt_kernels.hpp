@@ -167,11 +167,11 @@ __device__ __forceinline__ int signed_bin(int k, int N) { return k < (N >> 1) ? 
 // k_small: whole transform of length N = 2^logN (16..lmax) inside one workgroup, TB rows per WG.
 // MODE IN_SPECTRUM: rows of W.  MODE IN_REAL: forward FFT of the zero-padded real signal
 // (nrows = 1, out = conj(inverse(x))).
-template <typename T, int MODE>
+template <typename T, int MODE, typename WT = cplx<T>>
 __global__ void __launch_bounds__(CWT_MAX_THREADS)
 k_small(const void* __restrict__ in, const RowDesc* __restrict__ rows, int nrows, Mother mo,
         const cplx<T>* __restrict__ tw, int logN, int logTB, long n0, long in_ld,
-        cplx<T>* __restrict__ out, long ldw, long ncols) {
+        WT* __restrict__ out, long ldw, long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
   const int N = 1 << logN, logNT = logN - 4, NT = 1 << logNT;
@@ -215,14 +215,18 @@ k_small(const void* __restrict__ in, const RowDesc* __restrict__ rows, int nrows
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const long m = g.j + (e << logNT);
-    if (m < ncols) out[orow * ldw + m] = mk<T>(re[e], MODE != IN_SPECTRUM ? -im[e] : im[e]);
+    if constexpr (power_out<T, WT>()) {
+      if (m < ncols) out[orow * ldw + m] = re[e] * re[e] + im[e] * im[e];
+    } else {
+      if (m < ncols) out[orow * ldw + m] = mk<T>(re[e], MODE != IN_SPECTRUM ? -im[e] : im[e]);
+    }
   }
 }
 
 // k_direct: N <= 8.  One thread per output element.
-template <typename T, int MODE>
+template <typename T, int MODE, typename WT = cplx<T>>
 __global__ void k_direct(const void* __restrict__ in, const RowDesc* __restrict__ rows, int nrows,
-                         Mother mo, int logN, long n0, long in_ld, cplx<T>* __restrict__ out, long ldw,
+                         Mother mo, int logN, long n0, long in_ld, WT* __restrict__ out, long ldw,
                          long ncols) {
   const int N = 1 << logN;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -248,7 +252,8 @@ __global__ void k_direct(const void* __restrict__ in, const RowDesc* __restrict_
     si += yr * s + yi * c;
   }
   const long orow = (MODE != IN_SPECTRUM) ? long(row) : long(rows[row].out_row);
-  out[orow * ldw + m] = mk<T>(T(sr), T(MODE != IN_SPECTRUM ? -si : si));
+  if constexpr (power_out<T, WT>()) out[orow * ldw + m] = T(sr) * T(sr) + T(si) * T(si);
+  else out[orow * ldw + m] = mk<T>(T(sr), T(MODE != IN_SPECTRUM ? -si : si));
 }
 
 // slot e *= first * step^e  (the inter-pass twiddle e^{2 pi i q r / N} walked along one index)
@@ -268,11 +273,11 @@ __device__ __forceinline__ void twiddle_slots(T (&re)[16], T (&im)[16], cplx<T> 
 //   W[R m + r] = sum_{q<K} ( Y[k(q)] e^{2 pi i k(q) r / N} ) e^{2 pi i q m / K},
 // k(q) = the only in-band bin congruent to q mod K.  grid = (R/TB, rows of this class);
 // PLANES layout, lanes run along r so that the stores of W are TB*sizeof(complex) contiguous.
-template <typename T>
+template <typename T, typename WT = cplx<T>>
 __global__ void __launch_bounds__(CWT_MAX_THREADS)
 k_narrow(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ rows, Mother mo,
          const cplx<T>* __restrict__ tw, TwN<T> twn, int logN, int logK, int logTB,
-         cplx<T>* __restrict__ W, long ldw, long ncols) {
+         WT* __restrict__ W, long ldw, long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
   const int N = 1 << logN, K = 1 << logK, logNT = logK - 4, NT = 1 << logNT;
@@ -315,7 +320,7 @@ k_narrow(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ rows, Mot
 
   wg_ifft<T, true>(re, im, lds, g, tw);
 
-  cplx<T>* wrow = W + long(rd.out_row) * ldw;
+  WT* wrow = W + long(rd.out_row) * ldw;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const long n = (long(g.j + (e << logNT)) << logR) + r;
@@ -380,10 +385,10 @@ k_pass_a(const void* __restrict__ in, const RowDesc* __restrict__ rows, Mother m
 // k_pass_b: second pass: W[R m + r] = sum_{q<K} (Z[r][q] e^{2 pi i q r / N}) e^{2 pi i q m / K}.
 // grid = (R/TB, rows in chunk).  ROWS layout for the FFT (coalesced reads of Z rows), then an LDS
 // transpose so that lanes run along r for the stores.  CONJ: store conj (forward transform).
-template <typename T, bool CONJ>
+template <typename T, bool CONJ, typename WT = cplx<T>>
 __global__ void __launch_bounds__(CWT_MAX_THREADS)
 k_pass_b(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
-         const cplx<T>* __restrict__ tw, TwN<T> twn, int logN, int logK, int logTB, cplx<T>* __restrict__ W,
+         const cplx<T>* __restrict__ tw, TwN<T> twn, int logN, int logK, int logTB, WT* __restrict__ W,
          long ldw, long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
@@ -420,7 +425,7 @@ k_pass_b(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
   for (int c = 0; c < 16; ++c) im[c] = lds[lds_swizzle<T>(threadIdx.x + c * blockDim.x)];
 
   const long orow = rows ? long(rows[blockIdx.y].out_row) : long(blockIdx.y);
-  cplx<T>* wrow = W + orow * ldw;
+  WT* wrow = W + orow * ldw;
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
     const int idx = threadIdx.x + c * blockDim.x;
@@ -439,9 +444,9 @@ k_pass_b(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
 // Epilogue shared by the ROWS-layout kernels: thread (t, j) holds outputs m = j + e*NT of FFT t (residue
 // r0 + t).  LDS transpose (t, m) -> m*TB + t with one pad element per 16, read back linearly in tid, so
 // that consecutive lanes store consecutive r: W[R m + r0 + t] in TB*sizeof(complex)-byte segments.
-template <typename T, int LOGK, int LOGP, bool CONJ>
+template <typename T, int LOGK, int LOGP, bool CONJ, typename WT>
 __device__ __forceinline__ void transpose_store(T (&re)[16], T (&im)[16], T* lds, int t, int j,
-                                                cplx<T>* __restrict__ wrow, int logR, unsigned r0,
+                                                WT* __restrict__ wrow, int logR, unsigned r0,
                                                 long ncols) {
   constexpr int LOGTB = LOGP - LOGK, NT = 1 << (LOGK - 4), BD = 1 << (LOGP - 4);
   constexpr int TS = (BD) + (BD >> 4);                    // physical stride of BD elements
@@ -529,10 +534,10 @@ __device__ __forceinline__ void narrow_phases(const cplx<T>* __restrict__ xhat, 
     narrow_phases<T, LOGK, LOGP, NTERMS, NQ, PH + 1>(xhat, rd, mo, N, ytile, j, rho, step, stepw, cur, d, re, im);
 }
 
-template <typename T, int LOGK, int LOGP, int NTERMS>
+template <typename T, int LOGK, int LOGP, int NTERMS, typename WT>
 __device__ __forceinline__ void narrow_ct_body(const cplx<T>* __restrict__ xhat, const RowDesc& rd,
                                                const Mother& mo, const cplx<T>* __restrict__ tw_all,
-                                               const TwN<T>& twn, int logN, cplx<T>* __restrict__ W, long ldw,
+                                               const TwN<T>& twn, int logN, WT* __restrict__ W, long ldw,
                                                long ncols, T* lds) {
   constexpr int LOGTB = LOGP - LOGK, K = 1 << LOGK, LOGNT = LOGK - 4, NT = 1 << LOGNT;
   // PLANES layout: lanes run along the residue r, stores go straight from registers in 128-B segments.
@@ -574,7 +579,7 @@ __device__ __forceinline__ void narrow_ct_body(const cplx<T>* __restrict__ xhat,
   narrow_phases<T, LOGK, LOGP, NTERMS, NQ, 0>(xhat, rd, mo, N, ytile, f.j, rho, step, stepw, cur, d, re, im);
   __syncthreads();  // the tiles alias the exchange buffer
   f.run(re, im, lds, tw);
-  cplx<T>* wrow = W + long(rd.out_row) * ldw;
+  WT* wrow = W + long(rd.out_row) * ldw;
   const unsigned off = (unsigned(f.j) << logR) + r;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
@@ -592,17 +597,17 @@ constexpr int narrow_waves_per_simd() {
 // All band-limited rows of a transform in ONE launch: blockIdx.y walks the row table (sorted by
 // class), every workgroup branches once to the body specialised for its row's (K, terms).  One
 // launch instead of one per class removes ~10 kernel boundaries and partial last waves per transform.
-template <typename T, int LOGP>
+template <typename T, int LOGP, typename WT = cplx<T>>
 __global__ void __launch_bounds__(1 << (LOGP - 4), (narrow_waves_per_simd<T, LOGP>()))
 k_narrow_ct_all(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ rows, Mother mo,
-                const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, cplx<T>* __restrict__ W, long ldw,
+                const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, WT* __restrict__ W, long ldw,
                 long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
   const RowDesc rd = rows[blockIdx.y];
 #define CWT_NARROW_CASE(LK, NT_)                                                                    \
   case (LK) + 100 * (NT_):                                                                           \
-    narrow_ct_body<T, LK, LOGP, NT_>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds);          \
+    narrow_ct_body<T, LK, LOGP, NT_, WT>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds);          \
     break;
   switch (rd.logK + 100 * rd.nterms) {
     CWT_NARROW_CASE(4, 1) CWT_NARROW_CASE(5, 1) CWT_NARROW_CASE(6, 1) CWT_NARROW_CASE(7, 1)
@@ -616,16 +621,16 @@ k_narrow_ct_all(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ ro
 
 // Band-limited rows with 5..16 aliased terms of K = 1024 bins (support up to 16384 bins): a kernel of their own so
 // that the common cases above keep their register allocation.
-template <typename T, int LOGP>
+template <typename T, int LOGP, typename WT = cplx<T>>
 __global__ void __launch_bounds__(1 << (LOGP - 4), (narrow_waves_per_simd<T, LOGP>()))
 k_narrow_ct_many(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ rows, Mother mo,
-                 const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, cplx<T>* __restrict__ W, long ldw,
+                 const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, WT* __restrict__ W, long ldw,
                  long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
   const RowDesc rd = rows[blockIdx.y];
 #define CWT_MANY_CASE(NT_)                                                                           \
-  case NT_: narrow_ct_body<T, 10, LOGP, NT_>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
+  case NT_: narrow_ct_body<T, 10, LOGP, NT_, WT>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
   switch (rd.nterms) {
     CWT_MANY_CASE(5) CWT_MANY_CASE(6) CWT_MANY_CASE(7) CWT_MANY_CASE(8) CWT_MANY_CASE(9) CWT_MANY_CASE(10)
     CWT_MANY_CASE(11) CWT_MANY_CASE(12) CWT_MANY_CASE(13) CWT_MANY_CASE(14) CWT_MANY_CASE(15) CWT_MANY_CASE(16)
@@ -638,23 +643,23 @@ k_narrow_ct_many(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ r
 // 16384 points per workgroup (1024 threads, 128 KiB of LDS, one workgroup per CU) so that the stores stay
 // 128-byte segments (TB = 8).  Converts rows of support 4096..8192 from the two-pass transform (48 B per
 // sample*scale of traffic) to the single-pass form (16 B).
-template <typename T>
+template <typename T, typename WT = cplx<T>>
 __global__ void __launch_bounds__(1024, 4)
 k_narrow_ct_big(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ rows, Mother mo,
-                const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, cplx<T>* __restrict__ W, long ldw,
+                const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, WT* __restrict__ W, long ldw,
                 long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
   const RowDesc rd = rows[blockIdx.y];
   switch (rd.nterms) {
-    case 1: narrow_ct_body<T, 11, 14, 1>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
-    case 2: narrow_ct_body<T, 11, 14, 2>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
-    case 3: narrow_ct_body<T, 11, 14, 3>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
-    case 4: narrow_ct_body<T, 11, 14, 4>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
-    case 5: narrow_ct_body<T, 11, 14, 5>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
-    case 6: narrow_ct_body<T, 11, 14, 6>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
-    case 7: narrow_ct_body<T, 11, 14, 7>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
-    case 8: narrow_ct_body<T, 11, 14, 8>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
+    case 1: narrow_ct_body<T, 11, 14, 1, WT>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
+    case 2: narrow_ct_body<T, 11, 14, 2, WT>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
+    case 3: narrow_ct_body<T, 11, 14, 3, WT>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
+    case 4: narrow_ct_body<T, 11, 14, 4, WT>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
+    case 5: narrow_ct_body<T, 11, 14, 5, WT>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
+    case 6: narrow_ct_body<T, 11, 14, 6, WT>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
+    case 7: narrow_ct_body<T, 11, 14, 7, WT>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
+    case 8: narrow_ct_body<T, 11, 14, 8, WT>(xhat, rd, mo, tw_all, twn, logN, W, ldw, ncols, lds); break;
     default: break;
   }
 }
@@ -812,10 +817,10 @@ k_pass_a_ct_rows(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ r
   for (int e = 0; e < 16; ++e) (z + (long(e * NT) << logK))[off] = mk<T>(re[e], im[e]);
 }
 
-template <typename T, int LOGK, int LOGP, bool CONJ>
+template <typename T, int LOGK, int LOGP, bool CONJ, typename WT = cplx<T>>
 __global__ void __launch_bounds__(1 << (LOGP - 4), (sizeof(T) == 8 ? CWT_LB_PASS_B_F64 : CWT_LB_PASS_B_F32))
 k_pass_b_ct(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
-            const cplx<T>* __restrict__ tw, TwN<T> twn, int logN, cplx<T>* __restrict__ W, long ldw, long ncols) {
+            const cplx<T>* __restrict__ tw, TwN<T> twn, int logN, WT* __restrict__ W, long ldw, long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
   constexpr int LOGTB = LOGP - LOGK, LOGNT = LOGK - 4, NT = 1 << LOGNT, BD = 1 << (LOGP - 4);
@@ -839,7 +844,7 @@ k_pass_b_ct(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
   f.run(re, im, lds, tw);
 
   const long orow = rows ? long(rows[blockIdx.y].out_row) : long(blockIdx.y);
-  transpose_store<T, LOGK, LOGP, CONJ>(re, im, lds, f.t, f.j, W + orow * ldw, logR, r0, ncols);
+  transpose_store<T, LOGK, LOGP, CONJ, WT>(re, im, lds, f.t, f.j, W + orow * ldw, logR, r0, ncols);
 }
 
 }  // namespace cwt

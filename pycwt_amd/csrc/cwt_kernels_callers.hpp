@@ -183,6 +183,37 @@ k_icwt(const cplx<T>* __restrict__ W, long ldw, long ncols, int nrows,
   out[n] = coeff * (((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7])));
 }
 
+// The same two reductions over a real power matrix P (cwt_reduce_scales with power = 2): out[n] = coeff sum_j w_j P[j, n]
+template <typename T>
+__global__ void __launch_bounds__(ICWT_THREADS)
+k_icwt_real(const T* __restrict__ P, long ldp, long ncols, int nrows, const T* __restrict__ w, T coeff, T* __restrict__ out) {
+  const long n = long(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (n >= ncols) return;
+  constexpr int U = ICWT_INFLIGHT;
+  T acc[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) acc[u] = T(0);
+  int j = 0;
+  for (; j + U <= nrows; j += U) {
+    T v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = __builtin_nontemporal_load(P + long(j + u) * ldp + n);
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc[u] += v[u] * w[j + u];
+  }
+  for (; j < nrows; ++j) acc[0] += __builtin_nontemporal_load(P + long(j) * ldp + n) * w[j];
+  out[n] = coeff * (((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7])));
+}
+
+// P[j, n] = |W[j, n]|^2 (the power of the paths that compute W first: filter banks of the caller's, Bluestein)
+template <typename T>
+__global__ void k_abs2(const cplx<T>* __restrict__ W, long ldw, long ncols, T* __restrict__ P, long ldp) {
+  const long n = long(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (n >= ncols) return;
+  const cplx<T> v = load_once<T>(W + long(blockIdx.y) * ldw + n);
+  __builtin_nontemporal_store(v.x * v.x + v.y * v.y, P + long(blockIdx.y) * ldp + n);
+}
+
 // Cross wavelet spectrum W12 = W1 conj(W2) (pycwt/wavelet.py:399).  `out` may be W1 (every thread reads its own
 // element of both inputs before it writes).
 template <typename T>
@@ -329,6 +360,32 @@ __global__ void k_time_mean(const cplx<T>* __restrict__ W, long ldw, long ncols,
     const cplx<T> v = load_once<T>(row + n);
     a4[0] += double(v.x) * double(v.x) + double(v.y) * double(v.y);
   }
+  const double acc = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = blockDim.x >> 1; s > 0; s >>= 1) {
+    if (int(threadIdx.x) < s) part[threadIdx.x] += part[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = T(part[0] / double(ncols));
+}
+
+// k_time_mean_real: out[j] = (1/ncols) sum_n P[j, n] over a real power matrix, as k_time_mean
+template <typename T>
+__global__ void k_time_mean_real(const T* __restrict__ P, long ldp, long ncols, T* __restrict__ out) {
+  HIP_DYNAMIC_SHARED(double2, lds_raw)
+  double* part = reinterpret_cast<double*>(lds_raw);
+  const T* row = P + long(blockIdx.x) * ldp;
+  double a4[4] = {0, 0, 0, 0};
+  long n = threadIdx.x;
+  for (; n + 3 * long(blockDim.x) < ncols; n += 4 * long(blockDim.x)) {
+    T v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = __builtin_nontemporal_load(row + n + u * long(blockDim.x));
+#pragma unroll
+    for (int u = 0; u < 4; ++u) a4[u] += double(v[u]);
+  }
+  for (; n < ncols; n += blockDim.x) a4[0] += double(__builtin_nontemporal_load(row + n));
   const double acc = (a4[0] + a4[1]) + (a4[2] + a4[3]);
   part[threadIdx.x] = acc;
   __syncthreads();

@@ -138,10 +138,10 @@ k_ols_fwd_r(const T* __restrict__ x, long n0, int logN, OlsClasses cls, const cp
 }
 
 // Block transform with K = P: every thread filters its own 16 bins (rows whose block support exceeds P/2 bins).
-template <typename T, int LOGP>
+template <typename T, int LOGP, typename WT>
 __device__ __forceinline__ void ols_full_body(const cplx<T>* __restrict__ xb, const RowDesc& rd,
                                               const cplx<T>* __restrict__ gt, const cplx<T>* __restrict__ tw_all,
-                                              cplx<T>* __restrict__ wout, int H, int nlim, T* lds) {
+                                              WT* __restrict__ wout, int H, int nlim, T* lds) {
   constexpr int P = 1 << LOGP, NT = P >> 4;
   using F = ct::Fft<T, LOGP, 0, false>;
   F f;
@@ -170,11 +170,11 @@ __device__ __forceinline__ void ols_full_body(const cplx<T>* __restrict__ xb, co
 // t, n_local = TB m + t), inputs Z_r[q] = Y[k(q)] e^{2 pi i k(q) r / P} with the filtered band Y built once in LDS.
 // The host aligns the band start k_lo to a multiple of K/16, so that k(q) = k_lo + ((q - k_lo) mod K) wraps between
 // the same two slots for every thread: slots e >= ew = 16 - ((-k_lo mod K) / NT) carry an extra e^{-2 pi i K r / P}.
-template <typename T, int LOGK, int LOGP>
+template <typename T, int LOGK, int LOGP, typename WT>
 __device__ __forceinline__ void ols_band_body(const cplx<T>* __restrict__ xb, const RowDesc& rd,
                                               const cplx<T>* __restrict__ gt,
                                               const cplx<T>* __restrict__ tw_all, const TwN<T>& twn, int logN,
-                                              cplx<T>* __restrict__ wout, int H, int nlim, T* lds, int logx, unsigned g) {
+                                              WT* __restrict__ wout, int H, int nlim, T* lds, int logx, unsigned g) {
   // logx = log2(P_b / P), g < P_b / P: this workgroup's residues are r = g TB + t of the P_b / K of the block
   constexpr int LOGTB = LOGP - LOGK, K = 1 << LOGK, NT = K >> 4, BD = 1 << (LOGP - 4);
   using F = ct::Fft<T, LOGK, LOGTB, true, (LOGTB <= CWT_OLS_PAD_LOGTB)>;
@@ -269,10 +269,10 @@ __device__ __forceinline__ void ols_band_body(const cplx<T>* __restrict__ xb, co
 // (2.35-2.47 -> 1.94-2.14): these kernels are NOT bound by the issue rate alone]
 __device__ __forceinline__ pairf pair_of(float a, float b) { pairf v = {a, b}; return v; }
 
-template <int LOGP>
+template <int LOGP, typename WT>
 __device__ __forceinline__ void ols_full_body2(const float2* __restrict__ xb0, const float2* __restrict__ xb1, const RowDesc& rd,
                                                const float2* __restrict__ gt, const float2* __restrict__ tw_all,
-                                               float2* __restrict__ w0, float2* __restrict__ w1, int H, int nlim0, int nlim1,
+                                               WT* __restrict__ w0, WT* __restrict__ w1, int H, int nlim0, int nlim1,
                                                pairf* lds) {
   constexpr int P = 1 << LOGP, NT = P >> 4;
   using F = ct::Fft<pairf, LOGP, 0, false>;
@@ -304,10 +304,10 @@ __device__ __forceinline__ void ols_full_body2(const float2* __restrict__ xb0, c
   }
 }
 
-template <int LOGK, int LOGP>
+template <int LOGK, int LOGP, typename WT>
 __device__ __forceinline__ void ols_band_body2(const float2* __restrict__ xb0, const float2* __restrict__ xb1, const RowDesc& rd,
                                                const float2* __restrict__ gt, const float2* __restrict__ tw_all,
-                                               const TwN<float>& twn, int logN, float2* __restrict__ w0, float2* __restrict__ w1,
+                                               const TwN<float>& twn, int logN, WT* __restrict__ w0, WT* __restrict__ w1,
                                                int H, int nlim0, int nlim1, pairf* lds, int logx, unsigned g) {
   constexpr int LOGTB = LOGP - LOGK, K = 1 << LOGK, NT = K >> 4, BD = 1 << (LOGP - 4);
   using F = ct::Fft<pairf, LOGK, LOGTB, true, (LOGTB <= CWT_OLS_PAD_LOGTB)>;
@@ -393,11 +393,11 @@ __device__ __forceinline__ void ols_band_body2(const float2* __restrict__ xb0, c
 // All overlap-save rows of a transform in one launch: 1-D grid, class c owns workgroups [wg_first, next wg_first);
 // inside a class the 8 XCDs (workgroup id & 7) take every 8th block and walk all rows of a block back to back, so that
 // a block spectrum is fetched into one L2 once and read there by every row.
-template <typename T, int LOGP>
+template <typename T, int LOGP, typename WT = cplx<T>>
 __global__ void __launch_bounds__(1 << (LOGP - 4), (sizeof(T) == 8 ? (LOGP == 12 ? CWT_LB_OLS_F64_HALF : CWT_LB_OLS_F64)
                                                                 : (LOGP == 12 ? CWT_LB_OLS_F32_HALF : CWT_LB_OLS_F32)))
 k_ols_ct(const cplx<T>* __restrict__ xs, const RowDesc* __restrict__ rows, const cplx<T>* __restrict__ gtab,
-         const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, OlsClasses cls, cplx<T>* __restrict__ W, long ldw,
+         const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, OlsClasses cls, WT* __restrict__ W, long ldw,
          long ncols, unsigned wg0) {
   // wg0 (a multiple of 8): this launch covers the workgroups wg0 ... of the class list -- the classes on blocks of one tile and the
   // classes on longer blocks go in two launches where their block spectra come from two kernels (serial schedule)
@@ -429,7 +429,7 @@ k_ols_ct(const cplx<T>* __restrict__ xs, const RowDesc* __restrict__ rows, const
   const long col0 = long(blk) * L;
   const long left = ncols - col0;
   const int nlim = left < L ? int(left) : L;
-  cplx<T>* wout = W + long(rd.out_row) * ldw + col0;
+  WT* wout = W + long(rd.out_row) * ldw + col0;
   const cplx<T>* gt = gtab + rd.tab_off;
   if constexpr (PAIR) {
     const bool two = blk + 1u < unsigned(oc.nblocks);
@@ -439,26 +439,26 @@ k_ols_ct(const cplx<T>* __restrict__ xs, const RowDesc* __restrict__ rows, const
     pairf* lds2 = reinterpret_cast<pairf*>(lds_raw);
 #define CWT_OLS_CASE2(LK)                                                                                                    \
   case LK:                                                                                                                    \
-    if constexpr (LK < LOGP) ols_band_body2<LK, LOGP>(xb, xb1, rd, gt, tw_all, twn, logN, wout, wout + L, H, nlim, nlim1, lds2, logx, g); \
-    else ols_full_body2<LOGP>(xb, xb1, rd, gt, tw_all, wout, wout + L, H, nlim, nlim1, lds2);                                  \
+    if constexpr (LK < LOGP) ols_band_body2<LK, LOGP, WT>(xb, xb1, rd, gt, tw_all, twn, logN, wout, wout + L, H, nlim, nlim1, lds2, logx, g); \
+    else ols_full_body2<LOGP, WT>(xb, xb1, rd, gt, tw_all, wout, wout + L, H, nlim, nlim1, lds2);                                  \
     break;
     switch (rd.logK) {
       CWT_OLS_CASE2(4) CWT_OLS_CASE2(5) CWT_OLS_CASE2(6) CWT_OLS_CASE2(7) CWT_OLS_CASE2(8) CWT_OLS_CASE2(9)
       CWT_OLS_CASE2(10) CWT_OLS_CASE2(11) CWT_OLS_CASE2(12) CWT_OLS_CASE2(13)
-      default: ols_full_body2<LOGP>(xb, xb1, rd, gt, tw_all, wout, wout + L, H, nlim, nlim1, lds2); break;
+      default: ols_full_body2<LOGP, WT>(xb, xb1, rd, gt, tw_all, wout, wout + L, H, nlim, nlim1, lds2); break;
     }
 #undef CWT_OLS_CASE2
     return;
   }
 #define CWT_OLS_CASE(LK)                                                                            \
   case LK:                                                                                           \
-    if constexpr (LK < LOGP) ols_band_body<T, LK, LOGP>(xb, rd, gt, tw_all, twn, logN, wout, H, nlim, lds, logx, g); \
-    else ols_full_body<T, LOGP>(xb, rd, gt, tw_all, wout, H, nlim, lds);                            \
+    if constexpr (LK < LOGP) ols_band_body<T, LK, LOGP, WT>(xb, rd, gt, tw_all, twn, logN, wout, H, nlim, lds, logx, g); \
+    else ols_full_body<T, LOGP, WT>(xb, rd, gt, tw_all, wout, H, nlim, lds);                            \
     break;
   switch (rd.logK) {
     CWT_OLS_CASE(4) CWT_OLS_CASE(5) CWT_OLS_CASE(6) CWT_OLS_CASE(7) CWT_OLS_CASE(8) CWT_OLS_CASE(9)
     CWT_OLS_CASE(10) CWT_OLS_CASE(11) CWT_OLS_CASE(12) CWT_OLS_CASE(13)
-    default: ols_full_body<T, LOGP>(xb, rd, gt, tw_all, wout, H, nlim, lds); break;
+    default: ols_full_body<T, LOGP, WT>(xb, rd, gt, tw_all, wout, H, nlim, lds); break;
   }
 #undef CWT_OLS_CASE
 }
@@ -554,10 +554,10 @@ k_aols_fwd(const cplx<T>* __restrict__ xm, int logN, int halo, const cplx<T>* __
 // back, so that a block spectrum is fetched into one L2 once.  y = IFFT_P(X_b * table), columns [H, H + L) are stored.
 // blockIdx.y = signal of a batch: its rows at rows + y g.nrows, its block spectra at xs + y nblocks (P + 8); xhat = the
 // spectra of the batch (the Nyquist bin of a row's signal at xhat[rd.spec_off + N / 2], two-sided filters only).
-template <typename T, int LOGP>
+template <typename T, int LOGP, typename WT = cplx<T>>
 __global__ void __launch_bounds__(1 << (LOGP - 4), (sizeof(T) == 8 ? (LOGP == 12 ? CWT_LB_OLS_F64_HALF : CWT_LB_OLS_F64) : CWT_LB_AOLS_F32))
 k_aols_rows(const cplx<T>* __restrict__ xs, const RowDesc* __restrict__ rows, const T* __restrict__ gtab,
-            const cplx<T>* __restrict__ tw_all, AolsGeom g, const cplx<T>* __restrict__ xhat, long nyq, cplx<T>* __restrict__ W,
+            const cplx<T>* __restrict__ tw_all, AolsGeom g, const cplx<T>* __restrict__ xhat, long nyq, WT* __restrict__ W,
             long ldw, long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
@@ -574,14 +574,14 @@ k_aols_rows(const cplx<T>* __restrict__ xs, const RowDesc* __restrict__ rows, co
   const T* gt = gtab + rd.tab_off;
   const long col0 = long(blk) * L, left = ncols - col0;
   const int nlim = left < L ? int(left) : L;
-  cplx<T>* wout = W + long(rd.out_row) * ldw + col0;
+  WT* wout = W + long(rd.out_row) * ldw + col0;
   if constexpr (PAIR) {
     using F2 = ct::Fft<pairf, LOGP, 0, false>;
     const bool two = blk + 1u < unsigned(g.nblocks);
     const float2* xb1 = two ? xb + (P + 8) : xb;
     const long left1 = left - L;
     const int nlim1 = !two ? 0 : left1 < L ? int(left1) : L;
-    float2* wout1 = wout + L;
+    WT* wout1 = wout + L;
     F2 f;
     f.t = 0;
     f.j = threadIdx.x;
@@ -830,9 +830,9 @@ k_poly_coef(const cplx<T>* __restrict__ yb, const RowDesc* __restrict__ rows, co
 
 // Stage 2.  One workgroup = 256 lanes x POLY_PASSES passes; a lane stores 16 bytes per pass (one complex128 or two adjacent
 // complex64 outputs).  sc[i][d] = a_d[m0 + i] for the intervals m0 ... the workgroup touches.
-template <typename T, int D>
+template <typename T, int D, typename WT>
 __device__ __forceinline__ void poly_rows_body(const RowDesc& rd, const cplx<T>* __restrict__ coef, const TwN<T>& twn,
-                                               int logN, cplx<T>* __restrict__ W, long ldw, long ncols, cplx<T>* sc) {
+                                               int logN, WT* __restrict__ W, long ldw, long ncols, cplx<T>* sc) {
   constexpr int PT = sizeof(T) == 8 ? 1 : 2, SPAN = 256 * PT, I = POLY_PASSES, WSPAN = 64 * PT;
   static_assert((I & (I - 1)) == 0, "POLY_PASSES: a power of two (a wavefront's span must divide the interval length)");
   const int logR = logN - rd.logK;
@@ -857,7 +857,7 @@ __device__ __forceinline__ void poly_rows_body(const RowDesc& rd, const cplx<T>*
   cplx<T> adj = mk<T>(T(1), T(0));
   if constexpr (PT == 2) adj = twn(unsigned(kc) & nmask);                // e^{2 pi i k_c / N}: the lane's second output
   const T scale = T(2) / T(1u << logR);
-  cplx<T>* wrow = W + long(rd.out_row) * ldw;
+  WT* wrow = W + long(rd.out_row) * ldw;
   __syncthreads();
   T pr[I][PT], pi[I][PT], u[I][PT];
 #pragma unroll
@@ -896,6 +896,27 @@ __device__ __forceinline__ void poly_rows_body(const RowDesc& rd, const cplx<T>*
         for (int i = 0; i < PT; ++i) { pr[p][i] = fma(pr[p][i], u[p][i], cd.x); pi[p][i] = fma(pi[p][i], u[p][i], cd.y); }
       }
     }
+  }
+  if constexpr (power_out<T, WT>()) {
+    // power: |e^{i phi} v|^2 = |v|^2, the carrier is not applied; a lane's PT adjacent columns in one store
+#pragma unroll
+    for (int p = 0; p < I; ++p) {
+      const unsigned n = nl + unsigned(p * WSPAN);
+      T q[PT];
+#pragma unroll
+      for (int i = 0; i < PT; ++i) q[i] = pr[p][i] * pr[p][i] + pi[p][i] * pi[p][i];
+      if constexpr (PT == 1) {
+        if (long(n) < ncols) __builtin_nontemporal_store(q[0], wrow + n);
+      } else {
+        if (long(n) + 1 < ncols && ((reinterpret_cast<size_t>(wrow + n) & (2 * sizeof(T) - 1)) == 0)) {
+          store_p2<T>(wrow + n, q[0], q[PT - 1]);
+        } else {
+          if (long(n) < ncols) __builtin_nontemporal_store(q[0], wrow + n);
+          if (long(n) + 1 < ncols) __builtin_nontemporal_store(q[PT - 1], wrow + n + 1);
+        }
+      }
+    }
+    return;
   }
 #pragma unroll
   for (int p = 0; p < I; ++p) {
@@ -944,9 +965,9 @@ __device__ __forceinline__ unsigned wave_uniform(unsigned v) {
 // As poly_rows_body, but a wavefront reads the coefficient set(s) of its own interval(s) itself: the addresses are uniform over the
 // wavefront (R >= 64 outputs of one pass lie in one interval), so the loads are scalar loads and the Horner FMAs take the coefficient from
 // scalar registers -- no staging in LDS, no workgroup barrier, no LDS reads.
-template <typename T, int D>
+template <typename T, int D, typename WT>
 __device__ __forceinline__ void poly_rows_body_s(const RowDesc& rd, const cplx<T>* __restrict__ coef, const TwN<T>& twn,
-                                                 int logN, cplx<T>* __restrict__ W, long ldw, long ncols) {
+                                                 int logN, WT* __restrict__ W, long ldw, long ncols) {
   constexpr int PT = sizeof(T) == 8 ? 1 : 2, SPAN = 256 * PT, I = POLY_PASSES, WSPAN = 64 * PT;
   const int logR = logN - rd.logK;
   const unsigned nmask = unsigned((1 << logN) - 1);
@@ -959,7 +980,7 @@ __device__ __forceinline__ void poly_rows_body_s(const RowDesc& rd, const cplx<T
   cplx<T> adj = mk<T>(T(1), T(0));
   if constexpr (PT == 2) adj = twn(unsigned(kc) & nmask);
   const T scale = T(2) / T(1u << logR);
-  cplx<T>* wrow = W + long(rd.out_row) * ldw;
+  WT* wrow = W + long(rd.out_row) * ldw;
   const cplx<T>* a = coef + rd.tab_off;
   T pr[I][PT], pi[I][PT], u[I][PT];
 #pragma unroll
@@ -999,6 +1020,27 @@ __device__ __forceinline__ void poly_rows_body_s(const RowDesc& rd, const cplx<T
       }
     }
   }
+  if constexpr (power_out<T, WT>()) {
+    // power: |e^{i phi} v|^2 = |v|^2, the carrier is not applied; a lane's PT adjacent columns in one store
+#pragma unroll
+    for (int p = 0; p < I; ++p) {
+      const unsigned n = nl + unsigned(p * WSPAN);
+      T q[PT];
+#pragma unroll
+      for (int i = 0; i < PT; ++i) q[i] = pr[p][i] * pr[p][i] + pi[p][i] * pi[p][i];
+      if constexpr (PT == 1) {
+        if (long(n) < ncols) __builtin_nontemporal_store(q[0], wrow + n);
+      } else {
+        if (long(n) + 1 < ncols && ((reinterpret_cast<size_t>(wrow + n) & (2 * sizeof(T) - 1)) == 0)) {
+          store_p2<T>(wrow + n, q[0], q[PT - 1]);
+        } else {
+          if (long(n) < ncols) __builtin_nontemporal_store(q[0], wrow + n);
+          if (long(n) + 1 < ncols) __builtin_nontemporal_store(q[PT - 1], wrow + n + 1);
+        }
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int p = 0; p < I; ++p) {
     const unsigned n = nl + unsigned(p * WSPAN);
@@ -1024,10 +1066,10 @@ __device__ __forceinline__ void poly_rows_body_s(const RowDesc& rd, const cplx<T
   }
 }
 
-template <typename T>
+template <typename T, typename WT = cplx<T>>
 __global__ void __launch_bounds__(256)
 k_poly_rows(const RowDesc* __restrict__ rows, const cplx<T>* __restrict__ coef, TwN<T> twn, int logN,
-            cplx<T>* __restrict__ W, long ldw, long ncols) {
+            WT* __restrict__ W, long ldw, long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   cplx<T>* sc = reinterpret_cast<cplx<T>*>(lds_raw);
   const RowDesc rd = rows[blockIdx.y];
@@ -1035,8 +1077,8 @@ k_poly_rows(const RowDesc* __restrict__ rows, const cplx<T>* __restrict__ coef, 
   static_assert(sizeof(T) == 8 || SMAX == 0, "poly_rows_body_s: one interval per pass of a wavefront (R >= 128 in complex64 is not guaranteed)");
 #define CWT_POLYR_CASE(DD)                                                                      \
   case DD:                                                                                      \
-    if constexpr (DD <= SMAX) poly_rows_body_s<T, DD>(rd, coef, twn, logN, W, ldw, ncols);      \
-    else poly_rows_body<T, DD>(rd, coef, twn, logN, W, ldw, ncols, sc);                         \
+    if constexpr (DD <= SMAX) poly_rows_body_s<T, DD, WT>(rd, coef, twn, logN, W, ldw, ncols);      \
+    else poly_rows_body<T, DD, WT>(rd, coef, twn, logN, W, ldw, ncols, sc);                         \
     break;
   switch (rd.nterms) {
     CWT_POLYR_CASE(2) CWT_POLYR_CASE(4) CWT_POLYR_CASE(6) CWT_POLYR_CASE(8) CWT_POLYR_CASE(10) CWT_POLYR_CASE(12)

@@ -59,6 +59,23 @@ __device__ __forceinline__ void store_w(cplx<T>* p, T re, T im) {
   vec2 v = {re, im};
   __builtin_nontemporal_store(v, reinterpret_cast<vec2*>(p));
 }
+// The power output (cwt_transform_power): P = re^2 + im^2, one real of the plan's precision per element, through the same
+// streaming store.  A row kernel is compiled once per output: its W pointer is WT* with WT = cplx<T> (the transform W) or
+// WT = T (its power), and overload resolution picks the store -- no runtime branch in either instantiation.
+template <typename T>
+__device__ __forceinline__ void store_w(T* p, T re, T im) {
+  __builtin_nontemporal_store(re * re + im * im, p);
+}
+// Two adjacent power columns in one 2 x sizeof(T)-byte streaming store (complex64 polynomial rows: a lane owns two columns).
+template <typename T>
+__device__ __forceinline__ void store_p2(T* p, T a, T b) {
+  typedef T vec2 __attribute__((vector_size(2 * sizeof(T))));
+  vec2 v = {a, b};
+  __builtin_nontemporal_store(v, reinterpret_cast<vec2*>(p));
+}
+// True where a row kernel writes power (WT = T) instead of the transform (WT = cplx<T>)
+template <typename T, typename WT>
+constexpr bool power_out() { return sizeof(WT) == sizeof(T); }
 
 // Pins a value to a register at this point of the program (an empty asm that "modifies" it): the compiler must
 // finish computing it here and may not sink the computation past later barriers.  Used where a result is produced

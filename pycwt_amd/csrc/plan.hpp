@@ -83,6 +83,7 @@ struct cwt_plan {
   struct Call {
     int fft_small = 0;                     // the serial schedule's forward FFT, queued on side stream 0, takes half-size tiles
     int64_t ols_x_ld = 0;                  // cwt_transform_batch: elements between the signals of the batch
+    int power = 0;                         // the *_power entry points: the row kernels write |W|^2 as reals, not W
   };
   Call call;
   // options

@@ -112,7 +112,7 @@ def _reduction_plan(precision: int, device: int, rows: int) -> _hip.Plan:
     return _plan(16, precision, device, rows)
 
 
-def _transform(plan, x_host, xd_ptr, n0, kind, param, dt, sj, xh_ptr, W_ptr, auto=True):
+def _transform(plan, x_host, xd_ptr, n0, kind, param, dt, sj, xh_ptr, W_ptr, auto=True, power=False):
     """Signal (already uploaded at xd_ptr) -> spectrum and rows of W on the device.
 
     `cwt_transform` computes time-compact rows block by block from the signal itself (overlap-save), so a NaN or inf
@@ -127,26 +127,29 @@ def _transform(plan, x_host, xd_ptr, n0, kind, param, dt, sj, xh_ptr, W_ptr, aut
         if target:      # automatic accuracy: the tolerance of this call from the dynamic range of its spectrum
             plan.forward_fft(xd_ptr, n0, xh_ptr)
             plan.set_tolerance(plan.auto_tolerance(xh_ptr, target))
-        plan.transform(xd_ptr, n0, kind, param, dt, sj, xh_ptr, W_ptr, n0, n0)
+        (plan.transform_power if power else plan.transform)(xd_ptr, n0, kind, param, dt, sj, xh_ptr, W_ptr, n0, n0)
     else:
         plan.forward_fft(xd_ptr, n0, xh_ptr)
-        plan.transform_rows(xh_ptr, kind, param, dt, sj, W_ptr, n0, n0)
+        (plan.transform_rows_power if power else plan.transform_rows)(xh_ptr, kind, param, dt, sj, W_ptr, n0, n0)
 
 
-def _cwt_builtin(x, dt, sj, kind, param, N, precision, device, finite):
-    """W (rows x n0) and the spectrum (N) for a built-in mother through the device-resident entry points."""
+def _cwt_builtin(x, dt, sj, kind, param, N, precision, device, finite, power=False):
+    """W (rows x n0) and the spectrum (N) for a built-in mother through the device-resident entry points; power=True:
+    |W|^2 (rows x n0 reals) from the power entry points instead of W."""
     plan = _plan(N, precision, device, sj.size)
     if finite:
-        return plan.execute_host(x, kind, param, dt, sj)
+        return plan.execute_host_power(x, kind, param, dt, sj) if power else plan.execute_host(x, kind, param, dt, sj)
     es = np.dtype(plan.real).itemsize
     n0 = x.size
+    ow = 1 if power else 2
     sc = _Scratch(device)
     try:
-        xd, xh, Wd = sc.new(n0 * es), sc.new(N * 2 * es), sc.new(sj.size * n0 * 2 * es)
+        xd, xh, Wd = sc.new(n0 * es), sc.new(N * 2 * es), sc.new(sj.size * n0 * ow * es)
         with plan.lock:
             xd.upload(plan, np.ascontiguousarray(x, dtype=plan.real))
-            _transform(plan, x, xd.ptr, n0, kind, param, dt, sj, xh.ptr, Wd.ptr)
-            return Wd.download(plan, (sj.size, n0), plan.cplx), xh.download(plan, (N,), plan.cplx)
+            _transform(plan, x, xd.ptr, n0, kind, param, dt, sj, xh.ptr, Wd.ptr, power=power)
+            return (Wd.download(plan, (sj.size, n0), plan.real if power else plan.cplx),
+                    xh.download(plan, (N,), plan.cplx))
     finally:
         sc.free()
 
@@ -236,11 +239,11 @@ def _geometry(mother, n0, dt, dj, s0, J, freqs, pad):
     return geo
 
 
-def _cwt_with_host_filter_bank(x, dt, sj, mother, N, precision, device):
+def _cwt_with_host_filter_bank(x, dt, sj, mother, N, precision, device, power=False):
     """Any duck-typed mother (only `psi_ft`, `flambda`, `coi` needed, as in the reference): the filter
     bank of wavelet.py:102-104 is evaluated with NumPy exactly as the reference does and handed to the
     engine as an explicit table; FFTs, multiply and the band-limited / two-pass machinery stay on the
-    GPU.  Returns (W, xhat, keep-mask or None)."""
+    GPU.  Returns (W, xhat, keep-mask or None); power=True: |W|^2 in place of W (W in scratch, squared on the device)."""
     ftfreqs = 2 * np.pi * np.fft.fftfreq(N, dt)
     with np.errstate(all="ignore"):
         bank = (sj[:, None] * ftfreqs[1] * N) ** .5 * np.conjugate(mother.psi_ft(sj[:, None] * ftfreqs))
@@ -268,14 +271,19 @@ def _cwt_with_host_filter_bank(x, dt, sj, mother, N, precision, device):
             tab.upload(plan, np.ascontiguousarray(bank, dtype=plan.cplx))
             plan.forward_fft(xd.ptr, x.size, xh.ptr)
             plan.transform_rows_table(xh.ptr, tab.ptr, k_lo, nband, Wd.ptr, x.size, x.size)
+            if power:
+                Pd = sc.new(rows * x.size * es)
+                plan.abs2(Wd.ptr, x.size, x.size, rows, Pd.ptr, x.size)
+                return Pd.download(plan, (rows, x.size), plan.real), xh.download(plan, (N,), plan.cplx), keep
             return Wd.download(plan, (rows, x.size), plan.cplx), xh.download(plan, (N,), plan.cplx), keep
     finally:
         sc.free()
 
 
-def _cwt_unpadded(x, dt, sj, kind, param, precision, device):
+def _cwt_unpadded(x, dt, sj, kind, param, precision, device, power=False):
     """W (rows x n0) and the spectrum (n0) at transform length n0 = len(x), not a power of two: Bluestein's chirp-z
-    identity on the power-of-two engine (cwt_forward_fft_n / cwt_transform_rows_n)."""
+    identity on the power-of-two engine (cwt_forward_fft_n / cwt_transform_rows_n).  power=True: |W|^2, W squared on the
+    device (cwt_abs2)."""
     n0 = x.size
     M = _next_pow2(2 * n0 - 1)
     plan = _plan(M, precision, device, min(sj.size, 1024))
@@ -287,6 +295,10 @@ def _cwt_unpadded(x, dt, sj, kind, param, precision, device):
             xd.upload(plan, x)
             plan.forward_fft_n(xd.ptr, n0, xh.ptr)
             plan.transform_rows_n(xh.ptr, n0, kind, param, dt, sj, Wd.ptr, n0)
+            if power:
+                Pd = sc.new(sj.size * n0 * es)
+                plan.abs2(Wd.ptr, n0, n0, sj.size, Pd.ptr, n0)
+                return Pd.download(plan, (sj.size, n0), plan.real), xh.download(plan, (n0,), plan.cplx)
             return Wd.download(plan, (sj.size, n0), plan.cplx), xh.download(plan, (n0,), plan.cplx)
     finally:
         sc.free()
@@ -368,10 +380,8 @@ def cwt(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, pre
     return (W, np.array(sj), freqs, np.array(coi), fft5, np.array(fftfreqs))
 
 
-class DeviceTransform:
-    """A wavelet transform that stays on the GPU (SURVEY.md 8f-3): W (rows x n0 complex) is device
-    resident; the reductions every caller of `cwt` does next -- power, global spectrum, scale
-    averages, reconstruction -- run there and only vectors cross PCIe.  `W()` downloads the matrix."""
+class _DeviceResult:
+    """A device-resident result of one transform (a matrix in `_buf`) with the grids of `cwt` and its spectrum."""
 
     def __init__(self, plan, buf, sj, freqs, coi, fft, fftfreqs, mother, dt, n0, spectrum=None):
         self._plan, self._buf = plan, buf
@@ -413,6 +423,12 @@ class DeviceTransform:
                 return out.download(self._plan, (n,), self._plan.real).astype(np.float64)
         finally:
             out.free()
+
+
+class DeviceTransform(_DeviceResult):
+    """A wavelet transform that stays on the GPU (SURVEY.md 8f-3): W (rows x n0 complex) is device
+    resident; the reductions every caller of `cwt` does next -- power, global spectrum, scale
+    averages, reconstruction -- run there and only vectors cross PCIe.  `W()` downloads the matrix."""
 
     def W(self):
         return self._buf.download(self._plan, self.shape, self._plan.cplx).astype(np.complex128, copy=False)
@@ -523,6 +539,161 @@ def cwt_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None,
     coi = _coi(mother, n0, dt)
     ftfreqs = 2 * np.pi * np.fft.fftfreq(N, dt)
     return (W, sj, freqs, coi, xhat[:, 1:N // 2] / N ** 0.5, ftfreqs[1:N // 2] / (2 * np.pi))
+
+
+def cwt_power(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0, pad=True):
+    """``cwt`` that returns the wavelet power ``|W|^2`` in place of ``W``: ``(power, sj, freqs, coi, fft, fftfreqs)``.
+
+    ``power`` is float64 of shape (rows, n0) and equals ``np.abs(cwt(...)[0]) ** 2`` to rounding; the other five values are
+    ``cwt``'s.  For the built-in mothers the row kernels write the power themselves (half the bytes of ``W`` written and
+    downloaded); a duck-typed mother and ``pad=False`` with a length that is not a power of two compute ``W`` on the device and
+    square it there.  A complex signal is transformed through ``cwt`` (its ``W`` is the sum of the transforms of both parts,
+    whose power is not the sum of their powers) and squared.  Same rules as ``cwt`` otherwise: Paul's NaN rows, non-finite
+    samples (all NaN), float32 input, precision, automatic tolerance.
+    """
+    mother = _check_parameter_wavelet(wavelet)
+    precision = _default_precision() if precision is None else int(precision)
+    if np.iscomplexobj(signal):
+        W, sj, freqs, coi, fft5, fftfreqs = cwt(signal, dt, dj, s0, J, mother, freqs, precision=precision, device=device,
+                                                pad=pad)
+        return (W.real ** 2 + W.imag ** 2, sj, freqs, coi, fft5, fftfreqs)
+    in_dtype = getattr(signal, "dtype", None)
+    n0 = len(signal)
+    user_freqs = freqs is not None
+    N, sj, freqs, coi, fftfreqs, bad = _geometry(mother, n0, dt, dj, s0, J, freqs, pad)
+    real = np.float64 if precision == 64 else np.float32
+    if N & (N - 1):                                         # pad=False with a length that is not a power of two
+        if bad is not None and not bad.all():
+            sj, freqs = sj[~bad], np.asarray(freqs)[~bad]
+        kind, param = _device_id(mother)
+        P, xhat = _cwt_unpadded(np.ascontiguousarray(signal, dtype=real), dt, sj, kind, param, precision, device, power=True)
+    elif hasattr(mother, "device_id"):
+        x = np.asarray(signal, dtype=real)
+        finite = bool(np.isfinite(x).all())
+        if bad is not None and not bad.all() and finite:   # (see cwt)
+            keep = ~bad
+            sj = sj[keep]
+            freqs = np.asarray(freqs)[keep]
+        kind, param = mother.device_id()
+        P, xhat = _cwt_builtin(x, dt, sj, kind, param, N, precision, device, finite, power=True)
+        if bad is not None and bad.all():
+            P = np.full(P.shape, np.nan, dtype=P.dtype)
+    else:
+        P, xhat, keep = _cwt_with_host_filter_bank(np.asarray(signal, dtype=real), dt, sj, mother, N, precision, device,
+                                                   power=True)
+        if keep is not None:
+            sj = sj[keep]
+            freqs = np.asarray(freqs)[keep]
+    P = P.astype(np.float64)
+    xhat = xhat.astype(np.complex128, copy=False)
+    fft5 = xhat[1:N // 2] / N ** 0.5
+    if in_dtype == np.float32:
+        fft5 = fft5.astype(np.complex64)
+    if not user_freqs:
+        freqs = np.array(freqs)
+    return (P, np.array(sj), freqs, np.array(coi), fft5, np.array(fftfreqs))
+
+
+class DevicePower(_DeviceResult):
+    """The wavelet power |W|^2 (rows x n0 reals of the plan's precision) kept on the GPU, as `cwt_power` computes it: the
+    power-only counterpart of `DeviceTransform`.  `power()` downloads the matrix; `global_power()` and `scale_average()` reduce
+    it on the device.  There is no W here, hence no `W()` and no `icwt()`."""
+
+    def power(self):
+        return self._buf.download(self._plan, self.shape, self._plan.real).astype(np.float64, copy=False)
+
+    def global_power(self):
+        """mean over time of the power per scale (`power.mean(axis=1)`, sample/simple_sample.py:79)."""
+        rows, n0 = self.shape
+        return self._vector(rows, lambda p: self._plan.time_mean_real(self._buf.ptr, n0, n0, rows, p))
+
+    def scale_average(self, s1, s2, dj):
+        """Scale-averaged power over s1 <= s < s2: dj*dt/cdelta * sum_j P_j/s_j (TC98 eq. 24, sample/simple_sample.py:85-91)."""
+        rows, n0 = self.shape
+        w = np.where((self.sj >= s1) & (self.sj < s2), 1.0 / self.sj, 0.0)
+        coeff = dj * self.dt / self.mother.cdelta
+        return self._vector(n0, lambda p: self._plan.reduce_scales(self._buf.ptr, n0, n0, w, 2, coeff, p))
+
+
+def cwt_power_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0):
+    """`cwt_device` with the power output: returns a `DevicePower` (attributes sj, freqs, coi, fft, fftfreqs as in
+    `cwt_device`; methods power(), global_power(), scale_average(), close(); device_ptr)."""
+    mother = _check_parameter_wavelet(wavelet)
+    precision = _default_precision() if precision is None else int(precision)
+    n0 = len(signal)
+    kind, param = _device_id(mother)
+    N, sj, freqs, coi, fftfreqs, bad = _geometry(mother, n0, dt, dj, s0, J, freqs, True)
+    if bad is not None and not bad.all() and np.isfinite(np.asarray(signal, dtype=np.float64)).all():   # see cwt()
+        sj, freqs = sj[~bad], np.asarray(freqs)[~bad]
+    plan = _plan(N, precision, device, sj.size)
+    es = np.dtype(plan.real).itemsize
+    xd, xh = _hip.DeviceBuffer(n0 * es, device), _hip.DeviceBuffer(N * 2 * es, device)
+    Pd = _hip.DeviceBuffer(sj.size * n0 * es, device)
+    try:
+        with plan.lock:
+            xs_host = np.ascontiguousarray(signal, dtype=plan.real)
+            xd.upload(plan, xs_host)
+            _transform(plan, xs_host, xd.ptr, n0, kind, param, dt, sj, xh.ptr, Pd.ptr, power=True)
+            plan.sync()
+    except Exception:
+        Pd.free()
+        xh.free()
+        raise
+    finally:
+        xd.free()
+
+    def ro(a):
+        v = np.asarray(a).view()
+        v.flags.writeable = False
+        return v
+    return DevicePower(plan, Pd, ro(sj), ro(freqs), ro(coi), None, ro(fftfreqs), mother, dt, n0, spectrum=xh)
+
+
+def cwt_power_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None,
+                    device=0, max_batch_bytes=8 << 30):
+    """`cwt_batch` with the power output: `(power, sj, freqs, coi, fft, fftfreqs)` with `power` float64 of shape
+    (batch, rows, n0).  Slabs of at most `max_batch_bytes` of power; a slab with a non-finite sample goes through the
+    spectra (every coefficient of that signal NaN, as in `cwt_batch`)."""
+    mother = _check_parameter_wavelet(wavelet)
+    precision = _default_precision() if precision is None else int(precision)
+    X = np.atleast_2d(np.asarray(signals))
+    nb, n0 = X.shape
+    sj, freqs = _scale_grid(mother, n0, dt, dj, s0, J, freqs)
+    N = _next_pow2(n0)
+    bad = _nan_rows(mother, sj, N, dt)
+    if bad.any() and not bad.all():
+        sj, freqs = sj[~bad], np.asarray(freqs)[~bad]
+    kind, param = _device_id(mother)
+    rows = sj.size
+    es = 8 if precision == 64 else 4
+    slab = int(max(1, min(nb, max_batch_bytes // (rows * n0 * es))))
+    plan = _plan(N, precision, device, slab * rows)
+    P = np.empty((nb, rows, n0), dtype=np.float64)
+    xhat = np.empty((nb, N), dtype=np.complex128)
+    sc = _Scratch(device)
+    try:
+        xd, xh = sc.new(slab * n0 * es), sc.new(slab * N * 2 * es)
+        Pd = sc.new(slab * rows * n0 * es)
+        for b0 in range(0, nb, slab):
+            cnt = min(slab, nb - b0)
+            with plan.lock:
+                xs = np.ascontiguousarray(X[b0:b0 + cnt], dtype=plan.real)
+                xd.upload(plan, xs)
+                if np.isfinite(xs).all():
+                    plan.transform_batch_power(xd.ptr, cnt, n0, n0, kind, param, dt, sj, xh.ptr, Pd.ptr, n0, n0)
+                else:
+                    # (see cwt_batch) the rows of each signal from its spectrum alone
+                    plan.fft_rows(xd.ptr, False, cnt, n0, n0, xh.ptr)
+                    for b in range(cnt):
+                        plan.transform_rows_power(xh.ptr + b * N * 2 * es, kind, param, dt, sj, Pd.ptr + b * rows * n0 * es,
+                                                  n0, n0)
+                P[b0:b0 + cnt] = Pd.download(plan, (cnt, rows, n0), plan.real)
+                xhat[b0:b0 + cnt] = xh.download(plan, (cnt, N), plan.cplx)
+    finally:
+        sc.free()
+    coi = _coi(mother, n0, dt)
+    ftfreqs = 2 * np.pi * np.fft.fftfreq(N, dt)
+    return (P, sj, freqs, coi, xhat[:, 1:N // 2] / N ** 0.5, ftfreqs[1:N // 2] / (2 * np.pi))
 
 
 def icwt(W, sj, dt, dj=1 / 12, wavelet="morlet", *, precision=None, device=0):
