@@ -13,7 +13,7 @@ OUT = os.path.join(HERE, "_build", "libcwt_emu.so")
 OUT_ASAN = os.path.join(HERE, "_build", "libcwt_emu_asan.so")
 CSRC = os.path.join(ROOT, "pycwt_amd", "csrc")
 UNITS = ["plan_host.cpp", "launch_f64.hip", "launch_f32.hip", "abi.hip"]       # the product's translation units, unmodified
-SRCS = [os.path.join(CSRC, u) for u in UNITS] + [os.path.join(HERE, "hipemu.cpp")]
+SRCS = [os.path.join(CSRC, u) for u in UNITS] + [os.path.join(HERE, "hipemu.cpp"), os.path.join(HERE, "selftest_kernels.cpp")]
 DEPS = SRCS + [os.path.join(CSRC, f) for f in ("plan.hpp", "cwt_types.hpp", "launch_impl.hpp", "fft_engine.hpp", "cwt_kernels.hpp",
                                                "cwt_kernels_rows.hpp", "cwt_kernels_callers.hpp")] + [
     os.path.join(ROOT, "include", "cwt_hip.h"), os.path.join(HERE, "hip", "hip_runtime.h")]

@@ -2,12 +2,19 @@
 //
 // tests/emu/build_emu.py compiles pycwt_amd/csrc/*.hip with g++ and
 // `-I tests/emu`, so that this header is picked up instead of the ROCm one.
-// Every workgroup is run as a set of ucontext fibers that yield at
-// __syncthreads(); workgroups are spread over OS threads.  This lets the
-// `-m "not gpu"` tests execute the *unmodified* kernel sources (index
-// algebra, LDS staging, launch geometry, host orchestration) on a box without
-// a GPU.  It is never built into, loaded by, or reachable from the product
-// library (pycwt_amd/libcwt_hip.so); the product has no CPU path.
+// Every workgroup is run as a set of ucontext fibers that park at
+// __syncthreads() (workgroup barrier) and at __builtin_amdgcn_wave_barrier()
+// (barrier of one wavefront: 64 consecutive linear thread ids); workgroups are
+// spread over OS threads.  The order in which the parked fibers go on is a
+// SCHEDULE (hipemu.cpp): `lockstep` runs every fiber of the workgroup in thread
+// order between any two barriers; `waves` runs one wavefront at a time through
+// a whole workgroup-barrier interval, in forward, reverse or seeded order, so
+// that LDS traffic between waves that leans on a wave barrier, or between
+// lanes on no barrier at all, reads stale data.  This lets the `-m "not gpu"`
+// tests execute the *unmodified* kernel sources (index algebra, LDS staging
+// and its synchronisation, launch geometry, host orchestration) on a box
+// without a GPU.  It is never built into, loaded by, or reachable from the
+// product library (pycwt_amd/libcwt_hip.so); the product has no CPU path.
 #pragma once
 #define CWT_HIP_EMULATED 1     // lets the product sources skip what only makes sense on a device (hardware-queue probe)
 #include <ucontext.h>
@@ -45,20 +52,33 @@ struct Ctx {
   ucontext_t* self;
   ucontext_t* sched;
   bool done;
+  unsigned char park;        // where the fiber waits: Park below
 };
+enum Park : unsigned char { kReady = 0, kAtBlock = 1, kAtWave = 2 };
 extern thread_local Ctx* cur;
-inline void barrier() { swapcontext(cur->self, cur->sched); }
-void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& body);
+inline void barrier() { cur->park = kAtBlock; swapcontext(cur->self, cur->sched); }
+inline void wave_barrier() { cur->park = kAtWave; swapcontext(cur->self, cur->sched); }
+void launch(const char* name, dim3 grid, dim3 block, size_t shmem, const std::function<void()>& body);
 }  // namespace hipemu
+
+// Schedule of the fibers of a workgroup (process-global, read once per launch; initialised from CWT_EMU_SCHEDULE =
+// lockstep | waves | waves-reverse | waves-seeded:<n>) and the log of kernel names launched since the last clear.
+enum { HIPEMU_LOCKSTEP = 0, HIPEMU_WAVES = 1, HIPEMU_WAVES_REVERSE = 2, HIPEMU_WAVES_SEEDED = 3 };
+extern "C" {
+int hipemu_set_schedule(int kind, unsigned seed);          // 0, or -1 for an unknown kind (nothing changes)
+void hipemu_get_schedule(int* kind, unsigned* seed);
+void hipemu_clear_launched();
+size_t hipemu_launched(char* buf, size_t size);            // names joined by '\n'; returns the bytes needed (with the final 0)
+}
 
 #define threadIdx (hipemu::cur->tid)
 #define blockIdx (hipemu::cur->bid)
 #define blockDim (hipemu::cur->bdim)
 #define gridDim (hipemu::cur->gdim)
 #define __syncthreads() hipemu::barrier()
-// wavefront-level sync: every fiber of the block runs the same barrier sequence, so the block-wide
-// round-robin yield is a (stronger) stand-in
-#define __builtin_amdgcn_wave_barrier() hipemu::barrier()
+// wavefront-level sync: parks the fiber until every live fiber of ITS wave is parked (under `lockstep`, until every fiber
+// of the workgroup has had its turn, which hides a dependence between waves: the other schedules are there to show it)
+#define __builtin_amdgcn_wave_barrier() hipemu::wave_barrier()
 #define __builtin_amdgcn_fence(order, scope) ((void)0)
 #define __builtin_amdgcn_s_waitcnt(imm) ((void)0)
 #define __builtin_amdgcn_s_getreg(imm) (0u)
@@ -73,7 +93,7 @@ static inline void sincospi(double x, double* s, double* c) {
 #define __expf(x) expf(x)
 #define HIP_DYNAMIC_SHARED(type, var) type* var = reinterpret_cast<type*>(hipemu::cur->smem);
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-  hipemu::launch((grid), (block), (shmem), [=]() { kernel(__VA_ARGS__); })
+  hipemu::launch(#kernel, (grid), (block), (shmem), [=]() { kernel(__VA_ARGS__); })
 
 static inline unsigned atomicAdd(unsigned* p, unsigned v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) {
