@@ -355,7 +355,13 @@ int cwt_filter_rows(cwt_plan* plan, const void* spec_dev, int64_t spec_ld, int m
                     const double* a_host, const double* amp_re_host, const double* amp_im_host,
                     int nrows, void* W_dev, int64_t ldw, int64_t ncols);
 
-/* Boxcar along the scale axis, = scipy.signal.convolve2d(T, win[:, None], 'same') with zero
+/* Row counts of the element-wise building blocks below: cwt_abs2, cwt_boxcar_scales, cwt_wct_products, cwt_wct_coherence and
+ * cwt_coherence_histogram take ANY nrows >= 1 (a launch covers at most 32768 rows; more go out as several launches, in order, on
+ * the plan's stream); cwt_wct_products also needs nrows <= max_rows of the plan (one weight per row is staged) and
+ * cwt_boxcar_scales nwin <= max_rows; cwt_cross_spectrum refuses nrows > 65535 with CWT_EINVAL.  Every matrix has ld >= ncols;
+ * columns ncols .. ld - 1 are neither read nor written.
+ *
+ * Boxcar along the scale axis, = scipy.signal.convolve2d(T, win[:, None], 'same') with zero
  * boundary (mothers.py:100-102).  in/out: nrows x ld complex, distinct buffers.                    */
 int cwt_boxcar_scales(cwt_plan* plan, const void* in_dev, int nrows, int64_t ld, int64_t ncols,
                       const double* win_host, int nwin, void* out_dev);

@@ -895,8 +895,8 @@ int cwt_abs2(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols, int nro
   return by_precision(p, [&](auto t) {
     using T = decltype(t);
     return timed_launch(p, KC_ELEMENTWISE, [&] {
-      for (int r0 = 0; r0 < nrows; r0 += 32768)
-        hipLaunchKernelGGL((k_abs2<T>), dim3(unsigned((ncols + 255) / 256), unsigned(std::min(32768, nrows - r0))), dim3(256), 0,
+      for (int r0 = 0; r0 < nrows; r0 += kMaxGridY)
+        hipLaunchKernelGGL((k_abs2<T>), dim3(unsigned((ncols + 255) / 256), unsigned(std::min(kMaxGridY, nrows - r0))), dim3(256), 0,
                            p->stream, static_cast<const cplx<T>*>(W_dev) + size_t(r0) * size_t(ldw), long(ldw), long(ncols),
                            static_cast<T*>(P_dev) + size_t(r0) * size_t(ldp), long(ldp));
     });
@@ -915,9 +915,11 @@ int cwt_coherence_histogram(cwt_plan* p, const void* r2_dev, int64_t ld, int nro
   return by_precision(p, [&](auto t) {
     using T = decltype(t);
     return timed_launch(p, KC_ELEMENTWISE, [&] {
-      hipLaunchKernelGGL((k_coherence_hist<T>), dim3(gx, nrows), dim3(256), lds, p->stream,
-                         static_cast<const T*>(r2_dev), long(ld), reinterpret_cast<const long*>(lo_dev),
-                         reinterpret_cast<const long*>(hi_dev), nbins, reinterpret_cast<unsigned long long*>(hist_dev));
+      for (int r0 = 0; r0 < nrows; r0 += kMaxGridY)               // (gridDim.y is limited to 65535: slabs of rows)
+        hipLaunchKernelGGL((k_coherence_hist<T>), dim3(gx, unsigned(std::min(kMaxGridY, nrows - r0))), dim3(256), lds, p->stream,
+                           static_cast<const T*>(r2_dev) + size_t(r0) * size_t(ld), long(ld),
+                           reinterpret_cast<const long*>(lo_dev) + r0, reinterpret_cast<const long*>(hi_dev) + r0, nbins,
+                           reinterpret_cast<unsigned long long*>(hist_dev) + size_t(r0) * size_t(nbins));
     });
   });
 }

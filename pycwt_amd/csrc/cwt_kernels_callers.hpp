@@ -28,13 +28,14 @@ __global__ void k_wct_products(const cplx<T>* __restrict__ W1, const cplx<T>* __
 }
 
 // Boxcar along the scale axis = scipy.signal.convolve2d(T, win[:, None], 'same') (zero boundary):
-// out[j] = sum_i win[i] T[j + (L-1)/2 - i]
+// out[j] = sum_i win[i] T[j + (L-1)/2 - i].  A launch covers the rows row0 .. row0 + gridDim.y - 1 of the nrows (the host launches
+// in slabs of at most kMaxGridY rows; the taps of a row reach across the slab's edges).
 template <typename T>
 __global__ void k_boxcar_scales(const cplx<T>* __restrict__ in, int nrows, long ld, long ncols,
-                                const T* __restrict__ win, int L, cplx<T>* __restrict__ out) {
+                                const T* __restrict__ win, int L, cplx<T>* __restrict__ out, int row0) {
   const long n = long(blockIdx.x) * blockDim.x + threadIdx.x;
   if (n >= ncols) return;
-  const int j = blockIdx.y, c = (L - 1) / 2;
+  const int j = row0 + int(blockIdx.y), c = (L - 1) / 2;
   T sr = 0, si = 0;
   for (int i = 0; i < L; ++i) {
     const int jj = j + c - i;
@@ -50,14 +51,15 @@ __global__ void k_boxcar_scales(const cplx<T>* __restrict__ in, int nrows, long 
 // Same sums (same order), but every workgroup walks RB consecutive rows of its 256 columns and keeps the last L
 // input rows in a per-thread ring in LDS: every input element is read from memory (RB + L - 1) / RB times
 // instead of L times (L = 14 rows for the default dj = 1/12: 332 GB -> 34 GB per smoothing at BASELINE config 5).
+// A launch covers the strips strip0 .. strip0 + gridDim.y - 1.
 template <typename T>
 __global__ void k_boxcar_scales_ring(const cplx<T>* __restrict__ in, int nrows, long ld, long ncols,
-                                     const T* __restrict__ win, int L, cplx<T>* __restrict__ out, int RB) {
+                                     const T* __restrict__ win, int L, cplx<T>* __restrict__ out, int RB, int strip0) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   cplx<T>* ring = reinterpret_cast<cplx<T>*>(lds_raw) + threadIdx.x;       // slot s at ring[s * blockDim.x]
   const long n = long(blockIdx.x) * blockDim.x + threadIdx.x;
   const bool live = n < ncols;
-  const int j0 = blockIdx.y * RB, c = (L - 1) / 2, jend = (j0 + RB < nrows) ? j0 + RB : nrows;
+  const int j0 = (strip0 + int(blockIdx.y)) * RB, c = (L - 1) / 2, jend = (j0 + RB < nrows) ? j0 + RB : nrows;
   const int bias = L * (nrows / L + 2);                                     // keeps (jj + bias) positive
   auto fetch = [&](int jj) {
     return (live && jj >= 0 && jj < nrows) ? in[long(jj) * ld + n] : mk<T>(T(0), T(0));

@@ -1178,10 +1178,13 @@ int wct_products_impl(cwt_plan* p, const void* W1, const void* W2, const double*
   int rc = upload_reals<T>(p, inv.data(), nrows);
   if (rc) return rc;
   return timed_launch(p, KC_ELEMENTWISE, [&] {
-    hipLaunchKernelGGL((k_wct_products<T>), dim3(unsigned((ncols + 255) / 256), nrows), dim3(256), 0, p->stream,
-                       static_cast<const cplx<T>*>(W1), static_cast<const cplx<T>*>(W2),
-                       static_cast<const T*>(p->weights_dev), long(ld), long(ncols), static_cast<cplx<T>*>(P),
-                       static_cast<cplx<T>*>(C), static_cast<T*>(A));
+    for (int r0 = 0; r0 < nrows; r0 += kMaxGridY) {            // (gridDim.y is limited to 65535: slabs of rows)
+      const size_t o = size_t(r0) * size_t(ld);
+      hipLaunchKernelGGL((k_wct_products<T>), dim3(unsigned((ncols + 255) / 256), unsigned(std::min(kMaxGridY, nrows - r0))),
+                         dim3(256), 0, p->stream, static_cast<const cplx<T>*>(W1) + o, static_cast<const cplx<T>*>(W2) + o,
+                         static_cast<const T*>(p->weights_dev) + r0, long(ld), long(ncols), static_cast<cplx<T>*>(P) + o,
+                         static_cast<cplx<T>*>(C) + o, static_cast<T*>(A) + o);
+    }
   });
 }
 
@@ -1193,25 +1196,32 @@ int boxcar_impl(cwt_plan* p, const void* in, int nrows, int64_t ld, int64_t ncol
   const size_t ring_bytes = size_t(nwin) * 256 * sizeof(cplx<T>);
   if (nwin > 1 && ring_bytes <= 64 * 1024) {       // sliding window over 32-row strips (see the kernel)
     const int RB = 32;
+    const int strips = (nrows + RB - 1) / RB;
     return timed_launch(p, KC_ELEMENTWISE, [&] {
-      hipLaunchKernelGGL((k_boxcar_scales_ring<T>), dim3(unsigned((ncols + 255) / 256), unsigned((nrows + RB - 1) / RB)),
-                         dim3(256), ring_bytes, p->stream, static_cast<const cplx<T>*>(in), nrows, long(ld),
-                         long(ncols), static_cast<const T*>(p->weights_dev), nwin, static_cast<cplx<T>*>(out), RB);
+      for (int s0 = 0; s0 < strips; s0 += kMaxGridY)
+        hipLaunchKernelGGL((k_boxcar_scales_ring<T>), dim3(unsigned((ncols + 255) / 256), unsigned(std::min(kMaxGridY, strips - s0))),
+                           dim3(256), ring_bytes, p->stream, static_cast<const cplx<T>*>(in), nrows, long(ld),
+                           long(ncols), static_cast<const T*>(p->weights_dev), nwin, static_cast<cplx<T>*>(out), RB, s0);
     });
   }
+  // slabs of rows (gridDim.y is limited to 65535); every slab sees all nrows, so the taps reach across its edges
   return timed_launch(p, KC_ELEMENTWISE, [&] {
-    hipLaunchKernelGGL((k_boxcar_scales<T>), dim3(unsigned((ncols + 255) / 256), nrows), dim3(256), 0, p->stream,
-                       static_cast<const cplx<T>*>(in), nrows, long(ld), long(ncols),
-                       static_cast<const T*>(p->weights_dev), nwin, static_cast<cplx<T>*>(out));
+    for (int r0 = 0; r0 < nrows; r0 += kMaxGridY)
+      hipLaunchKernelGGL((k_boxcar_scales<T>), dim3(unsigned((ncols + 255) / 256), unsigned(std::min(kMaxGridY, nrows - r0))),
+                         dim3(256), 0, p->stream, static_cast<const cplx<T>*>(in), nrows, long(ld), long(ncols),
+                         static_cast<const T*>(p->weights_dev), nwin, static_cast<cplx<T>*>(out), r0);
   });
 }
 
 template <typename T>
 int coherence_impl(cwt_plan* p, const void* S, const void* S12, int nrows, int64_t ld, int64_t ncols, void* out) {
   return timed_launch(p, KC_ELEMENTWISE, [&] {
-    hipLaunchKernelGGL((k_wct_coherence<T>), dim3(unsigned((ncols + 255) / 256), nrows), dim3(256), 0, p->stream,
-                       static_cast<const cplx<T>*>(S), static_cast<const cplx<T>*>(S12), long(ld), long(ncols),
-                       static_cast<T*>(out));
+    for (int r0 = 0; r0 < nrows; r0 += kMaxGridY) {            // (gridDim.y is limited to 65535: slabs of rows)
+      const size_t o = size_t(r0) * size_t(ld);
+      hipLaunchKernelGGL((k_wct_coherence<T>), dim3(unsigned((ncols + 255) / 256), unsigned(std::min(kMaxGridY, nrows - r0))),
+                         dim3(256), 0, p->stream, static_cast<const cplx<T>*>(S) + o, static_cast<const cplx<T>*>(S12) + o,
+                         long(ld), long(ncols), static_cast<T*>(out) + o);
+    }
   });
 }
 

@@ -26,18 +26,19 @@ def test_kernel_suites_under_address_and_undefined_behaviour_sanitizers():
     env["PYTHONPATH"] = ROOT
     env.pop("CWT_RUN_SANITIZERS", None)
     r = subprocess.run([sys.executable, "-m", "pytest", "tests/test_kernels_randomized.py", "tests/test_new_forms_emulated.py",
-                        "tests/test_c_host.py", "-x", "-q", "-n", "6", "-m", "not gpu"], cwd=ROOT, env=env, capture_output=True, text=True)
+                        "tests/test_c_host.py", "tests/test_exports_edges.py", "-x", "-q", "-n", "6", "-m", "not gpu"], cwd=ROOT, env=env, capture_output=True, text=True)
     tail = (r.stdout + r.stderr)[-4000:]
     assert r.returncode == 0, tail
     assert "ERROR: AddressSanitizer" not in tail and "runtime error:" not in tail, tail
 
 
 SCHEDULE_MODULES = ["tests/test_kernels_emulated.py", "tests/test_kernels_randomized.py", "tests/test_new_forms_emulated.py",
-                    "tests/test_power_emulated.py", "tests/test_adjoint_emulated.py", "tests/test_callers_emulated.py"]
+                    "tests/test_power_emulated.py", "tests/test_adjoint_emulated.py", "tests/test_callers_emulated.py",
+                    "tests/test_exports_edges.py"]
 
 
 @pytest.mark.slow
-@pytest.mark.skipif(not os.environ.get("CWT_RUN_SCHEDULES"), reason="set CWT_RUN_SCHEDULES=1 (the six emulated kernel modules, twice)")
+@pytest.mark.skipif(not os.environ.get("CWT_RUN_SCHEDULES"), reason="set CWT_RUN_SCHEDULES=1 (the seven emulated kernel modules, twice)")
 @pytest.mark.parametrize("sched", ["waves-reverse", "waves-seeded:1"])
 def test_emulated_kernel_modules_under_a_wave_schedule(sched):
     """The emulated kernel modules as they are, in a child process whose emulator runs one wavefront at a time (CWT_EMU_SCHEDULE,
