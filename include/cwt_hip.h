@@ -298,6 +298,27 @@ int cwt_transform_batch_power(cwt_plan* plan, const void* x_dev, int nbatch, int
  * filter bank of the caller's, Bluestein).  W_dev: nrows x ldw complex, P_dev: nrows x ldp reals (may not alias W_dev).   */
 int cwt_abs2(cwt_plan* plan, const void* W_dev, int64_t ldw, int64_t ncols, int nrows, void* P_dev, int64_t ldp);
 
+/* ---- weighted output: (alpha Q) W instead of W ----------------------------------------------------------------------------
+ * What the backward of a differentiable power transform needs: with P = |W|^2 and a cotangent gP of P, the cotangent of W under
+ * the convention of cwt_adjoint_rows is G = 2 gP W -- W recomputed from the signal and multiplied in the row kernels' store, so
+ * that nothing of nrows x ncols elements has to be kept between forward and backward.  G[j, n] = (alpha * Q[j, n]) * W[j, n]:
+ * t = alpha * Q[j, n] is formed once per element, then t * Re W and t * Im W are written.  Q_dev is an nrows x ld matrix of
+ * reals of the plan's precision, read at the [j, n] of the store and never written; G_dev is nrows x ld complex; Q and G
+ * share the ONE leading dimension ld >= ncols (and, for the batch call, the batch stride nrows * ld).  Columns ncols .. ld - 1
+ * and rows not asked for are left untouched in G.  Each *_weighted function mirrors its sibling -- the same arguments, checks,
+ * row table (the output is not part of its key: a weighted call after a transform or power call of the same scales hits the
+ * cached table), schedule and NaN behaviour (a NaN or Inf in Q or W gives what the two multiplications give).  Fused in the row
+ * forms in which the power output is fused (polynomial rows apply their carrier, as for W); not offered for filter banks of
+ * the caller's, the Bluestein path or a spectrum without its signal.  Refused with CWT_EINVAL: NULL pointers, ld < ncols, Q
+ * overlapping G.  The output mode is state of the call only.                                                                */
+int cwt_transform_weighted(cwt_plan* plan, const void* x_dev, int64_t n0, int mother, double param, double dt,
+                           const double* scales_host, int nrows, void* xhat_dev, const void* Q_dev, double alpha,
+                           void* G_dev, int64_t ld, int64_t ncols);
+/* cwt_transform_batch with the weighted output: Q_dev is nbatch x nrows x ld reals, G_dev the same shape in complex. */
+int cwt_transform_batch_weighted(cwt_plan* plan, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother,
+                                 double param, double dt, const double* scales_host, int nrows, void* xhat_dev,
+                                 const void* Q_dev, double alpha, void* G_dev, int64_t ld, int64_t ncols);
+
 /* The same two steps at a transform length n0 that is NOT a power of two -- what the reference computes when pyfftw is
  * installed: helpers.py:15-19 then passes n = len(signal), i.e. no zero padding and circular edges -- by Bluestein's
  * chirp-z identity on this plan's power-of-two engine.  The plan must have nfft >= 2*n0 - 1.  xhat_dev: n0 complex

@@ -51,6 +51,10 @@ SYMBOLS = [
     ("cwt_transform_batch_power", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double,
                                             C.POINTER(C.c_double), C.c_int, _P, _P, C.c_int64, C.c_int64]),
     ("cwt_abs2", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P, C.c_int64]),
+    ("cwt_transform_weighted", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double),
+                                         C.c_int, _P, _P, C.c_double, _P, C.c_int64, C.c_int64]),
+    ("cwt_transform_batch_weighted", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double,
+                                               C.POINTER(C.c_double), C.c_int, _P, _P, C.c_double, _P, C.c_int64, C.c_int64]),
     ("cwt_adjoint_rows", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double,
                                    C.POINTER(C.c_double), C.c_int, _P, C.c_int64, C.c_int]),
     ("cwt_forward_fft_n", C.c_int, [_P, _P, C.c_int64, _P]),
@@ -427,6 +431,29 @@ class Plan:
         s = np.ascontiguousarray(scales, dtype=np.float64)
         self.lib.check(self.lib.cwt_transform_batch_power(self.h, _P(x_dev), nbatch, x_ld, n0, mother, float(param),
                                                           float(dt), _dptr(s), s.size, _P(xhat_dev), _P(P_dev), ldp, ncols))
+
+    # -- weighted output: G = (alpha Q) W, Q nrows x ld reals and G nrows x ld complex on ONE leading dimension --
+    @_locked
+    def transform_weighted(self, x_dev: int, n0: int, mother: int, param: float, dt: float, scales, xhat_dev, Q_dev: int,
+                           alpha: float, G_dev: int, ld: int, ncols: int):
+        """`transform` writing (alpha Q) W (cwt_transform_weighted): the cotangent of W under a weight on its power."""
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        self.lib.check(self.lib.cwt_transform_weighted(self.h, _P(x_dev), n0, mother, float(param), float(dt), _dptr(s), s.size,
+                                                       _P(xhat_dev) if xhat_dev else None, _P(Q_dev), float(alpha), _P(G_dev),
+                                                       ld, ncols))
+
+    @_locked
+    def transform_batch_weighted(self, x_dev: int, nbatch: int, x_ld: int, n0: int, mother: int, param: float, dt: float,
+                                 scales, xhat_dev: int, Q_dev: int, alpha: float, G_dev: int, ld: int, ncols: int):
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        self.lib.check(self.lib.cwt_transform_batch_weighted(self.h, _P(x_dev), nbatch, x_ld, n0, mother, float(param),
+                                                             float(dt), _dptr(s), s.size, _P(xhat_dev), _P(Q_dev), float(alpha),
+                                                             _P(G_dev), ld, ncols))
+
+    def transform_rows_weighted(self, *args, **kwargs):
+        """Not offered: the weighted output needs the signal (cwt_transform_weighted), as the backward that uses it has it."""
+        raise NotImplementedError("the weighted output is not offered from a spectrum alone (there is no cwt_transform_rows_weighted): "
+                                  "call transform_weighted with the signal")
 
     @_locked
     def abs2(self, W_dev: int, ldw: int, ncols: int, nrows: int, P_dev: int, ldp: int):

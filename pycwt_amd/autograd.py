@@ -73,10 +73,69 @@ def _function(torch):
             eng.plan.adjoint_rows(g.data_ptr(), nb, rows * n0, n0, n0, kind, param, dt, sj, xbar.data_ptr(), n0)
             return xbar, None, None, None, None, None
 
-    return CwtRows
+    class CwtPower(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, eng, kind, param, dt, sj):
+            n0 = x.shape[-1]
+            P = torch.empty(tuple(x.shape[:-1]) + (sj.size, n0), dtype=x.dtype, device=x.device)
+            tol = _tolerance()
+            _on_current_stream(torch, eng, x.device)
+            eng.plan.set_tolerance(tol)
+            eng.transform_power(x, n0, None, kind, param, dt, sj, P, n0)
+            ctx.save_for_backward(x)                             # the signal and the geometry: nothing of rows x n0 elements
+            ctx.geometry = (eng, kind, param, dt, sj, tol)
+            return P
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gP):
+            (x,) = ctx.saved_tensors
+            eng, kind, param, dt, sj, tol = ctx.geometry
+            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+            q = gP.to(x.dtype).contiguous()
+            rows, n0 = q.shape[-2], q.shape[-1]
+            nb = q.shape[0] if q.dim() == 3 else 1
+            G = torch.empty(q.shape, dtype=cplx_t, device=q.device)
+            xbar = torch.empty(tuple(q.shape[:-2]) + (n0,), dtype=x.dtype, device=q.device)
+            _on_current_stream(torch, eng, q.device)
+            eng.plan.set_tolerance(tol)
+            # dL = sum gP 2 Re(conj(W) dW) = Re sum conj(2 gP W) dW: W recomputed from x, weighted in the row kernels' store
+            eng.transform_weighted(x, n0, None, kind, param, dt, sj, q, 2.0, G, n0)
+            eng.plan.adjoint_rows(G.data_ptr(), nb, rows * n0, n0, n0, kind, param, dt, sj, xbar.data_ptr(), n0)
+            del G
+            return xbar, None, None, None, None, None
+
+    return CwtRows, CwtPower
 
 
 _fn = None
+
+
+def _prepare(name, x, dt, dj, s0, J, wavelet, freqs, pad):
+    """The checks, grid and engine of one call of `name` (cwt_torch, cwt_power_torch)."""
+    import torch
+    if not pad:
+        raise ValueError(f"{name}: pad=False (Bluestein transforms of any length) has no adjoint; use pad=True")
+    if not torch.is_tensor(x) or x.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"{name}: x must be a float64 or float32 torch tensor")
+    if x.dim() not in (1, 2) or x.shape[-1] < 1:
+        raise ValueError(f"{name}: x must have shape (n0,) or (B, n0)")
+    mother = _check_parameter_wavelet(wavelet)
+    if not hasattr(mother, "device_id"):
+        raise ValueError(f"{name}: only the built-in mothers (Morlet, Paul, DOG) have a HIP adjoint")
+    lib = _hip.load()
+    if x.device.type != "cuda" and lib.backend().startswith("hip"):
+        raise RuntimeError(f"{name} needs a tensor on a GPU (the HIP kernels cannot read host memory)")
+    n0 = int(x.shape[-1])
+    N, sj, freqs, coi, _, bad = _geometry(mother, n0, dt, dj, s0, J, freqs, True)
+    if bad is not None and not bad.all():
+        sj, freqs = sj[~bad], np.asarray(freqs)[~bad]
+    sj, freqs, coi = np.array(sj, dtype=np.float64), np.array(freqs), np.array(coi)
+    kind, param = _device_id(mother)
+    nb = int(x.shape[0]) if x.dim() == 2 else 1
+    precision = 64 if x.dtype == torch.float64 else 32
+    eng = _engine(torch, N, precision, nb * sj.size, x.device, lib)
+    return torch, eng, kind, float(param), sj, freqs, coi
 
 
 def cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=True):
@@ -89,29 +148,25 @@ def cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=T
     current stream.  Built-in mothers and pad=True only.  Tensors must live on a GPU; CPU tensors are accepted only by the
     CPU emulation of the library that the test suite loads."""
     global _fn
-    import torch
-    if not pad:
-        raise ValueError("cwt_torch: pad=False (Bluestein transforms of any length) has no adjoint; use pad=True")
-    if not torch.is_tensor(x) or x.dtype not in (torch.float64, torch.float32):
-        raise TypeError("cwt_torch: x must be a float64 or float32 torch tensor")
-    if x.dim() not in (1, 2) or x.shape[-1] < 1:
-        raise ValueError("cwt_torch: x must have shape (n0,) or (B, n0)")
-    mother = _check_parameter_wavelet(wavelet)
-    if not hasattr(mother, "device_id"):
-        raise ValueError("cwt_torch: only the built-in mothers (Morlet, Paul, DOG) have a HIP adjoint")
-    lib = _hip.load()
-    if x.device.type != "cuda" and lib.backend().startswith("hip"):
-        raise RuntimeError("cwt_torch needs a tensor on a GPU (the HIP kernels cannot read host memory)")
-    n0 = int(x.shape[-1])
-    N, sj, freqs, coi, _, bad = _geometry(mother, n0, dt, dj, s0, J, freqs, True)
-    if bad is not None and not bad.all():
-        sj, freqs = sj[~bad], np.asarray(freqs)[~bad]
-    sj, freqs, coi = np.array(sj, dtype=np.float64), np.array(freqs), np.array(coi)
-    kind, param = _device_id(mother)
-    nb = int(x.shape[0]) if x.dim() == 2 else 1
-    precision = 64 if x.dtype == torch.float64 else 32
-    eng = _engine(torch, N, precision, nb * sj.size, x.device, lib)
+    torch, eng, kind, param, sj, freqs, coi = _prepare("cwt_torch", x, dt, dj, s0, J, wavelet, freqs, pad)
     if _fn is None:
         _fn = _function(torch)
-    W = _fn.apply(x.contiguous(), eng, kind, float(param), float(dt), sj)
+    W = _fn[0].apply(x.contiguous(), eng, kind, param, float(dt), sj)
     return W, sj, freqs, coi
+
+
+def cwt_power_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=True):
+    """The scalogram ``|W|^2`` of a torch tensor, differentiable with respect to it: ``cwt_torch(x, ...)[0].abs() ** 2`` without
+    W -- neither written by the forward nor kept for the backward.
+
+    Inputs, refusals, engine, stream and tolerance as ``cwt_torch``.  Returns ``(P, sj, freqs, coi)``: P float64 / float32 on
+    x's device, (rows, n0) or (B, rows, n0), written by the power row kernels (``cwt_transform_power``).  Between forward and
+    backward only x and the geometry of the call are held.  The backward recomputes W from x under the cotangent of P in the
+    row kernels' store (``cwt_transform_weighted``: G = 2 gP W, complex, freed when the backward returns) and runs the HIP
+    adjoint of the rows on G; once differentiable."""
+    global _fn
+    torch, eng, kind, param, sj, freqs, coi = _prepare("cwt_power_torch", x, dt, dj, s0, J, wavelet, freqs, pad)
+    if _fn is None:
+        _fn = _function(torch)
+    P = _fn[1].apply(x.contiguous(), eng, kind, param, float(dt), sj)
+    return P, sj, freqs, coi

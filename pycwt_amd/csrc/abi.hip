@@ -644,10 +644,26 @@ int cwt_adjoint_rows(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch
   });
 }
 
+// The weights of a *_weighted call: Q (reals of the plan's precision, laid out as the output G) and alpha
+struct Weights { const void* q; double alpha; };
+
+// Q and G of a weighted call: nbatch * nrows rows of ld elements each, neither NULL, not overlapping
+static int check_weights(const cwt_plan* p, const Weights& wq, const void* G_dev, int nbatch, int nrows, int64_t ld, int64_t ncols) {
+  if (!wq.q) return fail(CWT_EINVAL, "NULL argument");
+  if (ncols < 1 || ld < ncols) return fail(CWT_EINVAL, "weighted output: need 1 <= ncols <= ld");
+  if (nbatch < 1 || nrows < 1) return fail(CWT_EINVAL, "weighted output: need nbatch >= 1 and nrows >= 1");
+  const size_t elems = (size_t(nbatch) * size_t(nrows) - 1) * size_t(ld) + size_t(ncols), es = p->esize();
+  const uintptr_t q0 = reinterpret_cast<uintptr_t>(wq.q), g0 = reinterpret_cast<uintptr_t>(G_dev);
+  if (q0 < g0 + elems * 2 * es && g0 < q0 + elems * es) return fail(CWT_EINVAL, "weighted output: Q and G overlap");
+  return CWT_OK;
+}
+
 static int transform_entry(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double param, double dt,
-                           const double* scales, int nrows, void* xhat_dev, void* W_dev, int64_t ldw, int64_t ncols, int power) {
+                           const double* scales, int nrows, void* xhat_dev, void* W_dev, int64_t ldw, int64_t ncols, int power,
+                           const Weights* wq = nullptr) {
   if (!p || !x_dev || !scales || !W_dev) return fail(CWT_EINVAL, "NULL argument");
   if (n0 < 1 || n0 > p->N) return fail(CWT_EINVAL, "n0 must be in [1, nfft]");
+  if (wq) if (int rc = check_weights(p, *wq, W_dev, 1, nrows, ldw, ncols)) return rc;
   HIPCHECK(hipSetDevice(p->device));
   int rc = prepare_rows_table(p, true, mother, param, dt, scales, nrows, ldw, ncols);
   if (!rc && p->logN >= 18 && !p->profile) rc = ensure_distinct_queues(p);     // (transforms that use the side streams)
@@ -662,6 +678,7 @@ static int transform_entry(cwt_plan* p, const void* x_dev, int64_t n0, int mothe
   const Mother mo = mother_of(mother, param);
   CallScope scope(p);
   p->call.power = power;
+  if (wq) { p->call.weighted = 1; p->call.q = wq->q; p->call.alpha = wq->alpha; }
   return scope.done(by_precision(p, [&](auto t) {
     return transform_impl<decltype(t)>(p, x_dev, n0, xhat_dev, mo, nrows, W_dev, ldw, ncols);
   }));
@@ -675,6 +692,15 @@ int cwt_transform(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double
 int cwt_transform_power(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double param, double dt,
                         const double* scales, int nrows, void* xhat_dev, void* P_dev, int64_t ldp, int64_t ncols) {
   return transform_entry(p, x_dev, n0, mother, param, dt, scales, nrows, xhat_dev, P_dev, ldp, ncols, 1);
+}
+
+// G = (alpha Q) W: the row kernels of cwt_transform under a real weight per element (the cotangent of W that a weight on |W|^2
+// induces); the row table and the schedule are those of cwt_transform / cwt_transform_power for the same scales
+int cwt_transform_weighted(cwt_plan* p, const void* x_dev, int64_t n0, int mother, double param, double dt, const double* scales,
+                           int nrows, void* xhat_dev, const void* Q_dev, double alpha, void* G_dev, int64_t ld, int64_t ncols) {
+  const Weights wq{Q_dev, alpha};
+  if (!Q_dev) return fail(CWT_EINVAL, "NULL argument");
+  return transform_entry(p, x_dev, n0, mother, param, dt, scales, nrows, xhat_dev, G_dev, ld, ncols, 0, &wq);
 }
 
 int cwt_transform_rows_batch(cwt_plan* p, const void* xhat_dev, int nbatch, int64_t xhat_ld, int mother,
@@ -698,10 +724,11 @@ int cwt_transform_rows_batch(cwt_plan* p, const void* xhat_dev, int nbatch, int6
 
 static int transform_batch_entry(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother,
                                  double param, double dt, const double* scales, int nrows, void* xhat_dev, void* W_dev,
-                                 int64_t ldw, int64_t ncols, int power) {
+                                 int64_t ldw, int64_t ncols, int power, const Weights* wq = nullptr) {
   if (!p || !x_dev || !scales || !xhat_dev || !W_dev) return fail(CWT_EINVAL, "NULL argument");
   if (nbatch < 1 || nrows < 1 || int64_t(nbatch) * nrows > p->max_rows)
     return fail(CWT_EINVAL, "need nbatch*nrows <= max_rows");
+  if (wq) if (int rc = check_weights(p, *wq, W_dev, nbatch, nrows, ldw, ncols)) return rc;
   if (n0 < 1 || n0 > p->N || x_ld < n0) return fail(CWT_EINVAL, "need 1 <= n0 <= nfft and x_ld >= n0");
   HIPCHECK(hipSetDevice(p->device));
   // as cwt_transform_rows_batch, with the signals at hand: time-compact rows may take the overlap-save form
@@ -719,6 +746,7 @@ static int transform_batch_entry(cwt_plan* p, const void* x_dev, int nbatch, int
   if (rc) return rc;
   p->call.ols_x_ld = x_ld;
   p->call.power = power;
+  if (wq) { p->call.weighted = 1; p->call.q = wq->q; p->call.alpha = wq->alpha; }
   return scope.done(by_precision(p, [&](auto t) {
     return rows_impl<decltype(t)>(p, xhat_dev, mo, nbatch * nrows, W_dev, ldw, ncols, x_dev, n0);
   }));
@@ -734,6 +762,14 @@ int cwt_transform_batch_power(cwt_plan* p, const void* x_dev, int nbatch, int64_
                               double param, double dt, const double* scales, int nrows, void* xhat_dev, void* P_dev,
                               int64_t ldp, int64_t ncols) {
   return transform_batch_entry(p, x_dev, nbatch, x_ld, n0, mother, param, dt, scales, nrows, xhat_dev, P_dev, ldp, ncols, 1);
+}
+
+int cwt_transform_batch_weighted(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother, double param,
+                                 double dt, const double* scales, int nrows, void* xhat_dev, const void* Q_dev, double alpha,
+                                 void* G_dev, int64_t ld, int64_t ncols) {
+  const Weights wq{Q_dev, alpha};
+  if (!Q_dev) return fail(CWT_EINVAL, "NULL argument");
+  return transform_batch_entry(p, x_dev, nbatch, x_ld, n0, mother, param, dt, scales, nrows, xhat_dev, G_dev, ld, ncols, 0, &wq);
 }
 
 int cwt_transform_rows_table(cwt_plan* p, const void* xhat_dev, const void* table_dev, const int* k_lo,

@@ -171,7 +171,7 @@ template <typename T, int MODE, typename WT = cplx<T>>
 __global__ void __launch_bounds__(CWT_MAX_THREADS)
 k_small(const void* __restrict__ in, const RowDesc* __restrict__ rows, int nrows, Mother mo,
         const cplx<T>* __restrict__ tw, int logN, int logTB, long n0, long in_ld,
-        WT* __restrict__ out, long ldw, long ncols) {
+        out_arg_t<WT> out, long ldw, long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
   const int N = 1 << logN, logNT = logN - 4, NT = 1 << logNT;
@@ -217,6 +217,8 @@ k_small(const void* __restrict__ in, const RowDesc* __restrict__ rows, int nrows
     const long m = g.j + (e << logNT);
     if constexpr (power_out<T, WT>()) {
       if (m < ncols) out[orow * ldw + m] = re[e] * re[e] + im[e] * im[e];
+    } else if constexpr (weighted_out<WT>()) {
+      if (m < ncols) store_w<T>(out + (orow * ldw + m), re[e], im[e]);
     } else {
       if (m < ncols) out[orow * ldw + m] = mk<T>(re[e], MODE != IN_SPECTRUM ? -im[e] : im[e]);
     }
@@ -226,7 +228,7 @@ k_small(const void* __restrict__ in, const RowDesc* __restrict__ rows, int nrows
 // k_direct: N <= 8.  One thread per output element.
 template <typename T, int MODE, typename WT = cplx<T>>
 __global__ void k_direct(const void* __restrict__ in, const RowDesc* __restrict__ rows, int nrows,
-                         Mother mo, int logN, long n0, long in_ld, WT* __restrict__ out, long ldw,
+                         Mother mo, int logN, long n0, long in_ld, out_arg_t<WT> out, long ldw,
                          long ncols) {
   const int N = 1 << logN;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -253,6 +255,7 @@ __global__ void k_direct(const void* __restrict__ in, const RowDesc* __restrict_
   }
   const long orow = (MODE != IN_SPECTRUM) ? long(row) : long(rows[row].out_row);
   if constexpr (power_out<T, WT>()) out[orow * ldw + m] = T(sr) * T(sr) + T(si) * T(si);
+  else if constexpr (weighted_out<WT>()) store_w<T>(out + (orow * ldw + m), T(sr), T(si));
   else out[orow * ldw + m] = mk<T>(T(sr), T(MODE != IN_SPECTRUM ? -si : si));
 }
 
@@ -277,7 +280,7 @@ template <typename T, typename WT = cplx<T>>
 __global__ void __launch_bounds__(CWT_MAX_THREADS)
 k_narrow(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ rows, Mother mo,
          const cplx<T>* __restrict__ tw, TwN<T> twn, int logN, int logK, int logTB,
-         WT* __restrict__ W, long ldw, long ncols) {
+         out_arg_t<WT> W, long ldw, long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
   const int N = 1 << logN, K = 1 << logK, logNT = logK - 4, NT = 1 << logNT;
@@ -320,7 +323,7 @@ k_narrow(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ rows, Mot
 
   wg_ifft<T, true>(re, im, lds, g, tw);
 
-  WT* wrow = W + long(rd.out_row) * ldw;
+  out_ptr_t<WT> wrow = W + long(rd.out_row) * ldw;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const long n = (long(g.j + (e << logNT)) << logR) + r;
@@ -388,7 +391,7 @@ k_pass_a(const void* __restrict__ in, const RowDesc* __restrict__ rows, Mother m
 template <typename T, bool CONJ, typename WT = cplx<T>>
 __global__ void __launch_bounds__(CWT_MAX_THREADS)
 k_pass_b(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
-         const cplx<T>* __restrict__ tw, TwN<T> twn, int logN, int logK, int logTB, WT* __restrict__ W,
+         const cplx<T>* __restrict__ tw, TwN<T> twn, int logN, int logK, int logTB, out_arg_t<WT> W,
          long ldw, long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
@@ -425,7 +428,7 @@ k_pass_b(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
   for (int c = 0; c < 16; ++c) im[c] = lds[lds_swizzle<T>(threadIdx.x + c * blockDim.x)];
 
   const long orow = rows ? long(rows[blockIdx.y].out_row) : long(blockIdx.y);
-  WT* wrow = W + orow * ldw;
+  out_ptr_t<WT> wrow = W + orow * ldw;
 #pragma unroll
   for (int c = 0; c < 16; ++c) {
     const int idx = threadIdx.x + c * blockDim.x;
@@ -446,7 +449,7 @@ k_pass_b(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
 // that consecutive lanes store consecutive r: W[R m + r0 + t] in TB*sizeof(complex)-byte segments.
 template <typename T, int LOGK, int LOGP, bool CONJ, typename WT>
 __device__ __forceinline__ void transpose_store(T (&re)[16], T (&im)[16], T* lds, int t, int j,
-                                                WT* __restrict__ wrow, int logR, unsigned r0,
+                                                out_arg_t<WT> wrow, int logR, unsigned r0,
                                                 long ncols) {
   constexpr int LOGTB = LOGP - LOGK, NT = 1 << (LOGK - 4), BD = 1 << (LOGP - 4);
   constexpr int TS = (BD) + (BD >> 4);                    // physical stride of BD elements
@@ -537,7 +540,7 @@ __device__ __forceinline__ void narrow_phases(const cplx<T>* __restrict__ xhat, 
 template <typename T, int LOGK, int LOGP, int NTERMS, typename WT>
 __device__ __forceinline__ void narrow_ct_body(const cplx<T>* __restrict__ xhat, const RowDesc& rd,
                                                const Mother& mo, const cplx<T>* __restrict__ tw_all,
-                                               const TwN<T>& twn, int logN, WT* __restrict__ W, long ldw,
+                                               const TwN<T>& twn, int logN, out_arg_t<WT> W, long ldw,
                                                long ncols, T* lds) {
   constexpr int LOGTB = LOGP - LOGK, K = 1 << LOGK, LOGNT = LOGK - 4, NT = 1 << LOGNT;
   // PLANES layout: lanes run along the residue r, stores go straight from registers in 128-B segments.
@@ -579,7 +582,7 @@ __device__ __forceinline__ void narrow_ct_body(const cplx<T>* __restrict__ xhat,
   narrow_phases<T, LOGK, LOGP, NTERMS, NQ, 0>(xhat, rd, mo, N, ytile, f.j, rho, step, stepw, cur, d, re, im);
   __syncthreads();  // the tiles alias the exchange buffer
   f.run(re, im, lds, tw);
-  WT* wrow = W + long(rd.out_row) * ldw;
+  out_ptr_t<WT> wrow = W + long(rd.out_row) * ldw;
   const unsigned off = (unsigned(f.j) << logR) + r;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
@@ -600,7 +603,7 @@ constexpr int narrow_waves_per_simd() {
 template <typename T, int LOGP, typename WT = cplx<T>>
 __global__ void __launch_bounds__(1 << (LOGP - 4), (narrow_waves_per_simd<T, LOGP>()))
 k_narrow_ct_all(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ rows, Mother mo,
-                const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, WT* __restrict__ W, long ldw,
+                const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, out_arg_t<WT> W, long ldw,
                 long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
@@ -624,7 +627,7 @@ k_narrow_ct_all(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ ro
 template <typename T, int LOGP, typename WT = cplx<T>>
 __global__ void __launch_bounds__(1 << (LOGP - 4), (narrow_waves_per_simd<T, LOGP>()))
 k_narrow_ct_many(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ rows, Mother mo,
-                 const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, WT* __restrict__ W, long ldw,
+                 const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, out_arg_t<WT> W, long ldw,
                  long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
@@ -646,7 +649,7 @@ k_narrow_ct_many(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ r
 template <typename T, typename WT = cplx<T>>
 __global__ void __launch_bounds__(1024, 4)
 k_narrow_ct_big(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ rows, Mother mo,
-                const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, WT* __restrict__ W, long ldw,
+                const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, out_arg_t<WT> W, long ldw,
                 long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
@@ -820,7 +823,7 @@ k_pass_a_ct_rows(const cplx<T>* __restrict__ xhat, const RowDesc* __restrict__ r
 template <typename T, int LOGK, int LOGP, bool CONJ, typename WT = cplx<T>>
 __global__ void __launch_bounds__(1 << (LOGP - 4), (sizeof(T) == 8 ? CWT_LB_PASS_B_F64 : CWT_LB_PASS_B_F32))
 k_pass_b_ct(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
-            const cplx<T>* __restrict__ tw, TwN<T> twn, int logN, WT* __restrict__ W, long ldw, long ncols) {
+            const cplx<T>* __restrict__ tw, TwN<T> twn, int logN, out_arg_t<WT> W, long ldw, long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
   constexpr int LOGTB = LOGP - LOGK, LOGNT = LOGK - 4, NT = 1 << LOGNT, BD = 1 << (LOGP - 4);

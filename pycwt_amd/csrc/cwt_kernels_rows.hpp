@@ -141,7 +141,7 @@ k_ols_fwd_r(const T* __restrict__ x, long n0, int logN, OlsClasses cls, const cp
 template <typename T, int LOGP, typename WT>
 __device__ __forceinline__ void ols_full_body(const cplx<T>* __restrict__ xb, const RowDesc& rd,
                                               const cplx<T>* __restrict__ gt, const cplx<T>* __restrict__ tw_all,
-                                              WT* __restrict__ wout, int H, int nlim, T* lds) {
+                                              out_arg_t<WT> wout, int H, int nlim, T* lds) {
   constexpr int P = 1 << LOGP, NT = P >> 4;
   using F = ct::Fft<T, LOGP, 0, false>;
   F f;
@@ -174,7 +174,7 @@ template <typename T, int LOGK, int LOGP, typename WT>
 __device__ __forceinline__ void ols_band_body(const cplx<T>* __restrict__ xb, const RowDesc& rd,
                                               const cplx<T>* __restrict__ gt,
                                               const cplx<T>* __restrict__ tw_all, const TwN<T>& twn, int logN,
-                                              WT* __restrict__ wout, int H, int nlim, T* lds, int logx, unsigned g) {
+                                              out_arg_t<WT> wout, int H, int nlim, T* lds, int logx, unsigned g) {
   // logx = log2(P_b / P), g < P_b / P: this workgroup's residues are r = g TB + t of the P_b / K of the block
   constexpr int LOGTB = LOGP - LOGK, K = 1 << LOGK, NT = K >> 4, BD = 1 << (LOGP - 4);
   using F = ct::Fft<T, LOGK, LOGTB, true, (LOGTB <= CWT_OLS_PAD_LOGTB)>;
@@ -272,7 +272,7 @@ __device__ __forceinline__ pairf pair_of(float a, float b) { pairf v = {a, b}; r
 template <int LOGP, typename WT>
 __device__ __forceinline__ void ols_full_body2(const float2* __restrict__ xb0, const float2* __restrict__ xb1, const RowDesc& rd,
                                                const float2* __restrict__ gt, const float2* __restrict__ tw_all,
-                                               WT* __restrict__ w0, WT* __restrict__ w1, int H, int nlim0, int nlim1,
+                                               out_arg_t<WT> w0, out_arg_t<WT> w1, int H, int nlim0, int nlim1,
                                                pairf* lds) {
   constexpr int P = 1 << LOGP, NT = P >> 4;
   using F = ct::Fft<pairf, LOGP, 0, false>;
@@ -307,7 +307,7 @@ __device__ __forceinline__ void ols_full_body2(const float2* __restrict__ xb0, c
 template <int LOGK, int LOGP, typename WT>
 __device__ __forceinline__ void ols_band_body2(const float2* __restrict__ xb0, const float2* __restrict__ xb1, const RowDesc& rd,
                                                const float2* __restrict__ gt, const float2* __restrict__ tw_all,
-                                               const TwN<float>& twn, int logN, WT* __restrict__ w0, WT* __restrict__ w1,
+                                               const TwN<float>& twn, int logN, out_arg_t<WT> w0, out_arg_t<WT> w1,
                                                int H, int nlim0, int nlim1, pairf* lds, int logx, unsigned g) {
   constexpr int LOGTB = LOGP - LOGK, K = 1 << LOGK, NT = K >> 4, BD = 1 << (LOGP - 4);
   using F = ct::Fft<pairf, LOGK, LOGTB, true, (LOGTB <= CWT_OLS_PAD_LOGTB)>;
@@ -397,7 +397,7 @@ template <typename T, int LOGP, typename WT = cplx<T>>
 __global__ void __launch_bounds__(1 << (LOGP - 4), (sizeof(T) == 8 ? (LOGP == 12 ? CWT_LB_OLS_F64_HALF : CWT_LB_OLS_F64)
                                                                 : (LOGP == 12 ? CWT_LB_OLS_F32_HALF : CWT_LB_OLS_F32)))
 k_ols_ct(const cplx<T>* __restrict__ xs, const RowDesc* __restrict__ rows, const cplx<T>* __restrict__ gtab,
-         const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, OlsClasses cls, WT* __restrict__ W, long ldw,
+         const cplx<T>* __restrict__ tw_all, TwN<T> twn, int logN, OlsClasses cls, out_arg_t<WT> W, long ldw,
          long ncols, unsigned wg0) {
   // wg0 (a multiple of 8): this launch covers the workgroups wg0 ... of the class list -- the classes on blocks of one tile and the
   // classes on longer blocks go in two launches where their block spectra come from two kernels (serial schedule)
@@ -429,7 +429,7 @@ k_ols_ct(const cplx<T>* __restrict__ xs, const RowDesc* __restrict__ rows, const
   const long col0 = long(blk) * L;
   const long left = ncols - col0;
   const int nlim = left < L ? int(left) : L;
-  WT* wout = W + long(rd.out_row) * ldw + col0;
+  out_ptr_t<WT> wout = W + long(rd.out_row) * ldw + col0;
   const cplx<T>* gt = gtab + rd.tab_off;
   if constexpr (PAIR) {
     const bool two = blk + 1u < unsigned(oc.nblocks);
@@ -557,7 +557,7 @@ k_aols_fwd(const cplx<T>* __restrict__ xm, int logN, int halo, const cplx<T>* __
 template <typename T, int LOGP, typename WT = cplx<T>>
 __global__ void __launch_bounds__(1 << (LOGP - 4), (sizeof(T) == 8 ? (LOGP == 12 ? CWT_LB_OLS_F64_HALF : CWT_LB_OLS_F64) : CWT_LB_AOLS_F32))
 k_aols_rows(const cplx<T>* __restrict__ xs, const RowDesc* __restrict__ rows, const T* __restrict__ gtab,
-            const cplx<T>* __restrict__ tw_all, AolsGeom g, const cplx<T>* __restrict__ xhat, long nyq, WT* __restrict__ W,
+            const cplx<T>* __restrict__ tw_all, AolsGeom g, const cplx<T>* __restrict__ xhat, long nyq, out_arg_t<WT> W,
             long ldw, long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   T* lds = reinterpret_cast<T*>(lds_raw);
@@ -574,14 +574,14 @@ k_aols_rows(const cplx<T>* __restrict__ xs, const RowDesc* __restrict__ rows, co
   const T* gt = gtab + rd.tab_off;
   const long col0 = long(blk) * L, left = ncols - col0;
   const int nlim = left < L ? int(left) : L;
-  WT* wout = W + long(rd.out_row) * ldw + col0;
+  out_ptr_t<WT> wout = W + long(rd.out_row) * ldw + col0;
   if constexpr (PAIR) {
     using F2 = ct::Fft<pairf, LOGP, 0, false>;
     const bool two = blk + 1u < unsigned(g.nblocks);
     const float2* xb1 = two ? xb + (P + 8) : xb;
     const long left1 = left - L;
     const int nlim1 = !two ? 0 : left1 < L ? int(left1) : L;
-    WT* wout1 = wout + L;
+    out_ptr_t<WT> wout1 = wout + L;
     F2 f;
     f.t = 0;
     f.j = threadIdx.x;
@@ -832,7 +832,7 @@ k_poly_coef(const cplx<T>* __restrict__ yb, const RowDesc* __restrict__ rows, co
 // complex64 outputs).  sc[i][d] = a_d[m0 + i] for the intervals m0 ... the workgroup touches.
 template <typename T, int D, typename WT>
 __device__ __forceinline__ void poly_rows_body(const RowDesc& rd, const cplx<T>* __restrict__ coef, const TwN<T>& twn,
-                                               int logN, WT* __restrict__ W, long ldw, long ncols, cplx<T>* sc) {
+                                               int logN, out_arg_t<WT> W, long ldw, long ncols, cplx<T>* sc) {
   constexpr int PT = sizeof(T) == 8 ? 1 : 2, SPAN = 256 * PT, I = POLY_PASSES, WSPAN = 64 * PT;
   static_assert((I & (I - 1)) == 0, "POLY_PASSES: a power of two (a wavefront's span must divide the interval length)");
   const int logR = logN - rd.logK;
@@ -857,7 +857,7 @@ __device__ __forceinline__ void poly_rows_body(const RowDesc& rd, const cplx<T>*
   cplx<T> adj = mk<T>(T(1), T(0));
   if constexpr (PT == 2) adj = twn(unsigned(kc) & nmask);                // e^{2 pi i k_c / N}: the lane's second output
   const T scale = T(2) / T(1u << logR);
-  WT* wrow = W + long(rd.out_row) * ldw;
+  out_ptr_t<WT> wrow = W + long(rd.out_row) * ldw;
   __syncthreads();
   T pr[I][PT], pi[I][PT], u[I][PT];
 #pragma unroll
@@ -930,7 +930,9 @@ __device__ __forceinline__ void poly_rows_body(const RowDesc& rd, const cplx<T>*
     if constexpr (PT == 1) {
       if (long(n) < ncols) store_w<T>(wrow + n, o[0].x, o[0].y);
     } else {
-      if (long(n) + 1 < ncols && ((reinterpret_cast<size_t>(wrow + n) & 15u) == 0)) {
+      if constexpr (weighted_out<WT>()) {
+        store_w_pair<T>(wrow + n, o[0], o[PT - 1], long(n) < ncols, long(n) + 1 < ncols);
+      } else if (long(n) + 1 < ncols && ((reinterpret_cast<size_t>(wrow + n) & 15u) == 0)) {
         typedef T vec4 __attribute__((vector_size(4 * sizeof(T))));
         vec4 v = {o[0].x, o[0].y, o[PT - 1].x, o[PT - 1].y};
         __builtin_nontemporal_store(v, reinterpret_cast<vec4*>(wrow + n));
@@ -967,7 +969,7 @@ __device__ __forceinline__ unsigned wave_uniform(unsigned v) {
 // scalar registers -- no staging in LDS, no workgroup barrier, no LDS reads.
 template <typename T, int D, typename WT>
 __device__ __forceinline__ void poly_rows_body_s(const RowDesc& rd, const cplx<T>* __restrict__ coef, const TwN<T>& twn,
-                                                 int logN, WT* __restrict__ W, long ldw, long ncols) {
+                                                 int logN, out_arg_t<WT> W, long ldw, long ncols) {
   constexpr int PT = sizeof(T) == 8 ? 1 : 2, SPAN = 256 * PT, I = POLY_PASSES, WSPAN = 64 * PT;
   const int logR = logN - rd.logK;
   const unsigned nmask = unsigned((1 << logN) - 1);
@@ -980,7 +982,7 @@ __device__ __forceinline__ void poly_rows_body_s(const RowDesc& rd, const cplx<T
   cplx<T> adj = mk<T>(T(1), T(0));
   if constexpr (PT == 2) adj = twn(unsigned(kc) & nmask);
   const T scale = T(2) / T(1u << logR);
-  WT* wrow = W + long(rd.out_row) * ldw;
+  out_ptr_t<WT> wrow = W + long(rd.out_row) * ldw;
   const cplx<T>* a = coef + rd.tab_off;
   T pr[I][PT], pi[I][PT], u[I][PT];
 #pragma unroll
@@ -1053,7 +1055,9 @@ __device__ __forceinline__ void poly_rows_body_s(const RowDesc& rd, const cplx<T
     if constexpr (PT == 1) {
       if (long(n) < ncols) store_w<T>(wrow + n, o[0].x, o[0].y);
     } else {
-      if (long(n) + 1 < ncols && ((reinterpret_cast<size_t>(wrow + n) & 15u) == 0)) {
+      if constexpr (weighted_out<WT>()) {
+        store_w_pair<T>(wrow + n, o[0], o[PT - 1], long(n) < ncols, long(n) + 1 < ncols);
+      } else if (long(n) + 1 < ncols && ((reinterpret_cast<size_t>(wrow + n) & 15u) == 0)) {
         typedef T vec4 __attribute__((vector_size(4 * sizeof(T))));
         vec4 v = {o[0].x, o[0].y, o[PT - 1].x, o[PT - 1].y};
         __builtin_nontemporal_store(v, reinterpret_cast<vec4*>(wrow + n));
@@ -1069,7 +1073,7 @@ __device__ __forceinline__ void poly_rows_body_s(const RowDesc& rd, const cplx<T
 template <typename T, typename WT = cplx<T>>
 __global__ void __launch_bounds__(256)
 k_poly_rows(const RowDesc* __restrict__ rows, const cplx<T>* __restrict__ coef, TwN<T> twn, int logN,
-            WT* __restrict__ W, long ldw, long ncols) {
+            out_arg_t<WT> W, long ldw, long ncols) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   cplx<T>* sc = reinterpret_cast<cplx<T>*>(lds_raw);
   const RowDesc rd = rows[blockIdx.y];

@@ -77,6 +77,59 @@ __device__ __forceinline__ void store_p2(T* p, T a, T b) {
 template <typename T, typename WT>
 constexpr bool power_out() { return sizeof(WT) == sizeof(T); }
 
+// The weighted output (cwt_transform_weighted): G[j, n] = (alpha Q[j, n]) W[j, n], the cotangent of W under a real weight on
+// its power (G = 2 gP W is what the adjoint of P = |W|^2 consumes).  WT = weighted<T> names the mode (it has the size of a
+// complex, so power_out is false and every kernel computes W -- carrier included -- as in the W mode); the kernel's output
+// handle is then not a pointer but weighted_ptr<T>: G and Q advance together, which is why they share one leading dimension,
+// and the weight alpha travels with them.  Q is read once, G written once: both streaming, as W.
+template <typename T> struct weighted { T re, im; };
+template <typename T>
+struct weighted_ptr {
+  cplx<T>* g;
+  const T* q;
+  T alpha;
+  __host__ __device__ __forceinline__ weighted_ptr operator+(long off) const { return weighted_ptr{g + off, q + off, alpha}; }
+};
+// out_ptr_t<WT>: the handle on a row kernel's output -- WT* for W and power, weighted_ptr<T> for WT = weighted<T>;
+// out_arg_t<WT>: the same as a kernel parameter (the pointers keep their __restrict__)
+template <typename WT> struct OutPtr { using type = WT*; using arg = WT* __restrict__; };
+template <typename T> struct OutPtr<weighted<T>> { using type = weighted_ptr<T>; using arg = weighted_ptr<T>; };
+template <typename WT> using out_ptr_t = typename OutPtr<WT>::type;
+template <typename WT> using out_arg_t = typename OutPtr<WT>::arg;
+// ... and back: the mode a launcher's output handle stands for
+template <typename OUT> struct OutTag;
+template <typename WT> struct OutTag<WT*> { using type = WT; };
+template <typename T> struct OutTag<weighted_ptr<T>> { using type = weighted<T>; };
+template <typename OUT> using out_tag_t = typename OutTag<OUT>::type;
+template <typename WT> struct IsWeighted { static constexpr bool value = false; };
+template <typename T> struct IsWeighted<weighted<T>> { static constexpr bool value = true; };
+template <typename WT>
+constexpr bool weighted_out() { return IsWeighted<WT>::value; }
+
+// t = alpha q once per element, then (t re, t im)
+template <typename T>
+__device__ __forceinline__ void store_w(weighted_ptr<T> p, T re, T im) {
+  const T t = p.alpha * __builtin_nontemporal_load(p.q);
+  store_w<T>(p.g, t * re, t * im);
+}
+// Two adjacent columns a, b of the weighted output (complex64 polynomial rows: a lane owns two columns): one load of the two
+// weights and one store of the two products where both columns exist and both addresses are aligned for it, else one by one.
+template <typename T>
+__device__ __forceinline__ void store_w_pair(weighted_ptr<T> p, cplx<T> a, cplx<T> b, bool have_a, bool have_b) {
+  typedef T vec2 __attribute__((vector_size(2 * sizeof(T))));
+  typedef T vec4 __attribute__((vector_size(4 * sizeof(T))));
+  if (have_a && have_b && ((reinterpret_cast<size_t>(p.g) & (4 * sizeof(T) - 1)) == 0) &&
+      ((reinterpret_cast<size_t>(p.q) & (2 * sizeof(T) - 1)) == 0)) {
+    const vec2 q = __builtin_nontemporal_load(reinterpret_cast<const vec2*>(p.q));
+    const T ta = p.alpha * q[0], tb = p.alpha * q[1];
+    vec4 v = {ta * a.x, ta * a.y, tb * b.x, tb * b.y};
+    __builtin_nontemporal_store(v, reinterpret_cast<vec4*>(p.g));
+  } else {
+    if (have_a) store_w<T>(p, a.x, a.y);
+    if (have_b) store_w<T>(p + 1, b.x, b.y);
+  }
+}
+
 // Pins a value to a register at this point of the program (an empty asm that "modifies" it): the compiler must
 // finish computing it here and may not sink the computation past later barriers.  Used where a result is produced
 // long before its use and sinking would keep many more inputs alive than outputs (narrow_phases).

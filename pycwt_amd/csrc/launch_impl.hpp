@@ -104,22 +104,22 @@ inline void narrow_class_counts(const cwt_plan* p, int* n_small_k, int* n_big, i
   if (n_many) *n_many = many;
 }
 
-template <typename T, typename WT>
-void launch_narrow_ct_many(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, WT* W, int64_t ldw,
+template <typename T, typename OUT>
+void launch_narrow_ct_many(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, OUT W, int64_t ldw,
                            int64_t ncols) {
   constexpr int LOGP = default_logp<T>();
   const int first = p->rt->narrow_groups.front().first;
   int n_small_k, n_big, n_many;
   narrow_class_counts(p, &n_small_k, &n_big, &n_many);
   for (int r0 = 0; r0 < n_many; r0 += kMaxGridY)
-    hipLaunchKernelGGL((k_narrow_ct_many<T, LOGP, WT>), dim3(1u << (p->logN - LOGP), std::min(kMaxGridY, n_many - r0)),
+    hipLaunchKernelGGL((k_narrow_ct_many<T, LOGP, out_tag_t<OUT>>), dim3(1u << (p->logN - LOGP), std::min(kMaxGridY, n_many - r0)),
                        dim3(1 << (LOGP - 4)), (size_t(1) << LOGP) * sizeof(T), p->stream, xhat,
                        p->rt->rows_dev + first + n_small_k + r0, mo, static_cast<const cplx<T>*>(p->tw_all),
                        twn_of<T>(p), p->logN, W, long(ldw), long(ncols));
 }
 
-template <typename T, typename WT>
-void launch_narrow_ct_all(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, WT* W, int64_t ldw,
+template <typename T, typename OUT>
+void launch_narrow_ct_all(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, OUT W, int64_t ldw,
                           int64_t ncols) {
   constexpr int LOGP = default_logp<T>();
   const int first = p->rt->narrow_groups.front().first;
@@ -135,27 +135,27 @@ void launch_narrow_ct_all(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, WT
       for (const auto& g : p->rt->narrow_groups) if (g.logK <= 9 && g.nterms == 1) n_half += g.count;
     n_half = std::max(n_half, n_wave);
     for (int r0 = n_wave; r0 < n_half; r0 += kMaxGridY)
-      hipLaunchKernelGGL((k_narrow_ct_all<T, LOGP - 1, WT>), dim3(1u << (p->logN - LOGP + 1), std::min(kMaxGridY, n_half - r0)),
+      hipLaunchKernelGGL((k_narrow_ct_all<T, LOGP - 1, out_tag_t<OUT>>), dim3(1u << (p->logN - LOGP + 1), std::min(kMaxGridY, n_half - r0)),
                          dim3(1 << (LOGP - 5)), (size_t(1) << (LOGP - 1)) * sizeof(T), p->stream, xhat,
                          p->rt->rows_dev + first + r0, mo, static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
                          p->logN, W, long(ldw), long(ncols));
   }
   for (int r0 = std::max(n_half, n_wave); r0 < n_small_k; r0 += kMaxGridY)
-    hipLaunchKernelGGL((k_narrow_ct_all<T, LOGP, WT>), dim3(1u << (p->logN - LOGP), std::min(kMaxGridY, n_small_k - r0)),
+    hipLaunchKernelGGL((k_narrow_ct_all<T, LOGP, out_tag_t<OUT>>), dim3(1u << (p->logN - LOGP), std::min(kMaxGridY, n_small_k - r0)),
                        dim3(1 << (LOGP - 4)), (size_t(1) << LOGP) * sizeof(T), p->stream, xhat,
                        p->rt->rows_dev + first + r0, mo, static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
                        p->logN, W, long(ldw), long(ncols));
 }
 
-template <typename T, typename WT>
-void launch_narrow_ct_big(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, WT* W, int64_t ldw,
+template <typename T, typename OUT>
+void launch_narrow_ct_big(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, OUT W, int64_t ldw,
                           int64_t ncols) {
   if constexpr (sizeof(T) == 8) {
     const int first = p->rt->narrow_groups.front().first;
     int n_small_k, n_big, n_many;
     narrow_class_counts(p, &n_small_k, &n_big, &n_many);
     for (int r0 = 0; r0 < n_big; r0 += kMaxGridY)
-      hipLaunchKernelGGL((k_narrow_ct_big<T, WT>), dim3(1u << (p->logN - 14), std::min(kMaxGridY, n_big - r0)), dim3(1024),
+      hipLaunchKernelGGL((k_narrow_ct_big<T, out_tag_t<OUT>>), dim3(1u << (p->logN - 14), std::min(kMaxGridY, n_big - r0)), dim3(1024),
                          (size_t(1) << 14) * sizeof(T), p->stream, xhat, p->rt->rows_dev + first + n_small_k + n_many + r0, mo,
                          static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p), p->logN, W, long(ldw), long(ncols));
   }
@@ -242,17 +242,17 @@ bool try_pass_a_ct(cwt_plan* p, int logR, const void* in, const RowDesc* rows, i
 #undef CWT_CASE
 }
 
-template <typename T, int LOGK, int LP, bool CONJ, typename WT>
-void launch_pass_b_ct_lp(cwt_plan* p, const RowDesc* rows, int cnt, WT* W, int64_t ldw, int64_t ncols,
+template <typename T, int LOGK, int LP, bool CONJ, typename OUT>
+void launch_pass_b_ct_lp(cwt_plan* p, const RowDesc* rows, int cnt, OUT W, int64_t ldw, int64_t ncols,
                          const cplx<T>* Z, hipStream_t st) {
   const size_t lds = ((size_t(1) << LP) + (size_t(1) << (LP - 4))) * sizeof(T);
   const dim3 grid(1u << (p->logN - LP), cnt), block(1 << (LP - 4));
-  hipLaunchKernelGGL((k_pass_b_ct<T, LOGK, LP, CONJ, WT>), grid, block, lds, st, Z, rows, tw_table<T>(p, LOGK),
+  hipLaunchKernelGGL((k_pass_b_ct<T, LOGK, LP, CONJ, out_tag_t<OUT>>), grid, block, lds, st, Z, rows, tw_table<T>(p, LOGK),
                      twn_of<T>(p), p->logN, W, long(ldw), long(ncols));
 }
 
-template <typename T, int LOGK, bool CONJ, typename WT>
-void launch_pass_b_ct(cwt_plan* p, const RowDesc* rows, int cnt, WT* W, int64_t ldw, int64_t ncols,
+template <typename T, int LOGK, bool CONJ, typename OUT>
+void launch_pass_b_ct(cwt_plan* p, const RowDesc* rows, int cnt, OUT W, int64_t ldw, int64_t ncols,
                       const cplx<T>* Z, hipStream_t st) {
   constexpr int LOGP = default_logp<T>();
   if constexpr (CONJ && LOGK <= LOGP - 1) {
@@ -262,8 +262,8 @@ void launch_pass_b_ct(cwt_plan* p, const RowDesc* rows, int cnt, WT* W, int64_t 
 }
 
 // Compile-time pass B for row lengths K = 2^9 .. 2^12 (K = 1024 for every N from 2^14 to 2^22).
-template <typename T, bool CONJ, typename WT>
-bool try_pass_b_ct(cwt_plan* p, int logK, const RowDesc* rows, int cnt, WT* W, int64_t ldw,
+template <typename T, bool CONJ, typename OUT>
+bool try_pass_b_ct(cwt_plan* p, int logK, const RowDesc* rows, int cnt, OUT W, int64_t ldw,
                    int64_t ncols, const cplx<T>* Z, hipStream_t st) {
   if (!default_tile_ct(p)) return false;
   switch (logK) {
@@ -369,25 +369,25 @@ int launch_ols_fwd(cwt_plan* p, const void* x_dev, int64_t n0, hipStream_t st, i
 }
 // ... and the rows themselves (k_ols_ct)
 // part: -1 = every class of the group in one launch, 0 = the classes on blocks of one tile, 1 = the classes on longer blocks
-template <typename T, int LOGP, typename WT>
-int launch_ols_rows_p(cwt_plan* p, int g, WT* W, int64_t ldw, int64_t ncols, hipStream_t st, int part = -1) {
+template <typename T, int LOGP, typename OUT>
+int launch_ols_rows_p(cwt_plan* p, int g, OUT W, int64_t ldw, int64_t ncols, hipStream_t st, int part = -1) {
   const cwt_plan::RowTable* rt = p->rt;
   const auto& G = rt->ols_grp[g];
   const long first = part == 1 ? G.wgs_base : 0, count = part == 0 ? G.wgs_base : G.wgs - first;
   if (count <= 0) return CWT_OK;
-  static const bool once = (allow_big_lds(&k_ols_ct<T, LOGP, WT>), true);
+  static const bool once = (allow_big_lds(&k_ols_ct<T, LOGP, out_tag_t<OUT>>), true);
   (void)once;
   // (complex64: two blocks per workgroup, 8-byte exchange elements)
   const size_t lds = ((size_t(1) << LOGP) + (size_t(1) << (LOGP - 4))) * (ols_pairs(sizeof(T), LOGP) ? sizeof(pairf) : sizeof(T));
   return timed_launch(p, g == 0 ? KC_OLS_SMALL : KC_OLS, [&] {
-    hipLaunchKernelGGL((k_ols_ct<T, LOGP, WT>), dim3(unsigned(count)), dim3(1 << (LOGP - 4)), lds, st,
+    hipLaunchKernelGGL((k_ols_ct<T, LOGP, out_tag_t<OUT>>), dim3(unsigned(count)), dim3(1 << (LOGP - 4)), lds, st,
                        static_cast<const cplx<T>*>(p->xs), rt->rows_dev + rt->ols_first + G.row_first,
                        static_cast<const cplx<T>*>(rt->gt_dev), static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
                        p->logN, G.cls, W, long(ldw), long(ncols), unsigned(first));
   }, st);
 }
-template <typename T, typename WT>
-int launch_ols_rows(cwt_plan* p, WT* W, int64_t ldw, int64_t ncols, hipStream_t st, int g_only = -1, int part = -1) {
+template <typename T, typename OUT>
+int launch_ols_rows(cwt_plan* p, OUT W, int64_t ldw, int64_t ncols, hipStream_t st, int g_only = -1, int part = -1) {
   int rc = CWT_OK;
   for (int g = 0; g < 2 && !rc; ++g) {        // the half-size tiles first (by far the longer launch since the rows with long
                                               // halos went to the polynomial form), then the default tile's rows
@@ -406,8 +406,8 @@ int launch_ols_rows(cwt_plan* p, WT* W, int64_t ldw, int64_t ncols, hipStream_t 
 // (the mask is the pseudo-row at aux_first: profile 1), its block spectra, then every (block, row) pair.
 // phase: 0 = everything on st; the serial schedule (one signal) splits it in two: 1 = the band-passed signal and its block
 // spectra on st, `ready` recorded behind them, 2 = the rows on st, which the caller has made wait for `ready`
-template <typename T, int LOGP, typename WT>
-int launch_aols_p(cwt_plan* p, const void* xhat_dev, WT* W, int64_t ldw, int64_t ncols, hipStream_t st, int phase = 0,
+template <typename T, int LOGP, typename OUT>
+int launch_aols_p(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, int64_t ncols, hipStream_t st, int phase = 0,
                   hipEvent_t ready = nullptr) {
   const cwt_plan::RowTable* rt = p->rt;
   const AolsGeom& g = rt->aols_geom;
@@ -425,7 +425,7 @@ int launch_aols_p(cwt_plan* p, const void* xhat_dev, WT* W, int64_t ldw, int64_t
   one.kind = MOTHER_DOG; one.m = 0; one.p = 0.0; one.table = nullptr;       // profile(0 * k) = 1
   cplx<T>* Z = static_cast<cplx<T>*>(p->Z);
   cplx<T>* xm = static_cast<cplx<T>*>(p->xm);
-  static const bool once = (allow_big_lds(&k_aols_fwd<T, LOGP>), allow_big_lds(&k_aols_rows<T, LOGP, WT>), true);
+  static const bool once = (allow_big_lds(&k_aols_fwd<T, LOGP>), allow_big_lds(&k_aols_rows<T, LOGP, out_tag_t<OUT>>), true);
   (void)once;
   const size_t lds = ((size_t(1) << LOGP) + (size_t(1) << (LOGP - 4))) * sizeof(T);
   const size_t lds_rows = aols_pairs(sizeof(T)) ? 2 * lds : lds;      // complex64 rows: two blocks per workgroup
@@ -452,7 +452,7 @@ int launch_aols_p(cwt_plan* p, const void* xhat_dev, WT* W, int64_t ldw, int64_t
       return rc;
     }
     if (!rc) rc = timed_launch(p, KC_AOLS, [&] {
-      hipLaunchKernelGGL((k_aols_rows<T, LOGP, WT>), dim3(unsigned(rt->aols_wgs), unsigned(cnt)), dim3(1 << (LOGP - 4)), lds_rows, st,
+      hipLaunchKernelGGL((k_aols_rows<T, LOGP, out_tag_t<OUT>>), dim3(unsigned(rt->aols_wgs), unsigned(cnt)), dim3(1 << (LOGP - 4)), lds_rows, st,
                          static_cast<const cplx<T>*>(p->xsa), rt->rows_dev + rt->aols_first + long(b0) * g.nrows,
                          static_cast<const T*>(rt->agt_dev), static_cast<const cplx<T>*>(p->tw_all), g,
                          static_cast<const cplx<T>*>(xhat_dev), long(p->N >> 1), W, long(ldw), long(ncols));
@@ -463,14 +463,14 @@ int launch_aols_p(cwt_plan* p, const void* xhat_dev, WT* W, int64_t ldw, int64_t
 }
 // The second class of such rows (Paul continued through f = 0, 8192-point tiles; one signal): block spectra of the SAME
 // band-passed signal on its own block grid, then its rows -- on the stream of the first class, behind it (both use p->xsa).
-template <typename T, typename WT>
-int launch_aols_second(cwt_plan* p, const void* xhat_dev, WT* W, int64_t ldw, int64_t ncols, hipStream_t st) {
+template <typename T, typename OUT>
+int launch_aols_second(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, int64_t ncols, hipStream_t st) {
   const cwt_plan::RowTable* rt = p->rt;
   const AolsGeom& g = rt->aols2_geom;
   constexpr int LOGP = 13, P = 1 << LOGP;
   int rc = grow(&p->xsa, &p->xsa_bytes, size_t(g.nblocks) * size_t(P + 8) * sizeof(cplx<T>), st);
   if (rc) return rc;
-  static const bool once = (allow_big_lds(&k_aols_fwd<T, LOGP>), allow_big_lds(&k_aols_rows<T, LOGP, WT>), true);
+  static const bool once = (allow_big_lds(&k_aols_fwd<T, LOGP>), allow_big_lds(&k_aols_rows<T, LOGP, out_tag_t<OUT>>), true);
   (void)once;
   const size_t lds = ((size_t(1) << LOGP) + (size_t(1) << (LOGP - 4))) * sizeof(T);
   rc = timed_launch(p, KC_AOLS_PRE, [&] {
@@ -479,7 +479,7 @@ int launch_aols_second(cwt_plan* p, const void* xhat_dev, WT* W, int64_t ldw, in
                        static_cast<cplx<T>*>(p->xsa));
   }, st);
   if (!rc) rc = timed_launch(p, KC_AOLS, [&] {
-    hipLaunchKernelGGL((k_aols_rows<T, LOGP, WT>), dim3(unsigned(rt->aols2_wgs), 1u), dim3(1 << (LOGP - 4)),
+    hipLaunchKernelGGL((k_aols_rows<T, LOGP, out_tag_t<OUT>>), dim3(unsigned(rt->aols2_wgs), 1u), dim3(1 << (LOGP - 4)),
                        aols_pairs(sizeof(T)) ? 2 * lds : lds, st,
                        static_cast<const cplx<T>*>(p->xsa), rt->rows_dev + rt->aols2_first, static_cast<const T*>(rt->agt_dev),
                        static_cast<const cplx<T>*>(p->tw_all), g, static_cast<const cplx<T>*>(xhat_dev), long(p->N >> 1), W,
@@ -487,8 +487,8 @@ int launch_aols_second(cwt_plan* p, const void* xhat_dev, WT* W, int64_t ldw, in
   }, st);
   return rc;
 }
-template <typename T, typename WT>
-int launch_aols(cwt_plan* p, const void* xhat_dev, WT* W, int64_t ldw, int64_t ncols, hipStream_t st, int phase = 0,
+template <typename T, typename OUT>
+int launch_aols(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, int64_t ncols, hipStream_t st, int phase = 0,
                 hipEvent_t ready = nullptr) {
   int rc = CWT_OK;
   switch (p->rt->aols_logp) {
@@ -548,8 +548,8 @@ int launch_poly_coef(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, int chu
   return rc;
 }
 // ... then the streaming kernel (k_poly_rows) over the rows of the chunk
-template <typename T, typename WT>
-int launch_poly_rows(cwt_plan* p, int chunk, WT* W, int64_t ldw, int64_t ncols, hipStream_t st) {
+template <typename T, typename OUT>
+int launch_poly_rows(cwt_plan* p, int chunk, OUT W, int64_t ldw, int64_t ncols, hipStream_t st) {
   const cwt_plan::RowTable* rt = p->rt;
   const auto& ch = rt->poly_chunks[size_t(chunk)];
   const RowDesc* rows = rt->rows_dev + rt->poly_first + ch.row_first;
@@ -559,14 +559,14 @@ int launch_poly_rows(cwt_plan* p, int chunk, WT* W, int64_t ldw, int64_t ncols, 
   const size_t lds2 = size_t((per_wg >> POLY_MIN_LOGR) + 2) * (POLY_MAX_DEGREE + 1) * sizeof(cplx<T>);
   return timed_launch(p, KC_POLY, [&] {
     for (int r0 = 0; r0 < ch.nrows; r0 += kMaxGridY)
-      hipLaunchKernelGGL((k_poly_rows<T, WT>), dim3(unsigned((ncols + per_wg - 1) / per_wg), std::min(kMaxGridY, ch.nrows - r0)),
+      hipLaunchKernelGGL((k_poly_rows<T, out_tag_t<OUT>>), dim3(unsigned((ncols + per_wg - 1) / per_wg), std::min(kMaxGridY, ch.nrows - r0)),
                          dim3(256), lds2, st, rows + r0, coef, twn_of<T>(p), p->logN, W, long(ldw), long(ncols));
   }, st);
 }
 
 // Two-pass rows (forms T), chunk by chunk on the plan's stream through the one intermediate buffer.
-template <typename T, typename WT>
-int launch_wide_rows(cwt_plan* p, const void* xhat_dev, const Mother& mo, WT* W, int64_t ldw, int64_t ncols) {
+template <typename T, typename OUT>
+int launch_wide_rows(cwt_plan* p, const void* xhat_dev, const Mother& mo, OUT W, int64_t ldw, int64_t ncols) {
   const int logN = p->logN, logP = std::min(p->log_wg_points, logN), threads = 1 << (logP - 4);
   const size_t lds = (size_t(1) << logP) * sizeof(T);
   const int logK = two_pass_logk(p), logR = logN - logK;
@@ -586,7 +586,7 @@ int launch_wide_rows(cwt_plan* p, const void* xhat_dev, const Mother& mo, WT* W,
     if (rc) return rc;
     rc = timed_launch(p, KC_PASS_B, [&] {
       if (try_pass_b_ct<T, false>(p, logK, rows, cnt, W, ldw, ncols, Z, p->stream)) return;
-      hipLaunchKernelGGL((k_pass_b<T, false, WT>), dim3(1u << (logN - logP), cnt), dim3(threads), lds, p->stream,
+      hipLaunchKernelGGL((k_pass_b<T, false, out_tag_t<OUT>>), dim3(1u << (logN - logP), cnt), dim3(threads), lds, p->stream,
                          static_cast<const cplx<T>*>(Z), rows, tw_table<T>(p, logK), twn_of<T>(p), logN, logK,
                          logP - logK, W, long(ldw), long(ncols));
     });
@@ -663,8 +663,8 @@ int launch_ols_early(cwt_plan* p, const void* x_dev, int64_t n0, bool first_on_m
 }
 
 // Step 3.  spectrum_ready: recorded behind a forward FFT on side stream 0; nullptr: the spectrum is on the caller's stream.
-template <typename T, typename WT>
-int rows_launch_serial_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, WT* W, int64_t ldw, int64_t ncols,
+template <typename T, typename OUT>
+int rows_launch_serial_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, OUT W, int64_t ldw, int64_t ncols,
                            hipEvent_t spectrum_ready) {
   const cwt_plan::RowTable* rt = p->rt;
   const cplx<T>* xhat = static_cast<const cplx<T>*>(xhat_dev);
@@ -729,10 +729,18 @@ int rows_launch_serial_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, 
   return rc;
 }
 
-// The call's output (p->call.power) picks the instantiation of every row kernel: W, or its power as reals
+// The output handle of a weighted call (p->call.weighted): G, the weights Q at the same element offsets, and alpha
+template <typename T>
+weighted_ptr<T> weighted_handle(const cwt_plan* p, void* G_dev) {
+  return weighted_ptr<T>{static_cast<cplx<T>*>(G_dev), static_cast<const T*>(p->call.q), T(p->call.alpha)};
+}
+
+// The call's output (p->call.power, p->call.weighted) picks the instantiation of every row kernel: W, its power as reals, or
+// W under the weights alpha Q
 template <typename T>
 int rows_launch_serial(cwt_plan* p, const void* xhat_dev, const Mother& mo, void* W_dev, int64_t ldw, int64_t ncols,
                        hipEvent_t spectrum_ready) {
+  if (p->call.weighted) return rows_launch_serial_out<T>(p, xhat_dev, mo, weighted_handle<T>(p, W_dev), ldw, ncols, spectrum_ready);
   if (p->call.power) return rows_launch_serial_out<T>(p, xhat_dev, mo, static_cast<T*>(W_dev), ldw, ncols, spectrum_ready);
   return rows_launch_serial_out<T>(p, xhat_dev, mo, static_cast<cplx<T>*>(W_dev), ldw, ncols, spectrum_ready);
 }
@@ -765,8 +773,8 @@ int transform_serial(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev,
 
 // ---- the round-5 schedule (serial_rows = 0, complex64 default; and every call the serial schedule does not take) ---------------
 // ols_early: cwt_transform has queued the block spectra of the overlap-save rows (launch_ols_early)
-template <typename T, typename WT>
-int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, WT* W, int64_t ldw, int64_t ncols,
+template <typename T, typename OUT>
+int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, OUT W, int64_t ldw, int64_t ncols,
                     const void* x_dev, int64_t n0, bool ols_early) {
   const int logN = p->logN;
   const cplx<T>* xhat = static_cast<const cplx<T>*>(xhat_dev);
@@ -775,7 +783,7 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
     if (logN <= 3) {
       const int total = nrows << logN;
       return timed_launch(p, KC_DIRECT, [&] {
-        hipLaunchKernelGGL((k_direct<T, IN_SPECTRUM, WT>), dim3((total + 63) / 64), dim3(64), 0, p->stream,
+        hipLaunchKernelGGL((k_direct<T, IN_SPECTRUM, out_tag_t<OUT>>), dim3((total + 63) / 64), dim3(64), 0, p->stream,
                            xhat_dev, p->rt->rows_dev, nrows, mo, logN, 0L, 0L, W, long(ldw), long(ncols));
       });
     }
@@ -785,7 +793,7 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
     const int threads = TB << (logN - 4);
     const size_t lds = (size_t(TB) << logN) * sizeof(T);
     return timed_launch(p, KC_SMALL, [&] {
-      hipLaunchKernelGGL((k_small<T, IN_SPECTRUM, WT>), dim3((nrows + TB - 1) / TB), dim3(threads), lds,
+      hipLaunchKernelGGL((k_small<T, IN_SPECTRUM, out_tag_t<OUT>>), dim3((nrows + TB - 1) / TB), dim3(threads), lds,
                          p->stream, xhat_dev, p->rt->rows_dev, nrows, mo, tw_table<T>(p, logN), logN, logTB,
                          0L, 0L, W, long(ldw), long(ncols));
     });
@@ -900,7 +908,7 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
       for (const auto& g : p->rt->narrow_groups) {
         rc = timed_launch(p, KC_NARROW, [&] {
           for (int r0 = 0; r0 < g.count; r0 += kMaxGridY)
-            hipLaunchKernelGGL((k_narrow<T, WT>), dim3(1u << (logN - logP), std::min(kMaxGridY, g.count - r0)),
+            hipLaunchKernelGGL((k_narrow<T, out_tag_t<OUT>>), dim3(1u << (logN - logP), std::min(kMaxGridY, g.count - r0)),
                                dim3(threads), lds, p->stream, xhat, p->rt->rows_dev + g.first + r0, mo,
                                tw_table<T>(p, g.logK), twn_of<T>(p), logN, g.logK, logP - g.logK, W, long(ldw),
                                long(ncols));
@@ -916,6 +924,7 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
 template <typename T>
 int rows_launch(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw, int64_t ncols,
                 const void* x_dev, int64_t n0, bool ols_early) {
+  if (p->call.weighted) return rows_launch_out<T>(p, xhat_dev, mo, nrows, weighted_handle<T>(p, W_dev), ldw, ncols, x_dev, n0, ols_early);
   if (p->call.power) return rows_launch_out<T>(p, xhat_dev, mo, nrows, static_cast<T*>(W_dev), ldw, ncols, x_dev, n0, ols_early);
   return rows_launch_out<T>(p, xhat_dev, mo, nrows, static_cast<cplx<T>*>(W_dev), ldw, ncols, x_dev, n0, ols_early);
 }
@@ -962,12 +971,16 @@ int set_func_attrs() {
                        reinterpret_cast<const void*>(&k_pass_b<T, false>),
                        reinterpret_cast<const void*>(&k_small<T, IN_SPECTRUM, T>),
                        reinterpret_cast<const void*>(&k_narrow<T, T>),
-                       reinterpret_cast<const void*>(&k_pass_b<T, false, T>)};
+                       reinterpret_cast<const void*>(&k_pass_b<T, false, T>),
+                       reinterpret_cast<const void*>(&k_small<T, IN_SPECTRUM, weighted<T>>),
+                       reinterpret_cast<const void*>(&k_narrow<T, weighted<T>>),
+                       reinterpret_cast<const void*>(&k_pass_b<T, false, weighted<T>>)};
   for (const void* f : fns)
     if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess)
       (void)hipGetLastError();
   for (const void* f : {reinterpret_cast<const void*>(&k_narrow_ct_big<double>),
-                        reinterpret_cast<const void*>(&k_narrow_ct_big<double, double>)})
+                        reinterpret_cast<const void*>(&k_narrow_ct_big<double, double>),
+                        reinterpret_cast<const void*>(&k_narrow_ct_big<double, weighted<double>>)})
     if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess)
       (void)hipGetLastError();
   return CWT_OK;

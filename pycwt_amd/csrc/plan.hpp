@@ -84,6 +84,9 @@ struct cwt_plan {
     int fft_small = 0;                     // the serial schedule's forward FFT, queued on side stream 0, takes half-size tiles
     int64_t ols_x_ld = 0;                  // cwt_transform_batch: elements between the signals of the batch
     int power = 0;                         // the *_power entry points: the row kernels write |W|^2 as reals, not W
+    int weighted = 0;                      // the *_weighted entry points: the row kernels write (alpha Q) W, Q read at the store's [j, n]
+    const void* q = nullptr;               // ... Q (reals of the plan's precision, the leading dimension and batch stride of the output)
+    double alpha = 0.0;
   };
   Call call;
   // options

@@ -117,6 +117,36 @@ class HipEngine:
             self.plan.transform_batch(x.data_ptr(), x.shape[0], x.shape[1], n0, kind, param, dt, sj, xhat.data_ptr(),
                                       W.data_ptr(), W.shape[-1], ncols)
 
+    def _spectra(self, x, like):
+        """Scratch spectra of a batch (cwt_transform_batch* want them): complex of x's precision on its device."""
+        cplx_t = self.torch.complex128 if x.dtype == self.torch.float64 else self.torch.complex64
+        return self.torch.empty((x.shape[0], self.plan.nfft), dtype=cplx_t, device=like.device)
+
+    def transform_power(self, x, n0, xhat, kind, param, dt, sj, P, ncols):
+        """`transform` writing |W|^2 as reals: P (rows, ld) for x (n0,), (batch, rows, ld) for x (batch, n0)."""
+        if x.dim() == 1:
+            self.plan.transform_power(x.data_ptr(), n0, kind, param, dt, sj, None if xhat is None else xhat.data_ptr(),
+                                      P.data_ptr(), P.shape[-1], ncols)
+        else:
+            if xhat is None:
+                xhat = self._spectra(x, P)
+            self.plan.transform_batch_power(x.data_ptr(), x.shape[0], x.shape[1], n0, kind, param, dt, sj, xhat.data_ptr(),
+                                            P.data_ptr(), P.shape[-1], ncols)
+
+    def transform_weighted(self, x, n0, xhat, kind, param, dt, sj, Q, alpha, G, ncols):
+        """`transform` writing G = (alpha Q) W: Q real and G complex of ONE shape, (rows, ld) or (batch, rows, ld), both
+        contiguous (they share the leading dimension and the batch stride)."""
+        if tuple(Q.shape) != tuple(G.shape) or not Q.is_contiguous() or not G.is_contiguous():
+            raise ValueError("transform_weighted: Q and G must be contiguous and of one shape")
+        if x.dim() == 1:
+            self.plan.transform_weighted(x.data_ptr(), n0, kind, param, dt, sj, None if xhat is None else xhat.data_ptr(),
+                                         Q.data_ptr(), alpha, G.data_ptr(), G.shape[-1], ncols)
+        else:
+            if xhat is None:
+                xhat = self._spectra(x, G)
+            self.plan.transform_batch_weighted(x.data_ptr(), x.shape[0], x.shape[1], n0, kind, param, dt, sj, xhat.data_ptr(),
+                                               Q.data_ptr(), alpha, G.data_ptr(), G.shape[-1], ncols)
+
     def classify(self, kind, param, dt, sj, ncols):
         return self.plan.classify(kind, param, dt, sj, ncols, True)
 
