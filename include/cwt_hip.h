@@ -142,6 +142,8 @@ int cwt_plan_set_stream(cwt_plan* plan, void* hip_stream);
  *                  0 for precision 32 (+-0 / +1.4 %).  1 and 3 have left the sources: setting them fails
  *   "adjoint_poly" 0 = cwt_adjoint_rows takes every row through its general path (default 1: the polynomial rows through the
  *                  transpose of their form)
+ *   "hop_fuse_terms" cwt_transform_hop: rows with at most this many aliases per folded bin fold their band inside the row kernel
+ *                  (default 1); 0 = every row through the fold kernel and plan scratch.  The results have the same bits
  *   "poly_carrier" 0 = the carrier of a polynomial row is the centre bin of its band (default 1: the bin, of 15 candidates, at which
  *                  the filter-weighted degree bound is lowest -- for a lopsided filter (Paul, DOG) near its peak: half the
  *                  intervals at the same degree; fp64 Paul: coefficient planes 143 -> 73 MB)
@@ -318,6 +320,53 @@ int cwt_transform_weighted(cwt_plan* plan, const void* x_dev, int64_t n0, int mo
 int cwt_transform_batch_weighted(cwt_plan* plan, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother,
                                  double param, double dt, const double* scales_host, int nrows, void* xhat_dev,
                                  const void* Q_dev, double alpha, void* G_dev, int64_t ld, int64_t ncols);
+
+/* ---- decimated output: every hop-th column of W, and nothing else ------------------------------------------------------------
+ * For callers that slice or pool W straight away (a scalogram image, a loss on a coarse time grid).  Sampling in time is
+ * folding in frequency: with h = hop (a power of two) and M = nfft / h,
+ *   W[j, m h] = (1/nfft) sum_{k' < M} Z_j[k'] exp(+2 pi i k' m / M),    Z_j[k'] = sum_{r < h} xhat[k' + r M] F_j[k' + r M],
+ * F_j the filter of cwt_transform_rows.  Per row: one pass over the filter's support band (Paul one-sided, DOG two-sided with
+ * its Nyquist bin, Morlet and Paul clipped at Nyquist at small scales -- the bins cwt_transform_rows uses, no truncation beyond
+ * them and none of the fast forms), one M-point inverse transform in a workgroup, M stores.  Nothing of nrows x n0 elements is
+ * written or kept.  The result is a SAMPLE of W -- column m equals column m h of cwt_transform_rows to rounding -- not an
+ * average over the hop: choosing h against the smallest scale is the caller's business.
+ *   hop       a power of two >= 2 with 16 <= nfft / hop <= 4096.  M > 4096 (a fold to scratch followed by a two-pass
+ *             transform) is NOT BUILT; a hop offset other than 0 neither.
+ *   ncols_h   must be ceil(n0 / hop): the columns m with m hop < n0; only they are written.  Columns ncols_h .. ld - 1 and rows
+ *             not asked for are left untouched.
+ *   output    0: W (complex), 1: |W|^2 (reals), 2: (alpha Q) W (complex; Q_dev reals of shape nbatch x nrows x ld on the ONE
+ *             leading dimension ld of out_dev, as in cwt_transform_weighted; Q_dev and alpha are ignored otherwise).
+ *   nbatch    signals (signal b at x_dev + b x_ld, its rows at out_dev + b nrows ld elements, its spectrum -- written by the
+ *             call -- at xhat_dev + b nfft); nbatch = 1 is the single-signal call.  xhat_dev may be NULL (plan scratch).
+ * The aliases of a folded bin are summed in one fixed order that depends on (nfft, hop) alone: a signal's bits do not depend
+ * on the batch around it or on the launch geometry.  The row table and its cache entry are those of cwt_transform for the same
+ * scales and n0 columns; hop and the output mode are state of the call only.  Everything goes through the spectrum: one NaN
+ * or inf sample makes every element of that signal's rows NaN, as in the two-call path.  Built-in mothers only; no Bluestein
+ * lengths, no filter banks of the caller's.  Refused with CWT_EINVAL before anything is queued: a hop that is not a power of
+ * two or < 2, nfft / hop outside [16, 4096], ncols_h != ceil(n0 / hop), ld < ncols_h, NULL pointers, Q overlapping the
+ * output, nbatch * nrows > max_rows, nrows > 32768.  Option "hop_fuse_terms" (default 1): rows with at most this many aliases per folded bin
+ * fold their band inside the transform kernel; the others go through a fold kernel gridded over (bins, row, signal) -- bounded
+ * work per thread whatever the support -- and nrows x M complex of plan scratch per signal (0 = every row).  Either way the
+ * same bits.                                                                                                               */
+int cwt_transform_hop(cwt_plan* plan, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother, double param,
+                      double dt, const double* scales_host, int nrows, int64_t hop, void* xhat_dev, int output, void* out_dev,
+                      const void* Q_dev, double alpha, int64_t ld, int64_t ncols_h);
+/* The same from spectra already on the device (signal b at xhat_dev + b xhat_ld, xhat_ld >= nfft; n0 = the length of the
+ * signals they came from), output 0 or 1 only: bit-identical to cwt_transform_hop on those signals.                      */
+int cwt_transform_rows_hop(cwt_plan* plan, const void* xhat_dev, int nbatch, int64_t xhat_ld, int64_t n0, int mother,
+                           double param, double dt, const double* scales_host, int nrows, int64_t hop, int output,
+                           void* out_dev, int64_t ld, int64_t ncols_h);
+/* Adjoint of the decimated rows: with A_h the linear map x -> W[:, ::hop] above (zero padding to nfft included),
+ *   xbar = Re A_h^H G,   so that Re sum_{j,m} conj(G[j, m]) (A_h x)[j, m] = sum_n x[n] xbar[n] for every real x.
+ * The transpose of decimation is periodisation of the spectrum: the nfft-point transform of a row that is zero between its kept
+ * columns is its M-point transform read at k mod M.  Per signal: M-point transforms of the rows of G, one accumulation over
+ * the bins of every row's support (fixed row order, no floating-point atomics: the same bits on every run, whatever the
+ * batch), the nfft-point transform of the accumulator and the trim to n0 of cwt_adjoint_rows.  Every row takes this path.
+ * G_dev: nbatch x nrows x ldg complex (signal b at G_dev + b g_batch_ld), the first ncols_h = ceil(n0 / hop) columns read;
+ * xbar_dev: nbatch x xbar_ld reals, the first n0 written, or added to with accumulate = 1.  The checks of cwt_transform_hop. */
+int cwt_adjoint_rows_hop(cwt_plan* plan, const void* G_dev, int nbatch, int64_t g_batch_ld, int64_t ldg, int64_t ncols_h,
+                         int64_t hop, int64_t n0, int mother, double param, double dt, const double* scales_host, int nrows,
+                         void* xbar_dev, int64_t xbar_ld, int accumulate);
 
 /* The same two steps at a transform length n0 that is NOT a power of two -- what the reference computes when pyfftw is
  * installed: helpers.py:15-19 then passes n = len(signal), i.e. no zero padding and circular edges -- by Bluestein's

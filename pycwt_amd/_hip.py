@@ -57,6 +57,12 @@ SYMBOLS = [
                                                C.POINTER(C.c_double), C.c_int, _P, _P, C.c_double, _P, C.c_int64, C.c_int64]),
     ("cwt_adjoint_rows", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double,
                                    C.POINTER(C.c_double), C.c_int, _P, C.c_int64, C.c_int]),
+    ("cwt_transform_hop", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double),
+                                    C.c_int, C.c_int64, _P, C.c_int, _P, _P, C.c_double, C.c_int64, C.c_int64]),
+    ("cwt_transform_rows_hop", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double,
+                                         C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_int, _P, C.c_int64, C.c_int64]),
+    ("cwt_adjoint_rows_hop", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double,
+                                       C.c_double, C.POINTER(C.c_double), C.c_int, _P, C.c_int64, C.c_int]),
     ("cwt_forward_fft_n", C.c_int, [_P, _P, C.c_int64, _P]),
     ("cwt_transform_rows_n", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double),
                                        C.c_int, _P, C.c_int64]),
@@ -472,6 +478,37 @@ class Plan:
         self.lib.check(self.lib.cwt_adjoint_rows(self.h, _P(G_dev), nbatch, g_batch_ld, ldg, ncols, mother, float(param),
                                                  float(dt), _dptr(s), s.size, _P(xbar_dev), xbar_ld, int(bool(accumulate))))
 
+    # -- decimated output: every hop-th column (ceil(n0 / hop) of them) of W, its power or its weighted form --
+    OUT_W, OUT_POWER, OUT_WEIGHTED = 0, 1, 2
+
+    @_locked
+    def transform_hop(self, x_dev: int, nbatch: int, x_ld: int, n0: int, mother: int, param: float, dt: float, scales, hop: int,
+                      xhat_dev, output: int, out_dev: int, ld: int, Q_dev=None, alpha: float = 0.0):
+        """Columns ::hop of the transform of nbatch signals (cwt_transform_hop): out nbatch x nrows x ld, complex for output
+        0 (W) and 2 ((alpha Q) W, Q_dev reals of the same shape), reals for 1 (|W|^2).  xhat_dev = None: plan scratch."""
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        self.lib.check(self.lib.cwt_transform_hop(self.h, _P(x_dev), nbatch, x_ld, n0, mother, float(param), float(dt), _dptr(s),
+                                                  s.size, hop, _P(xhat_dev) if xhat_dev else None, output, _P(out_dev),
+                                                  _P(Q_dev) if Q_dev else None, float(alpha), ld, -(-n0 // hop)))
+
+    @_locked
+    def transform_rows_hop(self, xhat_dev: int, nbatch: int, xhat_ld: int, n0: int, mother: int, param: float, dt: float, scales,
+                           hop: int, output: int, out_dev: int, ld: int):
+        """`transform_hop` from spectra on the device (cwt_transform_rows_hop; output 0 or 1)."""
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        self.lib.check(self.lib.cwt_transform_rows_hop(self.h, _P(xhat_dev), nbatch, xhat_ld, n0, mother, float(param), float(dt),
+                                                       _dptr(s), s.size, hop, output, _P(out_dev), ld, -(-n0 // hop)))
+
+    @_locked
+    def adjoint_rows_hop(self, G_dev: int, nbatch: int, g_batch_ld: int, ldg: int, hop: int, n0: int, mother: int, param: float,
+                         dt: float, scales, xbar_dev: int, xbar_ld: int, accumulate: bool = False):
+        """xbar = Re A_h^H G of the decimated rows (cwt_adjoint_rows_hop): G nbatch x nrows x ldg complex with ceil(n0 / hop)
+        columns read, xbar nbatch x xbar_ld reals with n0 written (added to with accumulate=True)."""
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        self.lib.check(self.lib.cwt_adjoint_rows_hop(self.h, _P(G_dev), nbatch, g_batch_ld, ldg, -(-n0 // hop), hop, n0, mother,
+                                                     float(param), float(dt), _dptr(s), s.size, _P(xbar_dev), xbar_ld,
+                                                     int(bool(accumulate))))
+
     @_locked
     def forward_fft_n(self, x_dev: int, n0: int, xhat_dev: int):
         """Forward transform at length n0 (not a power of two; this plan's nfft >= 2*n0 - 1)."""
@@ -605,7 +642,7 @@ class Plan:
 
     @_locked
     def timings(self):
-        cap = 16
+        cap = 32
         names = (C.c_char_p * cap)()
         ms = (C.c_double * cap)()
         cnt = (C.c_int * cap)()

@@ -365,7 +365,7 @@ int cwt_plan_destroy(cwt_plan* p) {
   for (auto& t : p->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   for (auto e : p->free_events) (void)hipEventDestroy(e);
   void* bufs[] = {p->tw_all, p->twn_lo, p->weights_dev, p->Z, p->xs, p->xm, p->xsa, p->pcoef, p->pband, p->range_dev, p->hx, p->hxhat, p->hW,
-                  p->bs_khat[0], p->bs_khat[1], p->bs_a, p->bs_spec, p->bs_par, p->adj_spec, p->adj_acc};
+                  p->bs_khat[0], p->bs_khat[1], p->bs_a, p->bs_spec, p->bs_par, p->adj_spec, p->adj_acc, p->hop_z};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (auto& t : p->slots) {
     if (t.gt_dev) (void)hipFree(t.gt_dev);
@@ -441,6 +441,7 @@ int cwt_plan_set_option(cwt_plan* p, const char* key, int64_t value) {
   else if (k == "poly_degree") { if (value < 2 || value > POLY_MAX_DEGREE) return fail(CWT_EINVAL, "poly_degree in [2, 24]"); p->poly_degree = int(value); }
   else if (k == "queue_probe") { p->queue_probe = value != 0; }
   else if (k == "adjoint_poly") p->adjoint_poly = value != 0;
+  else if (k == "hop_fuse_terms") { if (value < 0 || value > 65536) return fail(CWT_EINVAL, "hop_fuse_terms in [0, 65536]"); p->hop_fuse_terms = int(value); }
   else if (k == "poly_chunk_mb") { if (value < 0 || value > 4096) return fail(CWT_EINVAL, "poly_chunk_mb in [0, 4096] (0 = one chunk)"); p->poly_chunk_mb = int(value); }
   else if (k == "poly_max_logk") { if (value < 8 || value > 14) return fail(CWT_EINVAL, "poly_max_logk in [8, 14]"); p->poly_max_logk = int(value); }
   else if (k == "poly_min_logn") { if (value < 14 || value > 24) return fail(CWT_EINVAL, "poly_min_logn in [14, 24]"); p->poly_min_logn = int(value); }
@@ -770,6 +771,85 @@ int cwt_transform_batch_weighted(cwt_plan* p, const void* x_dev, int nbatch, int
   const Weights wq{Q_dev, alpha};
   if (!Q_dev) return fail(CWT_EINVAL, "NULL argument");
   return transform_batch_entry(p, x_dev, nbatch, x_ld, n0, mother, param, dt, scales, nrows, xhat_dev, G_dev, ld, ncols, 0, &wq);
+}
+
+// ---- decimated output: every hop-th column (cwt_hip.h) -------------------------------------------------------------------------
+// The checks every hop entry point shares, before anything is queued; *logM = log2(nfft / hop)
+static int check_hop(const cwt_plan* p, int nbatch, int nrows, int64_t n0, int64_t hop, int64_t ld, int64_t ncols_h, int* logM) {
+  if (nbatch < 1 || nrows < 1 || int64_t(nbatch) * nrows > p->max_rows) return fail(CWT_EINVAL, "need nbatch*nrows <= max_rows");
+  if (nrows > kMaxGridY) return fail(CWT_EINVAL, "decimated transform: at most 32768 scales per call");   // (gridDim.y of hop_fold)
+  if (n0 < 1 || n0 > p->N) return fail(CWT_EINVAL, "n0 must be in [1, nfft]");
+  if (hop < 2 || (hop & (hop - 1))) return fail(CWT_EINVAL, "hop must be a power of two >= 2");
+  const int64_t M = p->N / hop;
+  if (hop > p->N || M < 16 || M > 4096) return fail(CWT_EINVAL, "nfft / hop must be in [16, 4096] (longer decimated rows are not built)");
+  if (ncols_h != (n0 + hop - 1) / hop) return fail(CWT_EINVAL, "ncols_h must be ceil(n0 / hop)");
+  if (ld < ncols_h) return fail(CWT_EINVAL, "ld must be >= ncols_h");
+  *logM = ilog2(M);
+  return CWT_OK;
+}
+
+static int transform_hop_entry(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother, double param,
+                               double dt, const double* scales, int nrows, int64_t hop, void* xhat_dev, int64_t xhat_ld, int output,
+                               void* out_dev, const void* Q_dev, double alpha, int64_t ld, int64_t ncols_h, bool from_signal) {
+  if (!p || !scales || !out_dev || (from_signal ? !x_dev : !xhat_dev)) return fail(CWT_EINVAL, "NULL argument");
+  if (mother == MOTHER_TABLE) return fail(CWT_EINVAL, "decimated transform: a built-in mother is needed");
+  if (output < 0 || output > (from_signal ? 2 : 1)) return fail(CWT_EINVAL, from_signal ? "output must be 0 (W), 1 (power) or 2 (weighted)" : "output must be 0 (W) or 1 (power)");
+  int logM = 0;
+  if (int rc = check_hop(p, nbatch, nrows, n0, hop, ld, ncols_h, &logM)) return rc;
+  if (from_signal && nbatch > 1 && x_ld < n0) return fail(CWT_EINVAL, "x_ld must be >= n0");
+  if (!from_signal && xhat_ld < p->N && nbatch > 1) return fail(CWT_EINVAL, "xhat_ld must be >= nfft");
+  if (output == 2) {
+    const Weights wq{Q_dev, alpha};
+    if (int rc = check_weights(p, wq, out_dev, nbatch, nrows, ld, ncols_h)) return rc;
+  }
+  HIPCHECK(hipSetDevice(p->device));
+  // the table of cwt_transform for these scales and n0 columns (the output and the hop are not part of its key)
+  int rc = prepare_rows_table(p, true, mother, param, dt, scales, nrows, n0, n0);
+  if (rc) return rc;
+  if (from_signal && !xhat_dev) {                          // the caller has no use for the spectra: plan scratch
+    rc = grow(&p->hxhat, &p->hxhat_bytes, size_t(nbatch) * size_t(p->N) * 2 * p->esize(), p->stream);
+    if (rc) return rc;
+    xhat_dev = p->hxhat;
+  }
+  if (from_signal) xhat_ld = p->N;
+  const Mother mo = mother_of(mother, param);
+  CallScope scope(p);
+  return scope.done(by_precision(p, [&](auto t) {
+    return transform_hop_impl<decltype(t)>(p, from_signal ? x_dev : nullptr, nbatch, x_ld, n0, xhat_dev, xhat_ld, mo, nrows, logM, output,
+                                           out_dev, Q_dev, alpha, ld, ncols_h);
+  }));
+}
+
+int cwt_transform_hop(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother, double param, double dt,
+                      const double* scales, int nrows, int64_t hop, void* xhat_dev, int output, void* out_dev, const void* Q_dev,
+                      double alpha, int64_t ld, int64_t ncols_h) {
+  return transform_hop_entry(p, x_dev, nbatch, x_ld, n0, mother, param, dt, scales, nrows, hop, xhat_dev, 0, output, out_dev, Q_dev,
+                             alpha, ld, ncols_h, true);
+}
+
+int cwt_transform_rows_hop(cwt_plan* p, const void* xhat_dev, int nbatch, int64_t xhat_ld, int64_t n0, int mother, double param,
+                           double dt, const double* scales, int nrows, int64_t hop, int output, void* out_dev, int64_t ld,
+                           int64_t ncols_h) {
+  return transform_hop_entry(p, nullptr, nbatch, 0, n0, mother, param, dt, scales, nrows, hop, const_cast<void*>(xhat_dev), xhat_ld,
+                             output, out_dev, nullptr, 0.0, ld, ncols_h, false);
+}
+
+int cwt_adjoint_rows_hop(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld, int64_t ldg, int64_t ncols_h, int64_t hop,
+                         int64_t n0, int mother, double param, double dt, const double* scales, int nrows, void* xbar_dev,
+                         int64_t xbar_ld, int accumulate) {
+  if (!p || !G_dev || !scales || !xbar_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (mother == MOTHER_TABLE) return fail(CWT_EINVAL, "adjoint: a built-in mother is needed (a filter bank has no adjoint here)");
+  int logM = 0;
+  if (int rc = check_hop(p, nbatch, nrows, n0, hop, ldg, ncols_h, &logM)) return rc;
+  if (xbar_ld < n0) return fail(CWT_EINVAL, "xbar_ld must be >= n0");
+  if (nbatch > 1 && g_batch_ld < int64_t(nrows) * ldg) return fail(CWT_EINVAL, "g_batch_ld must be >= nrows * ldg");
+  HIPCHECK(hipSetDevice(p->device));
+  const int rc = prepare_rows_table(p, true, mother, param, dt, scales, nrows, n0, n0);
+  if (rc) return rc;
+  return by_precision(p, [&](auto t) {
+    return adjoint_hop_impl<decltype(t)>(p, G_dev, nbatch, g_batch_ld, ldg, ncols_h, logM, n0, mother_of(mother, param), nrows, xbar_dev,
+                                         xbar_ld, accumulate);
+  });
 }
 
 int cwt_transform_rows_table(cwt_plan* p, const void* xhat_dev, const void* table_dev, const int* k_lo,

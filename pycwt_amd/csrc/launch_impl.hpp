@@ -1168,6 +1168,133 @@ int adjoint_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld,
   return CWT_OK;
 }
 
+// ---- decimated output (cwt_transform_hop, cwt_adjoint_rows_hop; kernels: cwt_kernels_hop.hpp) ----------------------------------
+// The rows are the table's plain supports in out_row order (RowLayout::base, the device copy of the adjoint's general path with
+// every row in it); a batch is nbatch signals against the one table, in chunks of signals whose folded spectra fit 64 MiB
+// (and whose rows fit one launch: 32768).
+constexpr size_t kHopScratchBytes = size_t(64) << 20;
+
+template <typename T, int LOGM, typename OUT>
+void launch_hop_rows(cwt_plan* p, const cplx<T>* xhat, int64_t xhat_ld, const cplx<T>* Z, int nrows, int total, const Mother& mo,
+                     OUT out, int64_t ld, int64_t ncols_h) {
+  constexpr int LOGTB = HOP_LOG_POINTS - LOGM, P = 1 << HOP_LOG_POINTS;
+  const size_t lds = size_t(P + (P >> 4)) * sizeof(T);
+  hipLaunchKernelGGL((hop_rows<T, LOGM, out_tag_t<OUT>>), dim3(unsigned((total + (1 << LOGTB) - 1) >> LOGTB)), dim3(1 << (HOP_LOG_POINTS - 4)),
+                     lds, p->stream, xhat, long(xhat_ld), Z, p->rt->adj_dev, nrows, total, mo, tw_table<T>(p, LOGM), p->logN,
+                     p->hop_fuse_terms, out, long(ld), long(ncols_h));
+}
+
+// every row of every signal from the spectra: hop_fold for the rows with many aliases, then hop_rows
+template <typename T, typename OUT>
+int hop_rows_out(cwt_plan* p, const cplx<T>* xhat, int64_t xhat_ld, int nbatch, const Mother& mo, int nrows, int logM, OUT out,
+                 int64_t ld, int64_t ncols_h) {
+  int rc = check_geometry(p);
+  if (!rc) rc = upload_adjoint_rows(p, nrows, false);
+  if (rc) return rc;
+  bool any_fold = false;
+  for (const RowDesc& r : p->rt->base) any_fold = any_fold || hop_terms(r.nband, logM) > p->hop_fuse_terms;
+  const size_t per_signal = (size_t(nrows) << logM) * sizeof(cplx<T>);
+  const int chunk = int(std::max<size_t>(1, std::min<size_t>(size_t(std::min(nbatch, kMaxGridY / nrows)), kHopScratchBytes / per_signal)));
+  if (any_fold) rc = grow(&p->hop_z, &p->hop_z_bytes, size_t(chunk) * per_signal, p->stream);
+  if (rc) return rc;
+  cplx<T>* Z = static_cast<cplx<T>*>(p->hop_z);
+  const int logTK = hop_log_tk(logM);
+  for (int b0 = 0; b0 < nbatch; b0 += chunk) {
+    const int cnt = std::min(chunk, nbatch - b0);
+    const cplx<T>* xh = xhat + size_t(b0) * size_t(xhat_ld);
+    if (any_fold) rc = timed_launch(p, KC_HOP_FOLD, [&] {
+      hipLaunchKernelGGL((hop_fold<T>), dim3(1u << (logM - logTK), unsigned(cnt * nrows)), dim3(HOP_FOLD_THREADS),
+                         HOP_FOLD_THREADS * sizeof(cplx<T>), p->stream, xh, long(xhat_ld), p->rt->adj_dev, nrows, mo, p->logN, logM,
+                         p->hop_fuse_terms, Z);
+    });
+    if (rc) return rc;
+    OUT o = out + long(b0) * long(nrows) * long(ld);
+    const int total = cnt * nrows;
+    rc = timed_launch(p, KC_HOP_ROWS, [&] {
+      switch (logM) {
+        case 4: launch_hop_rows<T, 4>(p, xh, xhat_ld, Z, nrows, total, mo, o, ld, ncols_h); break;
+        case 5: launch_hop_rows<T, 5>(p, xh, xhat_ld, Z, nrows, total, mo, o, ld, ncols_h); break;
+        case 6: launch_hop_rows<T, 6>(p, xh, xhat_ld, Z, nrows, total, mo, o, ld, ncols_h); break;
+        case 7: launch_hop_rows<T, 7>(p, xh, xhat_ld, Z, nrows, total, mo, o, ld, ncols_h); break;
+        case 8: launch_hop_rows<T, 8>(p, xh, xhat_ld, Z, nrows, total, mo, o, ld, ncols_h); break;
+        case 9: launch_hop_rows<T, 9>(p, xh, xhat_ld, Z, nrows, total, mo, o, ld, ncols_h); break;
+        case 10: launch_hop_rows<T, 10>(p, xh, xhat_ld, Z, nrows, total, mo, o, ld, ncols_h); break;
+        case 11: launch_hop_rows<T, 11>(p, xh, xhat_ld, Z, nrows, total, mo, o, ld, ncols_h); break;
+        default: launch_hop_rows<T, 12>(p, xh, xhat_ld, Z, nrows, total, mo, o, ld, ncols_h); break;
+      }
+    });
+    if (rc) return rc;
+  }
+  return CWT_OK;
+}
+
+// cwt_transform_hop / cwt_transform_rows_hop after their checks and the row table: the forward transforms of the signals (x_dev
+// given; spectra to xhat_dev, nbatch x N), then the rows.  output: 0 = W, 1 = |W|^2, 2 = (alpha Q) W.
+template <typename T>
+int transform_hop_impl(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, const void* xhat_dev, int64_t xhat_ld,
+                       const Mother& mo, int nrows, int logM, int output, void* out_dev, const void* q, double alpha, int64_t ld,
+                       int64_t ncols_h) {
+  if (x_dev) {
+    const int rc = fft_rows_impl<T, IN_REAL>(p, x_dev, x_ld, nbatch, n0, const_cast<void*>(xhat_dev));
+    if (rc) return rc;
+  }
+  const cplx<T>* xhat = static_cast<const cplx<T>*>(xhat_dev);
+  if (output == 2)
+    return hop_rows_out<T>(p, xhat, xhat_ld, nbatch, mo, nrows, logM,
+                           weighted_ptr<T>{static_cast<cplx<T>*>(out_dev), static_cast<const T*>(q), T(alpha)}, ld, ncols_h);
+  if (output == 1) return hop_rows_out<T>(p, xhat, xhat_ld, nbatch, mo, nrows, logM, static_cast<T*>(out_dev), ld, ncols_h);
+  return hop_rows_out<T>(p, xhat, xhat_ld, nbatch, mo, nrows, logM, static_cast<cplx<T>*>(out_dev), ld, ncols_h);
+}
+
+// xbar_b (+)= Re A_h^H G_b (cwt_hip.h).  Per signal: the accumulator is zeroed; chunks of rows of G_h go through their M-point
+// forward transforms (k_small, as cwt_fft_rows runs it at length M) and hop_adj_accum; the N-point transform of the accumulator
+// and the trim to n0 are those of adjoint_impl.  Every row takes this path, in row order.
+template <typename T>
+int adjoint_hop_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld, int64_t ldg, int64_t ncols_h, int logM,
+                     int64_t n0, const Mother& mo, int nrows, void* xbar_dev, int64_t xbar_ld, int accumulate) {
+  cwt_plan::RowTable* rt = p->rt;
+  const int logN = p->logN;
+  const int64_t N = p->N, M = int64_t(1) << logM;
+  int rc = check_geometry(p);
+  if (!rc) rc = upload_adjoint_rows(p, nrows, false);
+  if (rc) return rc;
+  const int chunk = int(std::max<size_t>(1, std::min<size_t>(size_t(nrows), kHopScratchBytes / (size_t(M) * sizeof(cplx<T>)))));
+  rc = grow(&p->adj_spec, &p->adj_spec_bytes, std::max(size_t(chunk) * size_t(M), size_t(N)) * sizeof(cplx<T>), p->stream);
+  if (!rc) rc = grow(&p->adj_acc, &p->adj_acc_bytes, size_t(N) * sizeof(cplx<T>), p->stream);
+  if (rc) return rc;
+  cplx<T>* spec = static_cast<cplx<T>*>(p->adj_spec);
+  cplx<T>* acc = static_cast<cplx<T>*>(p->adj_acc);
+  const Mother none{MOTHER_MORLET, 0, 0.0, nullptr};
+  const int logTB = HOP_LOG_POINTS - logM, TB = 1 << logTB;
+  const unsigned bins = unsigned((N + 255) / 256);
+  for (int b = 0; b < nbatch; ++b) {
+    const cplx<T>* G = static_cast<const cplx<T>*>(G_dev) + size_t(b) * size_t(g_batch_ld);
+    HIPCHECK(hipMemsetAsync(acc, 0, size_t(N) * sizeof(cplx<T>), p->stream));
+    for (int first = 0; first < nrows; first += chunk) {
+      const int cnt = std::min(chunk, nrows - first);
+      rc = timed_launch(p, KC_FWD_SMALL, [&] {
+        hipLaunchKernelGGL((k_small<T, IN_CPLX>), dim3(unsigned((cnt + TB - 1) / TB)), dim3(TB << (logM - 4)), (size_t(TB) << logM) * sizeof(T),
+                           p->stream, static_cast<const void*>(G + size_t(first) * size_t(ldg)), (const RowDesc*)nullptr, cnt, none,
+                           tw_table<T>(p, logM), logM, logTB, long(ncols_h), long(ldg), spec, long(M), long(M));
+      });
+      if (!rc) rc = timed_launch(p, KC_ADJOINT, [&] {
+        hipLaunchKernelGGL((hop_adj_accum<T>), dim3(bins), dim3(256), 0, p->stream, static_cast<const cplx<T>*>(spec),
+                           rt->adj_dev + first, cnt, mo, logN, logM, acc);
+      });
+      if (rc) return rc;
+    }
+    rc = fft_rows_impl<T, IN_CPLX>(p, acc, N, 1, N, spec);
+    if (rc) return rc;
+    rc = timed_launch(p, KC_ADJOINT, [&] {
+      hipLaunchKernelGGL((k_adj_out<T>), dim3(unsigned((n0 + 255) / 256)), dim3(256), 0, p->stream,
+                         static_cast<const cplx<T>*>(spec), long(n0), static_cast<T*>(xbar_dev) + size_t(b) * size_t(xbar_ld),
+                         accumulate);
+    });
+    if (rc) return rc;
+  }
+  return CWT_OK;
+}
+
 template <typename T>
 int upload_reals(cwt_plan* p, const double* v, int n) {          // -> p->weights_dev as T[n]
   // two staging buffers used in turn; the only wait is for the copy that left this buffer two calls ago
@@ -1404,7 +1531,10 @@ int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g
   X int ar1_filter_impl<T>(cwt_plan*, const void*, int64_t, int64_t, double, void*);                                               \
   X int forward_fft_n_impl<T>(cwt_plan*, const void*, int64_t, void*);                                                              \
   X int transform_rows_n_impl<T>(cwt_plan*, const void*, int64_t, int, double, double, const double*, int, void*, int64_t);        \
-  X int adjoint_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int64_t, const Mother&, int, void*, int64_t, int);
+  X int adjoint_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int64_t, const Mother&, int, void*, int64_t, int);   \
+  X int transform_hop_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, const void*, int64_t, const Mother&, int, int, int, void*, \
+                              const void*, double, int64_t, int64_t);                                                              \
+  X int adjoint_hop_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int64_t, int, int64_t, const Mother&, int, void*, int64_t, int);
 
 #ifndef CWT_LAUNCH_TU
 CWT_LAUNCH_TEMPLATES(extern template, double)

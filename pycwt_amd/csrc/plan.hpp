@@ -45,7 +45,7 @@ int fail(int code, const std::string& msg);
 
 enum KernelClass { KC_FWD_SMALL, KC_FWD_A, KC_FWD_B, KC_SMALL, KC_DIRECT, KC_NARROW, KC_NARROW_MANY, KC_NARROW_BIG,
                    KC_PASS_A, KC_PASS_B, KC_ICWT, KC_ELEMENTWISE, KC_OLS_FWD, KC_OLS, KC_OLS_SMALL, KC_AOLS_PRE, KC_AOLS,
-                   KC_POLY_COEF, KC_POLY, KC_ADJOINT, KC_COUNT };
+                   KC_POLY_COEF, KC_POLY, KC_ADJOINT, KC_HOP_FOLD, KC_HOP_ROWS, KC_COUNT };
 extern const char* const kClassNames[KC_COUNT];
 
 int ilog2(int64_t v);
@@ -121,6 +121,8 @@ struct cwt_plan {
   int poly_degree = 8;     // preferred largest degree: the interval count K' of a row is the smallest that needs no more
   int poly_min_logn = 16;  // shortest transform that takes the form
   int poly_max_logk = 14;  // largest log2 K' (tuning: 13 keeps the rows that need 16384 intervals out of the form)
+  int hop_fuse_terms = 1;  // cwt_transform_hop: rows with at most this many aliases per folded bin fold their band inside hop_rows; the others go
+                           // through hop_fold and plan scratch (0 = every row through hop_fold)
   int adjoint_poly = 1;    // cwt_adjoint_rows: the rows of form P through its transpose (k_poly_moments); 0 = every row through the general path
   int poly_chunk_mb = 96;  // coefficient planes computed and consumed per chunk of polynomial rows (MiB; 0 = all rows at once)
   int host_direct = 1;     // cwt_execute_host, transforms that fit one workgroup: the kernels read the signal from / write W into page-locked host memory
@@ -166,6 +168,8 @@ struct cwt_plan {
   size_t adj_spec_bytes = 0;
   void* adj_acc = nullptr;  // ... and the per-signal accumulator conj(sum_j conj(F_j) DFT(G_j)) (N complex)
   size_t adj_acc_bytes = 0;
+  void* hop_z = nullptr;    // cwt_transform_hop: folded spectra of a chunk of signals (signals x rows x M complex)
+  size_t hop_z_bytes = 0;
   void* xm = nullptr;       // band-passed complex signal x_M of the k_aols rows (N complex)
   size_t xm_bytes = 0;
   void* xsa = nullptr;      // its block spectra (nblocks x (P + 8) complex)

@@ -147,6 +147,22 @@ class HipEngine:
             self.plan.transform_batch_weighted(x.data_ptr(), x.shape[0], x.shape[1], n0, kind, param, dt, sj, xhat.data_ptr(),
                                                Q.data_ptr(), alpha, G.data_ptr(), G.shape[-1], ncols)
 
+    def transform_hop(self, x, n0, hop, output, kind, param, dt, sj, out, Q=None, alpha=0.0):
+        """Columns ::hop of `transform` (cwt_transform_hop): out (rows, ld) or (batch, rows, ld) with ld >= ceil(n0 / hop),
+        contiguous; output 0 = W (complex), 1 = |W|^2 (real), 2 = (alpha Q) W (complex, Q real of out's shape).  The spectra
+        go to plan scratch."""
+        if not out.is_contiguous() or (Q is not None and (tuple(Q.shape) != tuple(out.shape) or not Q.is_contiguous())):
+            raise ValueError("transform_hop: out (and Q, of the same shape) must be contiguous")
+        nb = 1 if x.dim() == 1 else x.shape[0]
+        self.plan.transform_hop(x.data_ptr(), nb, x.shape[-1], n0, kind, param, dt, sj, hop, None, output, out.data_ptr(),
+                                out.shape[-1], None if Q is None else Q.data_ptr(), alpha)
+
+    def adjoint_rows_hop(self, G, n0, hop, kind, param, dt, sj, xbar, accumulate=False):
+        """xbar (+)= Re A_h^H G (cwt_adjoint_rows_hop): G (rows, ld) or (batch, rows, ld) complex, xbar (n0,) or (batch, ld_x)."""
+        nb = 1 if G.dim() == 2 else G.shape[0]
+        self.plan.adjoint_rows_hop(G.data_ptr(), nb, G.shape[-2] * G.shape[-1], G.shape[-1], hop, n0, kind, param, dt, sj,
+                                   xbar.data_ptr(), xbar.shape[-1], accumulate)
+
     def classify(self, kind, param, dt, sj, ncols):
         return self.plan.classify(kind, param, dt, sj, ncols, True)
 

@@ -133,6 +133,34 @@ def _transform(plan, x_host, xd_ptr, n0, kind, param, dt, sj, xh_ptr, W_ptr, aut
         (plan.transform_rows_power if power else plan.transform_rows)(xh_ptr, kind, param, dt, sj, W_ptr, n0, n0)
 
 
+def _check_hop(hop, N, mother=None, pad=True):
+    """`hop=` of the decimated calls: a power of two >= 2 with 16 <= N / hop <= 4096 (N the padded length), built-in mothers, pad=True."""
+    if isinstance(hop, bool) or int(hop) != hop:
+        raise ValueError("hop must be an integer")
+    hop = int(hop)
+    if hop < 2 or hop & (hop - 1):
+        raise ValueError("hop must be a power of two >= 2")
+    if not pad or N & (N - 1):
+        raise ValueError("hop needs pad=True (no decimated output at lengths that are not a power of two)")
+    if not 16 <= N // hop <= 4096:
+        raise ValueError(f"hop: the padded length / hop must be in [16, 4096], got {N} / {hop}")
+    if mother is not None and not hasattr(mother, "device_id"):
+        raise ValueError("hop: only the built-in mothers (Morlet, Paul, DOG) have a decimated transform")
+    return hop
+
+
+def _transform_hop(plan, x_host, xd_ptr, nb, n0, kind, param, dt, sj, hop, xh_ptr, output, out_ptr, auto=True):
+    """Signals (uploaded at xd_ptr, nb x n0) -> spectra and columns ::hop of their rows (cwt_transform_hop).  Everything goes
+    through the spectrum, so non-finite samples need no path of their own (all NaN, as in the reference); the automatic
+    accuracy target sets the support band of the rows as in `_transform`."""
+    if nb == 1 and auto and plan.nfft > 4096 and np.isfinite(x_host).all():
+        target = _auto(plan)
+        if target:
+            plan.forward_fft(xd_ptr, n0, xh_ptr)
+            plan.set_tolerance(plan.auto_tolerance(xh_ptr, target))
+    plan.transform_hop(xd_ptr, nb, n0, n0, kind, param, dt, sj, hop, xh_ptr, output, out_ptr, -(-n0 // hop))
+
+
 def _cwt_builtin(x, dt, sj, kind, param, N, precision, device, finite, power=False):
     """W (rows x n0) and the spectrum (N) for a built-in mother through the device-resident entry points; power=True:
     |W|^2 (rows x n0 reals) from the power entry points instead of W."""
@@ -383,12 +411,12 @@ def cwt(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, pre
 class _DeviceResult:
     """A device-resident result of one transform (a matrix in `_buf`) with the grids of `cwt` and its spectrum."""
 
-    def __init__(self, plan, buf, sj, freqs, coi, fft, fftfreqs, mother, dt, n0, spectrum=None):
+    def __init__(self, plan, buf, sj, freqs, coi, fft, fftfreqs, mother, dt, n0, spectrum=None, ncols=None):
         self._plan, self._buf = plan, buf
         self.sj, self.freqs, self.coi, self.fftfreqs = sj, freqs, coi, fftfreqs
         self._fft, self._spectrum = fft, spectrum              # the 5th return value of cwt(): downloaded when first asked for
         self.mother, self.dt, self.n0 = mother, dt, n0
-        self.shape = (sj.size, n0)
+        self.shape = (sj.size, n0 if ncols is None else ncols)     # (ncols: the columns of a decimated result, hop=)
 
     @property
     def fft(self):
@@ -453,10 +481,15 @@ class DeviceTransform(_DeviceResult):
         return dj * np.sqrt(self.dt) / (self.mother.cdelta * self.mother.psi(0)) * total
 
 
-def cwt_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0):
+def cwt_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0, hop=None):
     """`cwt` whose result stays on the GPU: returns a `DeviceTransform` (attributes sj, freqs, coi, fft,
     fftfreqs as in `cwt` -- read-only views of the cached grids; `fft`, the spectrum, is downloaded when first asked for
-    and must be asked for before `close()`; methods W(), global_power(), scale_average(), icwt())."""
+    and must be asked for before `close()`; methods W(), global_power(), scale_average(), icwt()).
+
+    hop=h (a power of two, 16 <= padded length / h <= 4096): only every h-th column is computed -- the matrix has
+    ceil(n0 / h) columns equal to columns ``::h`` of the undecimated result to rounding, `coi` is ``coi[::h]``, sj and freqs
+    are unchanged, and the reductions act on the kept columns.  The columns are a SAMPLE of W, not an average over the hop:
+    choosing h against the smallest scale is the caller's business."""
     mother = _check_parameter_wavelet(wavelet)
     precision = _default_precision() if precision is None else int(precision)
     n0 = len(signal)
@@ -467,13 +500,20 @@ def cwt_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None,
         sj, freqs = sj[~bad], np.asarray(freqs)[~bad]
     plan = _plan(N, precision, device, sj.size)
     es = np.dtype(plan.real).itemsize
+    ncols = n0
+    if hop is not None:
+        hop = _check_hop(hop, N, mother)
+        ncols, coi = -(-n0 // hop), np.asarray(coi)[::hop]
     xd, xh = _hip.DeviceBuffer(n0 * es, device), _hip.DeviceBuffer(N * 2 * es, device)
-    Wd = _hip.DeviceBuffer(sj.size * n0 * 2 * es, device)
+    Wd = _hip.DeviceBuffer(sj.size * ncols * 2 * es, device)
     try:
         with plan.lock:
             xs_host = np.ascontiguousarray(signal, dtype=plan.real)
             xd.upload(plan, xs_host)
-            _transform(plan, xs_host, xd.ptr, n0, kind, param, dt, sj, xh.ptr, Wd.ptr)
+            if hop is None:
+                _transform(plan, xs_host, xd.ptr, n0, kind, param, dt, sj, xh.ptr, Wd.ptr)
+            else:
+                _transform_hop(plan, xs_host, xd.ptr, 1, n0, kind, param, dt, sj, hop, xh.ptr, plan.OUT_W, Wd.ptr)
             plan.sync()
     except Exception:
         Wd.free()
@@ -487,7 +527,7 @@ def cwt_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None,
         v = np.asarray(a).view()
         v.flags.writeable = False
         return v
-    return DeviceTransform(plan, Wd, ro(sj), ro(freqs), ro(coi), None, ro(fftfreqs), mother, dt, n0, spectrum=xh)
+    return DeviceTransform(plan, Wd, ro(sj), ro(freqs), ro(coi), None, ro(fftfreqs), mother, dt, n0, spectrum=xh, ncols=ncols)
 
 
 def cwt_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None,
@@ -541,7 +581,7 @@ def cwt_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None,
     return (W, sj, freqs, coi, xhat[:, 1:N // 2] / N ** 0.5, ftfreqs[1:N // 2] / (2 * np.pi))
 
 
-def cwt_power(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0, pad=True):
+def cwt_power(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0, pad=True, hop=None):
     """``cwt`` that returns the wavelet power ``|W|^2`` in place of ``W``: ``(power, sj, freqs, coi, fft, fftfreqs)``.
 
     ``power`` is float64 of shape (rows, n0) and equals ``np.abs(cwt(...)[0]) ** 2`` to rounding; the other five values are
@@ -550,9 +590,16 @@ def cwt_power(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, 
     square it there.  A complex signal is transformed through ``cwt`` (its ``W`` is the sum of the transforms of both parts,
     whose power is not the sum of their powers) and squared.  Same rules as ``cwt`` otherwise: Paul's NaN rows, non-finite
     samples (all NaN), float32 input, precision, automatic tolerance.
+
+    hop=h (a power of two, 16 <= padded length / h <= 4096; real signals, built-in mothers, pad=True): only every h-th column
+    is computed and downloaded -- ``power`` has ceil(n0 / h) columns equal to columns ``::h`` of the undecimated power to
+    rounding, ``coi`` is ``coi[::h]``, everything else is unchanged.  The columns are SAMPLES of |W|^2, not its mean over the
+    hop: choosing h against the smallest scale is the caller's business.
     """
     mother = _check_parameter_wavelet(wavelet)
     precision = _default_precision() if precision is None else int(precision)
+    if hop is not None:
+        return _cwt_power_hop(signal, dt, dj, s0, J, mother, freqs, precision, device, pad, hop)
     if np.iscomplexobj(signal):
         W, sj, freqs, coi, fft5, fftfreqs = cwt(signal, dt, dj, s0, J, mother, freqs, precision=precision, device=device,
                                                 pad=pad)
@@ -594,6 +641,44 @@ def cwt_power(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, 
     return (P, np.array(sj), freqs, np.array(coi), fft5, np.array(fftfreqs))
 
 
+def _cwt_power_hop(signal, dt, dj, s0, J, mother, freqs, precision, device, pad, hop):
+    """`cwt_power(hop=)`: the power of every hop-th column through cwt_transform_hop."""
+    if np.iscomplexobj(signal):
+        raise ValueError("hop: real signals only")
+    in_dtype = getattr(signal, "dtype", None)
+    n0 = len(signal)
+    user_freqs = freqs is not None
+    N, sj, freqs, coi, fftfreqs, bad = _geometry(mother, n0, dt, dj, s0, J, freqs, pad)
+    hop = _check_hop(hop, N, mother, pad)
+    plan_real = np.float64 if precision == 64 else np.float32
+    x = np.ascontiguousarray(signal, dtype=plan_real)
+    finite = bool(np.isfinite(x).all())
+    if bad is not None and not bad.all() and finite:       # (see cwt)
+        sj, freqs = sj[~bad], np.asarray(freqs)[~bad]
+    kind, param = mother.device_id()
+    ncols = -(-n0 // hop)
+    plan = _plan(N, precision, device, sj.size)
+    es = np.dtype(plan.real).itemsize
+    sc = _Scratch(device)
+    try:
+        xd, xh, Pd = sc.new(n0 * es), sc.new(N * 2 * es), sc.new(sj.size * ncols * es)
+        with plan.lock:
+            xd.upload(plan, x)
+            _transform_hop(plan, x, xd.ptr, 1, n0, kind, param, dt, sj, hop, xh.ptr, plan.OUT_POWER, Pd.ptr)
+            P = Pd.download(plan, (sj.size, ncols), plan.real).astype(np.float64)
+            xhat = xh.download(plan, (N,), plan.cplx).astype(np.complex128, copy=False)
+    finally:
+        sc.free()
+    if bad is not None and bad.all():
+        P = np.full(P.shape, np.nan, dtype=P.dtype)
+    fft5 = xhat[1:N // 2] / N ** 0.5
+    if in_dtype == np.float32:
+        fft5 = fft5.astype(np.complex64)
+    if not user_freqs:
+        freqs = np.array(freqs)
+    return (P, np.array(sj), freqs, np.array(coi)[::hop], fft5, np.array(fftfreqs))
+
+
 class DevicePower(_DeviceResult):
     """The wavelet power |W|^2 (rows x n0 reals of the plan's precision) kept on the GPU, as `cwt_power` computes it: the
     power-only counterpart of `DeviceTransform`.  `power()` downloads the matrix; `global_power()` and `scale_average()` reduce
@@ -615,9 +700,10 @@ class DevicePower(_DeviceResult):
         return self._vector(n0, lambda p: self._plan.reduce_scales(self._buf.ptr, n0, n0, w, 2, coeff, p))
 
 
-def cwt_power_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0):
+def cwt_power_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0, hop=None):
     """`cwt_device` with the power output: returns a `DevicePower` (attributes sj, freqs, coi, fft, fftfreqs as in
-    `cwt_device`; methods power(), global_power(), scale_average(), close(); device_ptr)."""
+    `cwt_device`; methods power(), global_power(), scale_average(), close(); device_ptr).  hop=h as in `cwt_device`: the
+    power of every h-th column, ceil(n0 / h) of them -- samples of |W|^2, not its mean over the hop."""
     mother = _check_parameter_wavelet(wavelet)
     precision = _default_precision() if precision is None else int(precision)
     n0 = len(signal)
@@ -627,13 +713,20 @@ def cwt_power_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs
         sj, freqs = sj[~bad], np.asarray(freqs)[~bad]
     plan = _plan(N, precision, device, sj.size)
     es = np.dtype(plan.real).itemsize
+    ncols = n0
+    if hop is not None:
+        hop = _check_hop(hop, N, mother)
+        ncols, coi = -(-n0 // hop), np.asarray(coi)[::hop]
     xd, xh = _hip.DeviceBuffer(n0 * es, device), _hip.DeviceBuffer(N * 2 * es, device)
-    Pd = _hip.DeviceBuffer(sj.size * n0 * es, device)
+    Pd = _hip.DeviceBuffer(sj.size * ncols * es, device)
     try:
         with plan.lock:
             xs_host = np.ascontiguousarray(signal, dtype=plan.real)
             xd.upload(plan, xs_host)
-            _transform(plan, xs_host, xd.ptr, n0, kind, param, dt, sj, xh.ptr, Pd.ptr, power=True)
+            if hop is None:
+                _transform(plan, xs_host, xd.ptr, n0, kind, param, dt, sj, xh.ptr, Pd.ptr, power=True)
+            else:
+                _transform_hop(plan, xs_host, xd.ptr, 1, n0, kind, param, dt, sj, hop, xh.ptr, plan.OUT_POWER, Pd.ptr)
             plan.sync()
     except Exception:
         Pd.free()
@@ -646,14 +739,15 @@ def cwt_power_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs
         v = np.asarray(a).view()
         v.flags.writeable = False
         return v
-    return DevicePower(plan, Pd, ro(sj), ro(freqs), ro(coi), None, ro(fftfreqs), mother, dt, n0, spectrum=xh)
+    return DevicePower(plan, Pd, ro(sj), ro(freqs), ro(coi), None, ro(fftfreqs), mother, dt, n0, spectrum=xh, ncols=ncols)
 
 
 def cwt_power_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None,
-                    device=0, max_batch_bytes=8 << 30):
+                    device=0, max_batch_bytes=8 << 30, hop=None):
     """`cwt_batch` with the power output: `(power, sj, freqs, coi, fft, fftfreqs)` with `power` float64 of shape
     (batch, rows, n0).  Slabs of at most `max_batch_bytes` of power; a slab with a non-finite sample goes through the
-    spectra (every coefficient of that signal NaN, as in `cwt_batch`)."""
+    spectra (every coefficient of that signal NaN, as in `cwt_batch`).  hop=h as in `cwt_power`: (batch, rows, ceil(n0 / h))
+    samples of the power at columns ``::h`` and ``coi[::h]``."""
     mother = _check_parameter_wavelet(wavelet)
     precision = _default_precision() if precision is None else int(precision)
     X = np.atleast_2d(np.asarray(signals))
@@ -666,20 +760,27 @@ def cwt_power_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs
     kind, param = _device_id(mother)
     rows = sj.size
     es = 8 if precision == 64 else 4
-    slab = int(max(1, min(nb, max_batch_bytes // (rows * n0 * es))))
+    ncols = n0
+    if hop is not None:
+        hop = _check_hop(hop, N, mother)
+        ncols = -(-n0 // hop)
+    slab = int(max(1, min(nb, max_batch_bytes // (rows * ncols * es))))
     plan = _plan(N, precision, device, slab * rows)
-    P = np.empty((nb, rows, n0), dtype=np.float64)
+    P = np.empty((nb, rows, ncols), dtype=np.float64)
     xhat = np.empty((nb, N), dtype=np.complex128)
     sc = _Scratch(device)
     try:
         xd, xh = sc.new(slab * n0 * es), sc.new(slab * N * 2 * es)
-        Pd = sc.new(slab * rows * n0 * es)
+        Pd = sc.new(slab * rows * ncols * es)
         for b0 in range(0, nb, slab):
             cnt = min(slab, nb - b0)
             with plan.lock:
                 xs = np.ascontiguousarray(X[b0:b0 + cnt], dtype=plan.real)
                 xd.upload(plan, xs)
-                if np.isfinite(xs).all():
+                if hop is not None:
+                    # (auto=False: like the call without hop, a batch runs at the plan's tolerance -- a signal's bits do not depend on the slabs)
+                    _transform_hop(plan, xs, xd.ptr, cnt, n0, kind, param, dt, sj, hop, xh.ptr, plan.OUT_POWER, Pd.ptr, auto=False)
+                elif np.isfinite(xs).all():
                     plan.transform_batch_power(xd.ptr, cnt, n0, n0, kind, param, dt, sj, xh.ptr, Pd.ptr, n0, n0)
                 else:
                     # (see cwt_batch) the rows of each signal from its spectrum alone
@@ -687,11 +788,13 @@ def cwt_power_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs
                     for b in range(cnt):
                         plan.transform_rows_power(xh.ptr + b * N * 2 * es, kind, param, dt, sj, Pd.ptr + b * rows * n0 * es,
                                                   n0, n0)
-                P[b0:b0 + cnt] = Pd.download(plan, (cnt, rows, n0), plan.real)
+                P[b0:b0 + cnt] = Pd.download(plan, (cnt, rows, ncols), plan.real)
                 xhat[b0:b0 + cnt] = xh.download(plan, (cnt, N), plan.cplx)
     finally:
         sc.free()
     coi = _coi(mother, n0, dt)
+    if hop is not None:
+        coi = np.asarray(coi)[::hop]
     ftfreqs = 2 * np.pi * np.fft.fftfreq(N, dt)
     return (P, sj, freqs, coi, xhat[:, 1:N // 2] / N ** 0.5, ftfreqs[1:N // 2] / (2 * np.pi))
 
