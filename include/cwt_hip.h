@@ -78,6 +78,9 @@ int cwt_plan_set_stream(cwt_plan* plan, void* hip_stream);
  *   "poly_chunk_mb" the polynomial rows go through in as few chunks of about equal coefficient volume as keep that volume
  *                  below this many MiB (default 96; 0 = all rows at once): planes computed, then consumed while they still sit
  *                  in the Infinity Cache (matters from ~150 MB: fp64 Paul, round-off targets)
+ *   "poly_xcd"     0 = a workgroup of k_poly_rows computes the 8 KB piece blockIdx.x of its row (default 1: the workgroups that
+ *                  share an XCD take contiguous stretches of 256 KB, so that a 128-byte line of the coefficient planes is
+ *                  fetched into one L2 instead of eight; the outputs are bit-identical, -DCWT_POLY_XCD=0 makes 0 the default)
  *   "poly_max_logk" log2 of the largest interval count K' (8 ... 14, default 14 = the largest coefficient tile)
  *   "aols"         0 = rows clipped at the Nyquist bins stay two-pass rows (default 1: overlap-save rows on the band-passed
  *                  complex signal, k_aols_*; Morlet, Paul, and -- with the real signal at hand -- DOG of order >= 1)

@@ -832,12 +832,12 @@ k_poly_coef(const cplx<T>* __restrict__ yb, const RowDesc* __restrict__ rows, co
 // complex64 outputs).  sc[i][d] = a_d[m0 + i] for the intervals m0 ... the workgroup touches.
 template <typename T, int D, typename WT>
 __device__ __forceinline__ void poly_rows_body(const RowDesc& rd, const cplx<T>* __restrict__ coef, const TwN<T>& twn,
-                                               int logN, out_arg_t<WT> W, long ldw, long ncols, cplx<T>* sc) {
+                                               int logN, out_arg_t<WT> W, long ldw, long ncols, cplx<T>* sc, unsigned piece) {
   constexpr int PT = sizeof(T) == 8 ? 1 : 2, SPAN = 256 * PT, I = POLY_PASSES, WSPAN = 64 * PT;
   static_assert((I & (I - 1)) == 0, "POLY_PASSES: a power of two (a wavefront's span must divide the interval length)");
   const int logR = logN - rd.logK;
   const unsigned nmask = unsigned((1 << logN) - 1);
-  const unsigned n0 = blockIdx.x * unsigned(SPAN * I);
+  const unsigned n0 = piece * unsigned(SPAN * I);
   const unsigned m0 = n0 >> logR;
   const unsigned last = (n0 + unsigned(SPAN * I) - 1u) & nmask;          // (the grid covers ncols <= N outputs)
   const unsigned nint = ((last >= n0 ? last : nmask) >> logR) - m0 + 1u;
@@ -969,11 +969,11 @@ __device__ __forceinline__ unsigned wave_uniform(unsigned v) {
 // scalar registers -- no staging in LDS, no workgroup barrier, no LDS reads.
 template <typename T, int D, typename WT>
 __device__ __forceinline__ void poly_rows_body_s(const RowDesc& rd, const cplx<T>* __restrict__ coef, const TwN<T>& twn,
-                                                 int logN, out_arg_t<WT> W, long ldw, long ncols) {
+                                                 int logN, out_arg_t<WT> W, long ldw, long ncols, unsigned piece) {
   constexpr int PT = sizeof(T) == 8 ? 1 : 2, SPAN = 256 * PT, I = POLY_PASSES, WSPAN = 64 * PT;
   const int logR = logN - rd.logK;
   const unsigned nmask = unsigned((1 << logN) - 1);
-  const unsigned n0 = blockIdx.x * unsigned(SPAN * I);
+  const unsigned n0 = piece * unsigned(SPAN * I);
   const unsigned nw = n0 + wave_uniform(threadIdx.x >> 6) * unsigned(WSPAN * I);      // first output of this wavefront
   const unsigned nl = nw + (threadIdx.x & 63u) * unsigned(PT);
   const int kc = rd.k_lo + rd.kc_off;
@@ -1070,19 +1070,46 @@ __device__ __forceinline__ void poly_rows_body_s(const RowDesc& rd, const cplx<T
   }
 }
 
+// Which 8 KB piece of its row (POLY_PASSES x 256 lanes x 16 bytes of output) a workgroup computes.  The workgroups of a launch go
+// to the 8 XCDs round-robin by linear id, so with piece = blockIdx.x the eight pieces of a 64 KB stretch land on eight L2s, and
+// every one of them fetches the stretch's coefficient lines from the fabric: a 128-byte plane line holds the coefficients of
+// 128 / sizeof(complex) intervals and lies under 128 R bytes of output -- from one piece (K' = 16384 at N = 2^20) to 64 (K' = 256).
+// Here the workgroups that share an XCD inside a row (the same blockIdx.x & 7: a label of the group, not the XCD's number) take
+// CONTIGUOUS stretches of S = 2^logS pieces instead and walk a stretch piece by piece in the order they are dispatched, so that a
+// plane line is fetched into one L2 (two, where it crosses a stretch boundary), once.  A row is cut into groups of 8 S pieces;
+// piece t of stretch x of a group goes to workgroup 8 t + x of that group.  The last, shorter group of a row (m pieces, q = m / 8,
+// r = m % 8) gives its first r stretches q + 1 pieces and the others q: a bijection of [0, gridDim.x) for every grid -- nothing is
+// computed twice, no workgroup leaves early.  Placement decides where the coefficient lines are cached and nothing else: every
+// output is computed from the same operands in the same order under either mapping, whatever XCD a workgroup lands on.
+// S = 32 pieces (256 KB of output, CWT_POLY_XCD_LOG) for every row.  [measured, config 2, parent and variants alternated on one
+// box, profiles/poly_xcd.txt: FETCH_SIZE x2 of the kernel 168 -> 63 MB for 57 MB of planes; the classes K' <= 4096 gain 3 - 8 %,
+// K' >= 8192 0 - 6 %; step -1.1 ... -1.8 %.  Stretches of 8 pieces (64 KB) LOSE: the D = 4 rows store 6.3 TB/s against the parent's 6.7,
+// step +2.4 % -- eight write streams 64 KB apart; stretches of one plane line per row (8 ... 64 pieces) and of 16 pieces gain less
+// (-0.1 ... -0.7 %), and leaving the rows with K' >= 8192 on the old mapping does too (-0.9 %)]
+// Plan option "poly_xcd" = 0 (-DCWT_POLY_XCD=0 makes that the default) keeps piece = blockIdx.x.
+__host__ __device__ __forceinline__ unsigned poly_xcd_piece(unsigned bx, unsigned gx, int logS) {
+  const unsigned G = 8u << logS;                                         // workgroups (= pieces) of one group
+  const unsigned o = bx & (G - 1u), base = bx - o, x = o & 7u, t = o >> 3;
+  if (base + G <= gx) return base + (x << logS) + t;
+  const unsigned m = gx - base, q = m >> 3, r = m & 7u;                  // the row's last group
+  return base + (x < r ? x * (q + 1u) : r * (q + 1u) + (x - r) * q) + t;
+}
+
 template <typename T, typename WT = cplx<T>>
 __global__ void __launch_bounds__(256)
 k_poly_rows(const RowDesc* __restrict__ rows, const cplx<T>* __restrict__ coef, TwN<T> twn, int logN,
-            out_arg_t<WT> W, long ldw, long ncols) {
+            out_arg_t<WT> W, long ldw, long ncols, int xcd) {
   HIP_DYNAMIC_SHARED(double2, lds_raw)
   cplx<T>* sc = reinterpret_cast<cplx<T>*>(lds_raw);
   const RowDesc rd = rows[blockIdx.y];
+  // xcd = log2 of the stretch length in pieces, 0 = piece = blockIdx.x
+  const unsigned piece = xcd ? poly_xcd_piece(blockIdx.x, gridDim.x, xcd) : blockIdx.x;
   constexpr int SMAX = sizeof(T) == 8 ? CWT_POLY_SCALAR_D64 : CWT_POLY_SCALAR_D32;
   static_assert(sizeof(T) == 8 || SMAX == 0, "poly_rows_body_s: one interval per pass of a wavefront (R >= 128 in complex64 is not guaranteed)");
 #define CWT_POLYR_CASE(DD)                                                                      \
   case DD:                                                                                      \
-    if constexpr (DD <= SMAX) poly_rows_body_s<T, DD, WT>(rd, coef, twn, logN, W, ldw, ncols);      \
-    else poly_rows_body<T, DD, WT>(rd, coef, twn, logN, W, ldw, ncols, sc);                         \
+    if constexpr (DD <= SMAX) poly_rows_body_s<T, DD, WT>(rd, coef, twn, logN, W, ldw, ncols, piece); \
+    else poly_rows_body<T, DD, WT>(rd, coef, twn, logN, W, ldw, ncols, sc, piece);                    \
     break;
   switch (rd.nterms) {
     CWT_POLYR_CASE(2) CWT_POLYR_CASE(4) CWT_POLYR_CASE(6) CWT_POLYR_CASE(8) CWT_POLYR_CASE(10) CWT_POLYR_CASE(12)

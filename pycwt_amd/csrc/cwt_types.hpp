@@ -91,6 +91,15 @@ constexpr int POLY_MAX_DEGREE = 24;
 #endif
 constexpr int POLY_PASSES = CWT_POLY_PASSES;   // passes of 256 lanes x 16 bytes per workgroup of k_poly_rows (measured: 1, 3, 4 slower)
 constexpr int POLY_MIN_LOGR = 6;          // shortest interval: 64 samples
+// k_poly_rows: XCD-local stretches (poly_xcd_piece in cwt_kernels_rows.hpp).  CWT_POLY_XCD = default of the plan option "poly_xcd"
+// (0 = piece = blockIdx.x), CWT_POLY_XCD_LOG = log2 of the stretch length in 8 KB pieces (5: 256 KB; measured 3 ... 6).
+#ifndef CWT_POLY_XCD
+#define CWT_POLY_XCD 1
+#endif
+#ifndef CWT_POLY_XCD_LOG
+#define CWT_POLY_XCD_LOG 5
+#endif
+static_assert(CWT_POLY_XCD_LOG >= 1 && CWT_POLY_XCD_LOG <= 16, "CWT_POLY_XCD_LOG: stretches of 16 KB ... 512 MB");
 struct PolyClass {
   int logK;        // log2 K'
   int row_first;   // first row of the class in the row table handed to the kernels

@@ -560,7 +560,8 @@ int launch_poly_rows(cwt_plan* p, int chunk, OUT W, int64_t ldw, int64_t ncols, 
   return timed_launch(p, KC_POLY, [&] {
     for (int r0 = 0; r0 < ch.nrows; r0 += kMaxGridY)
       hipLaunchKernelGGL((k_poly_rows<T, out_tag_t<OUT>>), dim3(unsigned((ncols + per_wg - 1) / per_wg), std::min(kMaxGridY, ch.nrows - r0)),
-                         dim3(256), lds2, st, rows + r0, coef, twn_of<T>(p), p->logN, W, long(ldw), long(ncols));
+                         dim3(256), lds2, st, rows + r0, coef, twn_of<T>(p), p->logN, W, long(ldw), long(ncols),
+                         p->poly_xcd ? CWT_POLY_XCD_LOG : 0);
   }, st);
 }
 

@@ -125,6 +125,8 @@ struct cwt_plan {
                            // through hop_fold and plan scratch (0 = every row through hop_fold)
   int adjoint_poly = 1;    // cwt_adjoint_rows: the rows of form P through its transpose (k_poly_moments); 0 = every row through the general path
   int poly_chunk_mb = 96;  // coefficient planes computed and consumed per chunk of polynomial rows (MiB; 0 = all rows at once)
+  int poly_xcd = CWT_POLY_XCD;   // k_poly_rows: the workgroups that share an XCD take contiguous stretches of a row, so that a coefficient line
+                           // is fetched into one L2 once (poly_xcd_piece in cwt_kernels_rows.hpp); 0 = piece = blockIdx.x
   int host_direct = 1;     // cwt_execute_host, transforms that fit one workgroup: the kernels read the signal from / write W into page-locked host memory
   int aols = 1;            // rows clipped at Nyquist as overlap-save rows on the band-passed complex signal (k_aols_*)
   int aols_zc = 1;         // Paul rows not clipped at Nyquist on the band-passed signal too, their profile continued through f = 0

@@ -1,0 +1,27 @@
+"""k_poly_rows: the XCD-local mapping of its workgroups (poly_xcd = 1) writes the bits of the mapping piece = blockIdx.x
+(poly_xcd = 0), on the CPU emulation of the HIP runtime.  Cases and rules: poly_xcd_common.py."""
+import pytest
+
+import poly_xcd_common as pc
+
+N = 1 << 16
+
+
+@pytest.mark.parametrize("ncols", [N, N - 1, 12345, 40000])
+@pytest.mark.parametrize("prec", [64, 32])
+def test_both_mappings_write_the_same_bits(emu_library, prec, ncols):
+    pc.assert_same_bits(emu_library, N, prec, pc.scales(N, pc.IDX), ncols, want=pc.WANT)
+
+
+def test_two_plane_chunks(emu_library):
+    """poly_chunk_mb = 1 and 1.9 MB of coefficient planes: two launches of the kernel per call, each a grid of its own."""
+    idx = sorted(set(pc.IDX) | set(range(105, 117)))
+    pc.assert_same_bits(emu_library, N, 64, pc.scales(N, idx), N - 1, want=pc.WANT, min_chunks=2, extra={"poly_chunk_mb": 1})
+
+
+@pytest.mark.parametrize("prec", [64, 32])
+def test_a_whole_group_and_a_short_one(emu_library, prec):
+    """N = 2^18, 511 pieces per row in complex128 (a whole group of 256 and one of 255), 256 in complex64 (one whole group)."""
+    n = 1 << 18
+    pc.assert_same_bits(emu_library, n, prec, pc.scales(n, [112, 142, 154, 166, 202]), n - 1000,
+                        want={(2048, 8), (512, 8), (256, 8), (256, 6), (256, 4)} if prec == 64 else None)
