@@ -371,6 +371,36 @@ int cwt_adjoint_rows_hop(cwt_plan* plan, const void* G_dev, int nbatch, int64_t 
                          int64_t hop, int64_t n0, int mother, double param, double dt, const double* scales_host, int nrows,
                          void* xbar_dev, int64_t xbar_ld, int accumulate);
 
+/* ---- gradients with respect to the scales and Morlet's f0 ---------------------------------------------------------------------
+ * cwt_adjoint_rows (hop = 1, ncols = n0) or cwt_adjoint_rows_hop (hop >= 2, ncols = ceil(n0 / hop), the rules of that call) with
+ * the derivatives of L = Re sum conj(G) W with respect to the continuous parameters of the filter bank beside xbar.  The filter of
+ * row j is F_j[k] = amp_j g(a_j k), amp_j ~ sqrt(s_j), a_j = 2 pi s_j / (nfft dt); its derivative is F_j times a real polynomial
+ * in f = a_j k:
+ *     mother       g(f)                      q(f) = (dF/d ln s) / F      r(f) = (dF/d f0) / F
+ *     Morlet(f0)   exp(-(f - f0)^2 / 2)      1/2 - f (f - f0)            f - f0
+ *     Paul(m)      f^m exp(-f),  f > 0       1/2 + m - f                 0
+ *     DOG(m)       f^m exp(-f^2 / 2)         1/2 + m - f^2               0
+ * With term_j[k] = (F_j[k] / nfft) conj(DFT_nfft(pad G_j)[k]), the summand of cwt_adjoint_rows' accumulator,
+ *     sgrad[j][0] = dL/d ln s_j = Re sum_{k in band_j} q(a_j k) term_j[k] xhat[k]            (dL/d s_j = sgrad[j][0] / s_j)
+ *     sgrad[j][1] = row j's share of dL/d param = Re sum_k r(a_j k) term_j[k] xhat[k]        (Morlet; 0 for Paul and DOG),
+ * summed over the nbatch signals.  xhat_dev: the signals' nfft-point spectra as cwt_forward_fft or cwt_transform* write them
+ * (signal b at xhat_dev + b xhat_ld, xhat_ld >= nfft for a batch); sgrad_dev: nrows x 2 doubles on the device, for both
+ * precisions, written, or added to with accumulate = 1 (the one flag serves xbar and sgrad).  xbar_dev may be NULL: the
+ * accumulator, its nfft-point transform and the trim are then skipped and sgrad alone is computed.
+ * Here EVERY row takes the general path of the adjoint -- also the rows of form P, whatever "adjoint_poly" says: the reduction
+ * reads the nfft-point (hop: M-point) spectra of the rows of G that this path forms.  xbar is bit-identical to cwt_adjoint_rows
+ * with "adjoint_poly" = 0, and to cwt_adjoint_rows_hop.  The band of a row is the forward's support (bins below the plan's
+ * accuracy target of the filter's peak count as zero in the gradient too).
+ * Deterministic: a band is cut into slices of 2048 consecutive bins; a thread sums its bins in ascending order, a workgroup adds
+ * its threads in a fixed tree, the slices and then the signals are added in ascending order in double; no atomics.  The bits of
+ * sgrad[j] depend on (nfft, hop, the row's band) and the order of the signals, not on the rows around it, the plan's max_rows or
+ * the stream.  The row table and its cache entry are cwt_transform's.  Built-in mothers only.  Refused with CWT_EINVAL before
+ * anything is queued: what cwt_adjoint_rows (hop = 1) or cwt_adjoint_rows_hop refuses, hop < 1, a NULL xhat_dev or sgrad_dev.   */
+int cwt_adjoint_rows_scales(cwt_plan* plan, const void* G_dev, int nbatch, int64_t g_batch_ld, int64_t ldg, int64_t ncols,
+                            int64_t hop, int64_t n0, const void* xhat_dev, int64_t xhat_ld, int mother, double param, double dt,
+                            const double* scales_host, int nrows, void* xbar_dev, int64_t xbar_ld, int accumulate,
+                            double* sgrad_dev);
+
 /* The same two steps at a transform length n0 that is NOT a power of two -- what the reference computes when pyfftw is
  * installed: helpers.py:15-19 then passes n = len(signal), i.e. no zero padding and circular edges -- by Bluestein's
  * chirp-z identity on this plan's power-of-two engine.  The plan must have nfft >= 2*n0 - 1.  xhat_dev: n0 complex

@@ -63,6 +63,8 @@ SYMBOLS = [
                                          C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_int, _P, C.c_int64, C.c_int64]),
     ("cwt_adjoint_rows_hop", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double,
                                        C.c_double, C.POINTER(C.c_double), C.c_int, _P, C.c_int64, C.c_int]),
+    ("cwt_adjoint_rows_scales", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64,
+                                          C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int, _P, C.c_int64, C.c_int, _P]),
     ("cwt_forward_fft_n", C.c_int, [_P, _P, C.c_int64, _P]),
     ("cwt_transform_rows_n", C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double),
                                        C.c_int, _P, C.c_int64]),
@@ -508,6 +510,20 @@ class Plan:
         self.lib.check(self.lib.cwt_adjoint_rows_hop(self.h, _P(G_dev), nbatch, g_batch_ld, ldg, -(-n0 // hop), hop, n0, mother,
                                                      float(param), float(dt), _dptr(s), s.size, _P(xbar_dev), xbar_ld,
                                                      int(bool(accumulate))))
+
+    @_locked
+    def adjoint_rows_scales(self, G_dev: int, nbatch: int, g_batch_ld: int, ldg: int, hop, n0: int, xhat_dev: int, xhat_ld: int,
+                            mother: int, param: float, dt: float, scales, xbar_dev, xbar_ld: int, sgrad_dev: int,
+                            accumulate: bool = False):
+        """`adjoint_rows` (hop None or 1) or `adjoint_rows_hop` with the gradients with respect to the scales and f0
+        (cwt_adjoint_rows_scales): xhat_dev the signals' nfft-point spectra, sgrad_dev nrows x 2 doubles on the device
+        ([j, 0] = dL/d ln s_j, [j, 1] = row j's share of dL/d f0); xbar_dev = None: sgrad alone."""
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        hop = 1 if hop is None else int(hop)
+        self.lib.check(self.lib.cwt_adjoint_rows_scales(self.h, _P(G_dev), nbatch, g_batch_ld, ldg, -(-n0 // hop), hop, n0,
+                                                        _P(xhat_dev), xhat_ld, mother, float(param), float(dt), _dptr(s), s.size,
+                                                        _P(xbar_dev) if xbar_dev else None, xbar_ld, int(bool(accumulate)),
+                                                        _P(sgrad_dev)))
 
     @_locked
     def forward_fft_n(self, x_dev: int, n0: int, xhat_dev: int):

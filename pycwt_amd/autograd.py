@@ -1,14 +1,16 @@
 """Differentiable CWT for PyTorch: ``cwt_torch`` runs the transform on torch's current stream (``parallel.HipEngine``) and
 its backward through the HIP adjoint of the rows (``cwt_adjoint_rows``): dL/dx = Re(A^H dL/dW) for the real input x, with no
 dense filter bank and no activation saved but the geometry of the call.  With ``hop=h`` forward and backward work on every
-h-th column only (``cwt_transform_hop``, ``cwt_adjoint_rows_hop``): nothing of rows x n0 elements exists in either."""
+h-th column only (``cwt_transform_hop``, ``cwt_adjoint_rows_hop``): nothing of rows x n0 elements exists in either.  With
+``scales=`` (a torch tensor) and, for Morlet, ``f0=`` the transform is differentiable in those too (``cwt_adjoint_rows_scales``:
+one reduction over each row's band on the spectra the adjoint forms anyway)."""
 import threading
 
 import numpy as np
 
 from . import _hip
 from .parallel import HipEngine
-from .wavelet import _check_hop, _check_parameter_wavelet, _device_id, _geometry
+from .wavelet import _check_hop, _check_parameter_wavelet, _coi, _device_id, _geometry, _nan_rows, _next_pow2
 
 _engines: dict = {}       # (nfft, precision, device, library) -> HipEngine: keeps the plan and its cached row tables
 _engines_lock = threading.Lock()
@@ -119,14 +121,134 @@ def _function(torch):
             del G
             return xbar, None, None, None, None, None, None
 
-    return CwtRows, CwtPower
+    def scale_backward(ctx, x, G, needs):
+        """The backward of the two Functions below for the cotangent G of W (complex, contiguous): (xbar, grad_scales, grad_f0),
+        None where no gradient is asked.  Without a scale or f0 gradient it queues what CwtRows.backward queues."""
+        eng, kind, param, dt, sj, tol, hop, n0, keep, scales, f0 = ctx.geometry
+        real_t = x.dtype
+        need_x, need_s, need_f = needs
+        rows = G.shape[-2]
+        nb = G.shape[0] if G.dim() == 3 else 1
+        xbar = torch.empty(tuple(G.shape[:-2]) + (n0,), dtype=real_t, device=G.device) if need_x or not (need_s or need_f) else None
+        _on_current_stream(torch, eng, G.device)
+        eng.plan.set_tolerance(tol)
+        if not (need_s or need_f):
+            if hop is None:
+                eng.plan.adjoint_rows(G.data_ptr(), nb, rows * n0, n0, n0, kind, param, dt, sj, xbar.data_ptr(), n0)
+            else:
+                eng.adjoint_rows_hop(G, n0, hop, kind, param, dt, sj, xbar)
+            return xbar, None, None
+        xs = x if x.dim() == 2 else x[None]
+        xhat = eng._spectra(xs, G)                              # the signals' spectra, recomputed: x alone was saved
+        eng.forward(xs, n0, xhat)
+        sgrad = torch.empty((rows, 2), dtype=torch.float64, device=G.device)
+        eng.adjoint_rows_scales(G, n0, hop, xhat, kind, param, dt, sj, xbar, sgrad)
+        gs = gf = None
+        if need_s:                                              # d/ds = (d/d ln s) / s; the rows Paul's NaN rule dropped get 0
+            part = sgrad[:, 0] / torch.as_tensor(sj, dtype=torch.float64, device=sgrad.device)
+            gs = torch.zeros(scales.shape, dtype=torch.float64, device=sgrad.device)
+            gs[torch.as_tensor(keep, device=sgrad.device)] = part
+            gs = gs.to(scales.device)
+        if need_f:
+            gf = sgrad[:, 1].sum().to(f0.device)
+        return xbar, gs, gf
+
+    class CwtRowsScales(torch.autograd.Function):
+        """CwtRows with `scales` (and `f0`) as differentiable inputs; their values reach the kernels through `sj` and `param`."""
+        @staticmethod
+        def forward(ctx, x, scales, f0, eng, kind, param, dt, sj, hop, keep):
+            n0 = x.shape[-1]
+            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+            W = torch.empty(tuple(x.shape[:-1]) + (sj.size, n0 if hop is None else -(-n0 // hop)), dtype=cplx_t, device=x.device)
+            tol = _tolerance()
+            _on_current_stream(torch, eng, x.device)
+            eng.plan.set_tolerance(tol)
+            if hop is None:
+                eng.transform(x, n0, None, kind, param, dt, sj, W, n0)
+            else:
+                eng.transform_hop(x, n0, hop, eng.plan.OUT_W, kind, param, dt, sj, W)
+            ctx.save_for_backward(x)
+            ctx.geometry = (eng, kind, param, dt, sj, tol, hop, n0, keep, scales, f0)
+            return W
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gW):
+            (x,) = ctx.saved_tensors
+            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+            g = gW.to(cplx_t).resolve_conj().contiguous()
+            return scale_backward(ctx, x, g, ctx.needs_input_grad[:3]) + (None,) * 7
+
+    class CwtPowerScales(torch.autograd.Function):
+        """CwtPower with `scales` (and `f0`) as differentiable inputs."""
+        @staticmethod
+        def forward(ctx, x, scales, f0, eng, kind, param, dt, sj, hop, keep):
+            n0 = x.shape[-1]
+            P = torch.empty(tuple(x.shape[:-1]) + (sj.size, n0 if hop is None else -(-n0 // hop)), dtype=x.dtype, device=x.device)
+            tol = _tolerance()
+            _on_current_stream(torch, eng, x.device)
+            eng.plan.set_tolerance(tol)
+            if hop is None:
+                eng.transform_power(x, n0, None, kind, param, dt, sj, P, n0)
+            else:
+                eng.transform_hop(x, n0, hop, eng.plan.OUT_POWER, kind, param, dt, sj, P)
+            ctx.save_for_backward(x)
+            ctx.geometry = (eng, kind, param, dt, sj, tol, hop, n0, keep, scales, f0)
+            return P
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gP):
+            (x,) = ctx.saved_tensors
+            eng, kind, param, dt, sj, tol, hop, n0 = ctx.geometry[:8]
+            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+            q = gP.to(x.dtype).contiguous()
+            G = torch.empty(q.shape, dtype=cplx_t, device=q.device)
+            _on_current_stream(torch, eng, q.device)
+            eng.plan.set_tolerance(tol)
+            if hop is None:                                      # G = 2 gP W, as in CwtPower.backward
+                eng.transform_weighted(x, n0, None, kind, param, dt, sj, q, 2.0, G, n0)
+            else:
+                eng.transform_hop(x, n0, hop, eng.plan.OUT_WEIGHTED, kind, param, dt, sj, G, q, 2.0)
+            out = scale_backward(ctx, x, G, ctx.needs_input_grad[:3])
+            del G
+            return out + (None,) * 7
+
+    return CwtRows, CwtPower, CwtRowsScales, CwtPowerScales
 
 
 _fn = None
 
 
-def _prepare(name, x, dt, dj, s0, J, wavelet, freqs, pad, hop=None):
-    """The checks, grid and engine of one call of `name` (cwt_torch, cwt_power_torch)."""
+def _learnable(name, torch, x, dj, s0, J, freqs, mother, scales, f0):
+    """The checks of `scales=` and `f0=`: (the mother of this call, the scales as a float64 NumPy array or None)."""
+    if f0 is not None:
+        from .mothers import Morlet
+        if type(mother) is not Morlet:
+            raise ValueError(f"{name}: f0= is Morlet's parameter (Paul, DOG and duck-typed mothers have no differentiable one)")
+        if not torch.is_tensor(f0) or f0.dim() != 0 or f0.dtype != torch.float64:
+            raise ValueError(f"{name}: f0 must be a 0-dim float64 torch tensor")
+        v = float(f0.detach())
+        if not np.isfinite(v):
+            raise ValueError(f"{name}: f0 must be finite")
+        mother = Morlet(v)
+    if scales is None:
+        return mother, None
+    if not (dj == 1 / 12 and s0 == -1 and J == -1 and freqs is None):
+        raise ValueError(f"{name}: scales= replaces dj, s0, J and freqs; leave those at their defaults")
+    if not torch.is_tensor(scales) or scales.dim() != 1 or scales.dtype != torch.float64 or scales.numel() < 1:
+        raise ValueError(f"{name}: scales must be a 1-D float64 torch tensor")
+    if scales.device.type != "cpu" and scales.device != x.device:
+        raise ValueError(f"{name}: scales must live on the CPU or on x's device")
+    sj = np.array(scales.detach().cpu().numpy(), dtype=np.float64)        # (a device tensor: one read-back per call)
+    if not (np.isfinite(sj).all() and (sj > 0).all()):
+        raise ValueError(f"{name}: scales must be positive and finite")
+    return mother, sj
+
+
+def _prepare(name, x, dt, dj, s0, J, wavelet, freqs, pad, hop=None, scales=None, f0=None):
+    """The checks, grid and engine of one call of `name` (cwt_torch, cwt_power_torch).  With scales= or f0= a ninth value: the
+    mask of the scales that W keeps (Paul's NaN-row rule), for the gradient's way back."""
     import torch
     if not pad:
         raise ValueError(f"{name}: pad=False (Bluestein transforms of any length) has no adjoint; use pad=True")
@@ -141,9 +263,20 @@ def _prepare(name, x, dt, dj, s0, J, wavelet, freqs, pad, hop=None):
     if x.device.type != "cuda" and lib.backend().startswith("hip"):
         raise RuntimeError(f"{name} needs a tensor on a GPU (the HIP kernels cannot read host memory)")
     n0 = int(x.shape[-1])
-    N, sj, freqs, coi, _, bad = _geometry(mother, n0, dt, dj, s0, J, freqs, True)
+    learn = scales is not None or f0 is not None
+    given = None
+    if learn:
+        mother, given = _learnable(name, torch, x, dj, s0, J, freqs, mother, scales, f0)
+    if given is None:
+        N, sj, freqs, coi, _, bad = _geometry(mother, n0, dt, dj, s0, J, freqs, True)
+    else:                                                        # the grid is the caller's: no cache entry per step
+        N, sj = _next_pow2(n0), given
+        freqs, coi = 1 / (mother.flambda() * sj), _coi(mother, n0, dt)
+        bad = _nan_rows(mother, sj, N, dt)
+        bad = bad if bad.any() else None
+    keep = np.ones(sj.size, dtype=bool)
     if bad is not None and not bad.all():
-        sj, freqs = sj[~bad], np.asarray(freqs)[~bad]
+        sj, freqs, keep = sj[~bad], np.asarray(freqs)[~bad], ~bad
     sj, freqs, coi = np.array(sj, dtype=np.float64), np.array(freqs), np.array(coi)
     if hop is not None:
         hop = _check_hop(hop, N, mother)
@@ -152,10 +285,12 @@ def _prepare(name, x, dt, dj, s0, J, wavelet, freqs, pad, hop=None):
     nb = int(x.shape[0]) if x.dim() == 2 else 1
     precision = 64 if x.dtype == torch.float64 else 32
     eng = _engine(torch, N, precision, nb * sj.size, x.device, lib)
+    if learn:
+        return torch, eng, kind, float(param), sj, freqs, coi, hop, keep
     return torch, eng, kind, float(param), sj, freqs, coi, hop
 
 
-def cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=True, hop=None):
+def cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=True, hop=None, *, scales=None, f0=None):
     """Continuous wavelet transform of a torch tensor, differentiable with respect to it.
 
     x: (n0,) or (B, n0), float64 or float32.  Returns ``(W, sj, freqs, coi)``: W complex128 / complex64 on x's device,
@@ -168,8 +303,28 @@ def cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=T
     hop=h (a power of two, 16 <= padded length / h <= 4096): W has ceil(n0 / h) columns, equal to columns ``::h`` of the
     undecimated W to rounding, and coi is ``coi[::h]``; the forward computes nothing else (``cwt_transform_hop``) and the
     backward is ``cwt_adjoint_rows_hop`` of the cotangent.  The columns are a SAMPLE of W, not an average over the hop:
-    choosing h against the smallest scale is the caller's business."""
+    choosing h against the smallest scale is the caller's business.
+
+    scales=t (keyword only; a 1-D float64 torch tensor, positive and finite, on the CPU or on x's device) replaces the grid of
+    ``dj, s0, J, freqs``, which must then stay at their defaults (ValueError otherwise), and makes W differentiable with
+    respect to t.  f0=t0 (a 0-dim float64 tensor; Morlet only, ValueError for Paul, DOG or a duck-typed mother) replaces the
+    wavelet object's f0 for this call and makes W differentiable with respect to it.  sj, freqs, coi come back as NumPy
+    arrays of the detached values; scales that Paul's NaN-row rule drops from W get gradient 0.  The backward is ONE call of
+    ``cwt_adjoint_rows_scales``: the adjoint with every row on its general path (the rows of polynomial form included) plus
+    one reduction over each row's band, ``grad_scales = (dL/d ln s) / s``; x is saved and its spectrum recomputed there;
+    x.grad is computed only if x requires it.  If neither tensor requires a gradient the backward is the one of the call
+    without them.  Once differentiable.  A CPU tensor of scales is the cheap case: a tensor on the device costs one read-back
+    (a host synchronisation) per call, because the grid is classified on the host.  A step with fresh scales re-classifies
+    the grid there each time -- 1.9 ms for 256 scales at 2^20 points on the build machine (EXPERIMENTS.md); a whole step
+    measured 8.2 ms against 6.0 with fixed scales (profiles/scale_grad_bench.txt) -- and a plan caches four row tables, so at
+    most four distinct grids alternate for free."""
     global _fn
+    if scales is not None or f0 is not None:
+        torch, eng, kind, param, sj, freqs, coi, hop, keep = _prepare("cwt_torch", x, dt, dj, s0, J, wavelet, freqs, pad, hop, scales, f0)
+        if _fn is None:
+            _fn = _function(torch)
+        W = _fn[2].apply(x.contiguous(), scales, f0, eng, kind, param, float(dt), sj, hop, keep)
+        return W, sj, freqs, coi
     torch, eng, kind, param, sj, freqs, coi, hop = _prepare("cwt_torch", x, dt, dj, s0, J, wavelet, freqs, pad, hop)
     if _fn is None:
         _fn = _function(torch)
@@ -177,7 +332,7 @@ def cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=T
     return W, sj, freqs, coi
 
 
-def cwt_power_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=True, hop=None):
+def cwt_power_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=True, hop=None, *, scales=None, f0=None):
     """The scalogram ``|W|^2`` of a torch tensor, differentiable with respect to it: ``cwt_torch(x, ...)[0].abs() ** 2`` without
     W -- neither written by the forward nor kept for the backward.
 
@@ -189,8 +344,18 @@ def cwt_power_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None,
 
     hop=h as in ``cwt_torch``: P has ceil(n0 / h) columns, samples of |W|^2 at columns ``::h`` (not its mean over the hop), coi
     is ``coi[::h]``.  Forward, the transient G of the backward (``cwt_transform_hop`` with the weighted output) and its
-    adjoint (``cwt_adjoint_rows_hop``) are all of rows x ceil(n0 / h) elements; x alone is saved."""
+    adjoint (``cwt_adjoint_rows_hop``) are all of rows x ceil(n0 / h) elements; x alone is saved.
+
+    scales=, f0= (keyword only) as in ``cwt_torch``: P is differentiable with respect to them; the backward builds the same
+    G = 2 gP W and hands it to ``cwt_adjoint_rows_scales``."""
     global _fn
+    if scales is not None or f0 is not None:
+        torch, eng, kind, param, sj, freqs, coi, hop, keep = _prepare("cwt_power_torch", x, dt, dj, s0, J, wavelet, freqs, pad, hop, scales,
+                                                                      f0)
+        if _fn is None:
+            _fn = _function(torch)
+        P = _fn[3].apply(x.contiguous(), scales, f0, eng, kind, param, float(dt), sj, hop, keep)
+        return P, sj, freqs, coi
     torch, eng, kind, param, sj, freqs, coi, hop = _prepare("cwt_power_torch", x, dt, dj, s0, J, wavelet, freqs, pad, hop)
     if _fn is None:
         _fn = _function(torch)

@@ -365,7 +365,7 @@ int cwt_plan_destroy(cwt_plan* p) {
   for (auto& t : p->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   for (auto e : p->free_events) (void)hipEventDestroy(e);
   void* bufs[] = {p->tw_all, p->twn_lo, p->weights_dev, p->Z, p->xs, p->xm, p->xsa, p->pcoef, p->pband, p->range_dev, p->hx, p->hxhat, p->hW,
-                  p->bs_khat[0], p->bs_khat[1], p->bs_a, p->bs_spec, p->bs_par, p->adj_spec, p->adj_acc, p->hop_z};
+                  p->bs_khat[0], p->bs_khat[1], p->bs_a, p->bs_spec, p->bs_par, p->adj_spec, p->adj_acc, p->hop_z, p->sgrad_part};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (auto& t : p->slots) {
     if (t.gt_dev) (void)hipFree(t.gt_dev);
@@ -642,7 +642,7 @@ int cwt_adjoint_rows(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch
   if (rc) return rc;
   return by_precision(p, [&](auto t) {
     return adjoint_impl<decltype(t)>(p, G_dev, nbatch, g_batch_ld, ldg, ncols, mother_of(mother, param), nrows, xbar_dev, xbar_ld,
-                                     accumulate);
+                                     accumulate, nullptr);
   });
 }
 
@@ -849,7 +849,37 @@ int cwt_adjoint_rows_hop(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_b
   if (rc) return rc;
   return by_precision(p, [&](auto t) {
     return adjoint_hop_impl<decltype(t)>(p, G_dev, nbatch, g_batch_ld, ldg, ncols_h, logM, n0, mother_of(mother, param), nrows, xbar_dev,
-                                         xbar_ld, accumulate);
+                                         xbar_ld, accumulate, nullptr);
+  });
+}
+
+// cwt_adjoint_rows (hop = 1) or cwt_adjoint_rows_hop with the gradients with respect to the scales and f0 beside xbar: the checks of
+// those two, the same row table, every row through the general path (sgrad_partial reads the spectra it forms).
+int cwt_adjoint_rows_scales(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld, int64_t ldg, int64_t ncols, int64_t hop,
+                            int64_t n0, const void* xhat_dev, int64_t xhat_ld, int mother, double param, double dt, const double* scales,
+                            int nrows, void* xbar_dev, int64_t xbar_ld, int accumulate, double* sgrad_dev) {
+  if (!p || !G_dev || !scales || !xhat_dev || !sgrad_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (mother == MOTHER_TABLE) return fail(CWT_EINVAL, "adjoint: a built-in mother is needed (a filter bank has no adjoint here)");
+  int logM = 0;
+  if (hop == 1) {
+    if (nbatch < 1 || nrows < 1) return fail(CWT_EINVAL, "need nbatch >= 1 and nrows >= 1");
+    if (n0 < 1 || n0 > p->N || ncols != n0 || ldg < ncols) return fail(CWT_EINVAL, "hop = 1: need 1 <= ncols = n0 <= nfft and ldg >= ncols");
+  } else if (int rc = check_hop(p, nbatch, nrows, n0, hop, ldg, ncols, &logM)) {
+    return rc;
+  }
+  if (xbar_dev && xbar_ld < n0) return fail(CWT_EINVAL, "xbar_ld must be >= n0");
+  if (nbatch > 1 && g_batch_ld < int64_t(nrows) * ldg) return fail(CWT_EINVAL, "g_batch_ld must be >= nrows * ldg");
+  if (nbatch > 1 && xhat_ld < p->N) return fail(CWT_EINVAL, "xhat_ld must be >= nfft");
+  HIPCHECK(hipSetDevice(p->device));
+  const int rc = prepare_rows_table(p, true, mother, param, dt, scales, nrows, n0, n0);
+  if (rc) return rc;
+  const cwtd::ScaleGrad sg{xhat_dev, xhat_ld, sgrad_dev};
+  return by_precision(p, [&](auto t) {
+    if (hop == 1)
+      return adjoint_impl<decltype(t)>(p, G_dev, nbatch, g_batch_ld, ldg, ncols, mother_of(mother, param), nrows, xbar_dev, xbar_ld,
+                                       accumulate, &sg);
+    return adjoint_hop_impl<decltype(t)>(p, G_dev, nbatch, g_batch_ld, ldg, ncols, logM, n0, mother_of(mother, param), nrows, xbar_dev,
+                                         xbar_ld, accumulate, &sg);
   });
 }
 

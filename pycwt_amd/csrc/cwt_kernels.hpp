@@ -855,3 +855,4 @@ k_pass_b_ct(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
 #include "cwt_kernels_rows.hpp"      // overlap-save, band-passed, polynomial rows
 #include "cwt_kernels_callers.hpp"   // coherence helpers, Bluestein, icwt, spectrum range
 #include "cwt_kernels_hop.hpp"       // decimated output: folded spectrum, short row transforms, their adjoint
+#include "cwt_kernels_sgrad.hpp"     // gradients with respect to the scales and f0: one reduction over each row's band

@@ -1078,19 +1078,67 @@ inline int upload_adjoint_rows(cwt_plan* p, int nrows, bool use_poly) {
   return CWT_OK;
 }
 
+// The optional argument set of adjoint_impl / adjoint_hop_impl (cwt_adjoint_rows_scales): the signals' N-point spectra and the
+// nrows x 2 doubles that receive dL/d ln s_j and row j's share of dL/d f0.  With it every row takes the general path, sgrad_partial
+// runs on each chunk's spectra right behind the accumulation and sgrad_sum once at the end; xbar_dev may then be NULL (no
+// accumulator, no N-point transform of it, no k_adj_out).
+struct ScaleGrad {
+  const void* xhat;
+  int64_t xhat_ld;
+  double* out;
+};
+
+// slices of the widest band of the table (the stride of the slice sums in plan scratch) and the scratch itself
+template <typename T>
+int sgrad_prepare(cwt_plan* p, int nbatch, int nrows, int* nslices) {
+  int ns = 1;
+  for (const RowDesc& r : p->rt->base) ns = std::max(ns, sgrad_slices(r.nband));
+  *nslices = ns;
+  return grow(&p->sgrad_part, &p->sgrad_part_bytes, size_t(nbatch) * size_t(nrows) * size_t(ns) * 2 * sizeof(T), p->stream);
+}
+
+// sgrad_partial on the chunk [first, first + cnt) of the rows at rt->adj_dev (every row, in out_row order) for signal b
+template <typename T>
+int launch_sgrad_partial(cwt_plan* p, const ScaleGrad& sg, const cplx<T>* spec, int b, int first, int cnt, int nrows, const Mother& mo,
+                         int logM, int nslices) {
+  const cwt_plan::RowTable* rt = p->rt;
+  const cplx<T>* xhat = static_cast<const cplx<T>*>(sg.xhat) + size_t(b) * size_t(sg.xhat_ld);
+  T* part = static_cast<T*>(p->sgrad_part) + size_t(b) * size_t(nrows) * size_t(nslices) * 2;
+  return timed_launch(p, KC_SGRAD, [&] {
+    for (int r0 = 0; r0 < cnt; r0 += kMaxGridY) {
+      const int n = std::min(kMaxGridY, cnt - r0);
+      int gx = 1;                                           // slices of the widest band among these rows
+      for (int i = 0; i < n; ++i) gx = std::max(gx, sgrad_slices(rt->base[size_t(first + r0 + i)].nband));
+      hipLaunchKernelGGL((sgrad_partial<T>), dim3(unsigned(gx), unsigned(n)), dim3(SGRAD_THREADS), SGRAD_THREADS * sizeof(cplx<T>),
+                         p->stream, spec + (size_t(r0) << logM), xhat, rt->adj_dev + first + r0, mo, p->logN, logM, first + r0, nslices,
+                         part);
+    }
+  });
+}
+
+template <typename T>
+int launch_sgrad_sum(cwt_plan* p, const ScaleGrad& sg, int nbatch, int nrows, int nslices, int accumulate) {
+  return timed_launch(p, KC_SGRAD, [&] {
+    hipLaunchKernelGGL((sgrad_sum<T>), dim3(unsigned((nrows + SGRAD_THREADS - 1) / SGRAD_THREADS)), dim3(SGRAD_THREADS), 0, p->stream,
+                       static_cast<const T*>(p->sgrad_part), p->rt->adj_dev, nrows, nbatch, nslices, accumulate, sg.out);
+  });
+}
+
 // xbar_b (+)= Re A^H G_b for every signal b (cwt_hip.h).  Per signal: the accumulator is zeroed; the general rows go in chunks of
 // chunk_rows_of rows through the forward transform of their zero-padded inputs (cwt_fft_rows' kernels) and k_adj_accum; the
 // polynomial rows chunk by chunk through k_poly_moments, the K'-point transforms of k_poly_coef (in place) and k_poly_adj_accum;
 // one N-point transform of the accumulator gives xbar.  Fixed order throughout: a signal's bits do not depend on the batch.
 template <typename T>
 int adjoint_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld, int64_t ldg, int64_t ncols, const Mother& mo,
-                 int nrows, void* xbar_dev, int64_t xbar_ld, int accumulate) {
+                 int nrows, void* xbar_dev, int64_t xbar_ld, int accumulate, const ScaleGrad* sg) {
   cwt_plan::RowTable* rt = p->rt;
   const int logN = p->logN;
   const int64_t N = p->N;
-  const bool use_poly = p->adjoint_poly && rt->n_poly > 0;
+  const bool use_poly = !sg && p->adjoint_poly && rt->n_poly > 0;
   int rc = check_geometry(p);
   if (!rc) rc = upload_adjoint_rows(p, nrows, use_poly);
+  int nslices = 0;
+  if (!rc && sg) rc = sgrad_prepare<T>(p, nbatch, nrows, &nslices);
   if (rc) return rc;
   const int ngen = int(rt->adj_rows.size());
   const int chunk = ngen ? balanced_chunk(p, ngen) : 1;
@@ -1111,7 +1159,7 @@ int adjoint_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld,
   auto lds_of = [](int lp) { return ((size_t(1) << lp) + (size_t(1) << (lp - 4))) * sizeof(T); };
   for (int b = 0; b < nbatch; ++b) {
     const cplx<T>* G = static_cast<const cplx<T>*>(G_dev) + size_t(b) * size_t(g_batch_ld);
-    HIPCHECK(hipMemsetAsync(acc, 0, size_t(N) * sizeof(cplx<T>), p->stream));
+    if (xbar_dev) HIPCHECK(hipMemsetAsync(acc, 0, size_t(N) * sizeof(cplx<T>), p->stream));
     for (int first = 0; first < ngen; first += chunk) {
       const int cnt = std::min(chunk, ngen - first);
       for (int i = 0; i < cnt;) {                       // runs of consecutive rows of G: one forward transform call each
@@ -1122,12 +1170,14 @@ int adjoint_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld,
         if (rc) return rc;
         i += run;
       }
-      rc = timed_launch(p, KC_ADJOINT, [&] {
+      if (xbar_dev) rc = timed_launch(p, KC_ADJOINT, [&] {
         hipLaunchKernelGGL((k_adj_accum<T>), dim3(bins), dim3(256), 0, p->stream, static_cast<const cplx<T>*>(spec),
                            rt->adj_dev + first, cnt, mo, logN, acc);
       });
+      if (!rc && sg) rc = launch_sgrad_partial<T>(p, *sg, spec, b, first, cnt, nrows, mo, logN, nslices);
       if (rc) return rc;
     }
+    if (!xbar_dev) continue;
     for (size_t c = 0; use_poly && c < rt->poly_chunks.size(); ++c) {
       const auto& ch = rt->poly_chunks[c];
       const RowDesc* rows = rt->rows_dev + rt->poly_first + ch.row_first;
@@ -1166,6 +1216,7 @@ int adjoint_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld,
     });
     if (rc) return rc;
   }
+  if (sg) return launch_sgrad_sum<T>(p, *sg, nbatch, nrows, nslices, accumulate);
   return CWT_OK;
 }
 
@@ -1252,12 +1303,14 @@ int transform_hop_impl(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld,
 // and the trim to n0 are those of adjoint_impl.  Every row takes this path, in row order.
 template <typename T>
 int adjoint_hop_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld, int64_t ldg, int64_t ncols_h, int logM,
-                     int64_t n0, const Mother& mo, int nrows, void* xbar_dev, int64_t xbar_ld, int accumulate) {
+                     int64_t n0, const Mother& mo, int nrows, void* xbar_dev, int64_t xbar_ld, int accumulate, const ScaleGrad* sg) {
   cwt_plan::RowTable* rt = p->rt;
   const int logN = p->logN;
   const int64_t N = p->N, M = int64_t(1) << logM;
   int rc = check_geometry(p);
   if (!rc) rc = upload_adjoint_rows(p, nrows, false);
+  int nslices = 0;
+  if (!rc && sg) rc = sgrad_prepare<T>(p, nbatch, nrows, &nslices);
   if (rc) return rc;
   const int chunk = int(std::max<size_t>(1, std::min<size_t>(size_t(nrows), kHopScratchBytes / (size_t(M) * sizeof(cplx<T>)))));
   rc = grow(&p->adj_spec, &p->adj_spec_bytes, std::max(size_t(chunk) * size_t(M), size_t(N)) * sizeof(cplx<T>), p->stream);
@@ -1270,7 +1323,7 @@ int adjoint_hop_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch
   const unsigned bins = unsigned((N + 255) / 256);
   for (int b = 0; b < nbatch; ++b) {
     const cplx<T>* G = static_cast<const cplx<T>*>(G_dev) + size_t(b) * size_t(g_batch_ld);
-    HIPCHECK(hipMemsetAsync(acc, 0, size_t(N) * sizeof(cplx<T>), p->stream));
+    if (xbar_dev) HIPCHECK(hipMemsetAsync(acc, 0, size_t(N) * sizeof(cplx<T>), p->stream));
     for (int first = 0; first < nrows; first += chunk) {
       const int cnt = std::min(chunk, nrows - first);
       rc = timed_launch(p, KC_FWD_SMALL, [&] {
@@ -1278,12 +1331,14 @@ int adjoint_hop_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch
                            p->stream, static_cast<const void*>(G + size_t(first) * size_t(ldg)), (const RowDesc*)nullptr, cnt, none,
                            tw_table<T>(p, logM), logM, logTB, long(ncols_h), long(ldg), spec, long(M), long(M));
       });
-      if (!rc) rc = timed_launch(p, KC_ADJOINT, [&] {
+      if (!rc && xbar_dev) rc = timed_launch(p, KC_ADJOINT, [&] {
         hipLaunchKernelGGL((hop_adj_accum<T>), dim3(bins), dim3(256), 0, p->stream, static_cast<const cplx<T>*>(spec),
                            rt->adj_dev + first, cnt, mo, logN, logM, acc);
       });
+      if (!rc && sg) rc = launch_sgrad_partial<T>(p, *sg, spec, b, first, cnt, nrows, mo, logM, nslices);
       if (rc) return rc;
     }
+    if (!xbar_dev) continue;
     rc = fft_rows_impl<T, IN_CPLX>(p, acc, N, 1, N, spec);
     if (rc) return rc;
     rc = timed_launch(p, KC_ADJOINT, [&] {
@@ -1293,6 +1348,7 @@ int adjoint_hop_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch
     });
     if (rc) return rc;
   }
+  if (sg) return launch_sgrad_sum<T>(p, *sg, nbatch, nrows, nslices, accumulate);
   return CWT_OK;
 }
 
@@ -1532,10 +1588,12 @@ int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g
   X int ar1_filter_impl<T>(cwt_plan*, const void*, int64_t, int64_t, double, void*);                                               \
   X int forward_fft_n_impl<T>(cwt_plan*, const void*, int64_t, void*);                                                              \
   X int transform_rows_n_impl<T>(cwt_plan*, const void*, int64_t, int, double, double, const double*, int, void*, int64_t);        \
-  X int adjoint_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int64_t, const Mother&, int, void*, int64_t, int);   \
+  X int adjoint_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int64_t, const Mother&, int, void*, int64_t, int,     \
+                        const ScaleGrad*);                                                                                          \
   X int transform_hop_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, const void*, int64_t, const Mother&, int, int, int, void*, \
                               const void*, double, int64_t, int64_t);                                                              \
-  X int adjoint_hop_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int64_t, int, int64_t, const Mother&, int, void*, int64_t, int);
+  X int adjoint_hop_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int64_t, int, int64_t, const Mother&, int, void*, int64_t, int, \
+                            const ScaleGrad*);
 
 #ifndef CWT_LAUNCH_TU
 CWT_LAUNCH_TEMPLATES(extern template, double)

@@ -163,6 +163,15 @@ class HipEngine:
         self.plan.adjoint_rows_hop(G.data_ptr(), nb, G.shape[-2] * G.shape[-1], G.shape[-1], hop, n0, kind, param, dt, sj,
                                    xbar.data_ptr(), xbar.shape[-1], accumulate)
 
+    def adjoint_rows_scales(self, G, n0, hop, xhat, kind, param, dt, sj, xbar, sgrad, accumulate=False):
+        """`adjoint_rows` / `adjoint_rows_hop` with the gradients with respect to the scales and f0 (cwt_adjoint_rows_scales):
+        G (rows, ld) or (batch, rows, ld) complex, xhat (N,) or (batch, N) the signals' spectra, sgrad (rows, 2) float64 on the
+        device, xbar (n0,) / (batch, ld_x) or None (sgrad alone).  hop None: the undecimated adjoint."""
+        nb = 1 if G.dim() == 2 else G.shape[0]
+        self.plan.adjoint_rows_scales(G.data_ptr(), nb, G.shape[-2] * G.shape[-1], G.shape[-1], hop, n0, xhat.data_ptr(),
+                                      xhat.shape[-1], kind, param, dt, sj, None if xbar is None else xbar.data_ptr(),
+                                      n0 if xbar is None else xbar.shape[-1], sgrad.data_ptr(), accumulate)
+
     def classify(self, kind, param, dt, sj, ncols):
         return self.plan.classify(kind, param, dt, sj, ncols, True)
 
