@@ -371,6 +371,36 @@ int cwt_adjoint_rows_hop(cwt_plan* plan, const void* G_dev, int nbatch, int64_t 
                          int64_t hop, int64_t n0, int mother, double param, double dt, const double* scales_host, int nrows,
                          void* xbar_dev, int64_t xbar_ld, int accumulate);
 
+/* ---- time-pooled scalogram: window means of |W|^2 -----------------------------------------------------------------------------
+ * For callers that want the MEAN power over a window, not a sample of W (a scalogram image, a feature on a coarse time grid,
+ * global and scale-averaged spectra): at the small scales |W|^2 varies much faster than any useful hop, and power is not linear in
+ * W, so no folding of the spectrum gives it.  With h = pool (a power of two) and m < ncols_p = ceil(n0 / h):
+ *   Pbar[j, m] = (1 / c_m) sum_{n = m h}^{min((m + 1) h, n0) - 1} |W[j, n]|^2,      c_m = min((m + 1) h, n0) - m h,
+ * W exactly what cwt_transform computes for the same plan, scales, tolerance and options.  Every window lies inside [0, n0): no
+ * padded column enters a mean; only the last window can be short.  Pooled W (a mean of complex values) is not offered.
+ *   Fused where.  The call classifies and schedules as cwt_transform_power does (the same row table and cache entry: neither the
+ *   output nor the pool is part of its key, pooled, power and transform calls of the same scales alternate freely).  The rows of
+ *   polynomial form evaluate their columns and sum the windows in one kernel and store n0 / h reals instead of n0.  Every other
+ *   form runs its unchanged power kernel into plan scratch, and one reduction kernel on the caller's stream turns the scratch into
+ *   window means.  Pooling inside the overlap-save tile kernels is not built.
+ *   Scratch.  (rows not of polynomial form) x n0 reals of the plan's precision, one signal's, grown on demand -- never nrows x n0.
+ *   pool      a power of two with 2 <= pool <= nfft.  Other values are not built.
+ *   ncols_p   must be ceil(n0 / pool).  P_dev is nbatch x nrows x ldp reals; columns ncols_p .. ldp - 1 and rows not asked for are
+ *             left untouched.
+ *   nbatch    signals (signal b at x_dev + b x_ld, its rows at P_dev + b nrows ldp, its spectrum -- written by the call -- at
+ *             xhat_dev + b nfft).  xhat_dev may be NULL (plan scratch).  A batch runs signal by signal through the single-signal
+ *             path, so its polynomial rows pool in the kernel (cwt_transform_batch has no polynomial form).
+ * Deterministic: a window is summed in one fixed order that depends on (nfft, pool, the row's interval length) alone -- runs of
+ * consecutive columns in ascending order inside a thread, a fixed binary tree over the threads, no floating-point atomics.  A
+ * signal's bits do not depend on the batch around it, on n0 beyond the last window's length, or on the schedule.  One NaN or inf
+ * sample makes every element of that signal NaN.  Built-in mothers and power-of-two lengths only: no filter banks of the caller's,
+ * no Bluestein lengths; a variant that starts from a spectrum alone is NOT BUILT (the overlap-save rows need the signal).
+ * Refused with CWT_EINVAL before anything is queued: a pool that is not a power of two, is < 2 or > nfft, ncols_p != ceil(n0 /
+ * pool), ldp < ncols_p, NULL x_dev, P_dev or scales, nbatch * nrows > max_rows.                                               */
+int cwt_transform_pool(cwt_plan* plan, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother, double param,
+                       double dt, const double* scales_host, int nrows, int64_t pool, void* xhat_dev, void* P_dev, int64_t ldp,
+                       int64_t ncols_p);
+
 /* ---- gradients with respect to the scales and Morlet's f0 ---------------------------------------------------------------------
  * cwt_adjoint_rows (hop = 1, ncols = n0) or cwt_adjoint_rows_hop (hop >= 2, ncols = ceil(n0 / hop), the rules of that call) with
  * the derivatives of L = Re sum conj(G) W with respect to the continuous parameters of the filter bank beside xbar.  The filter of

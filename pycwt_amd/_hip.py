@@ -63,6 +63,8 @@ SYMBOLS = [
                                          C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_int, _P, C.c_int64, C.c_int64]),
     ("cwt_adjoint_rows_hop", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double,
                                        C.c_double, C.POINTER(C.c_double), C.c_int, _P, C.c_int64, C.c_int]),
+    ("cwt_transform_pool", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double),
+                                     C.c_int, C.c_int64, _P, _P, C.c_int64, C.c_int64]),
     ("cwt_adjoint_rows_scales", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64,
                                           C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int, _P, C.c_int64, C.c_int, _P]),
     ("cwt_forward_fft_n", C.c_int, [_P, _P, C.c_int64, _P]),
@@ -492,6 +494,15 @@ class Plan:
         self.lib.check(self.lib.cwt_transform_hop(self.h, _P(x_dev), nbatch, x_ld, n0, mother, float(param), float(dt), _dptr(s),
                                                   s.size, hop, _P(xhat_dev) if xhat_dev else None, output, _P(out_dev),
                                                   _P(Q_dev) if Q_dev else None, float(alpha), ld, -(-n0 // hop)))
+
+    @_locked
+    def transform_pool(self, x_dev: int, nbatch: int, x_ld: int, n0: int, mother: int, param: float, dt: float, scales, pool: int,
+                       xhat_dev, P_dev: int, ldp: int):
+        """Means of |W|^2 over windows of `pool` columns for nbatch signals (cwt_transform_pool): P nbatch x nrows x ldp reals,
+        ceil(n0 / pool) columns written per row.  xhat_dev = None: plan scratch."""
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        self.lib.check(self.lib.cwt_transform_pool(self.h, _P(x_dev), nbatch, x_ld, n0, mother, float(param), float(dt), _dptr(s),
+                                                   s.size, pool, _P(xhat_dev) if xhat_dev else None, _P(P_dev), ldp, -(-n0 // pool)))
 
     @_locked
     def transform_rows_hop(self, xhat_dev: int, nbatch: int, xhat_ld: int, n0: int, mother: int, param: float, dt: float, scales,

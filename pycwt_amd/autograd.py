@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _hip
 from .parallel import HipEngine
-from .wavelet import _check_hop, _check_parameter_wavelet, _coi, _device_id, _geometry, _nan_rows, _next_pow2
+from .wavelet import _check_hop, _check_pool, _pool_coi, _check_parameter_wavelet, _coi, _device_id, _geometry, _nan_rows, _next_pow2
 
 _engines: dict = {}       # (nfft, precision, device, library) -> HipEngine: keeps the plan and its cached row tables
 _engines_lock = threading.Lock()
@@ -48,6 +48,16 @@ def _tolerance():
 def _function(torch):
     from torch.autograd.function import once_differentiable
 
+    def pooled_columns(n0, hop, pool):
+        return n0 if hop is None and pool is None else -(-n0 // (pool if pool is not None else hop))
+
+    def spread_over_windows(q, n0, pool):
+        """gP (..., rows, ceil(n0 / pool)) -> (..., rows, n0): gP[j, n // pool] / c_m, c_m the columns of window m inside n0"""
+        ncols = q.shape[-1]
+        count = torch.full((ncols,), float(pool), dtype=q.dtype, device=q.device)
+        count[-1] = float(n0 - (ncols - 1) * pool)
+        return (q / count).repeat_interleave(pool, dim=-1)[..., :n0].contiguous()
+
     class CwtRows(torch.autograd.Function):
         @staticmethod
         def forward(ctx, x, eng, kind, param, dt, sj, hop):
@@ -84,27 +94,31 @@ def _function(torch):
 
     class CwtPower(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, x, eng, kind, param, dt, sj, hop):
+        def forward(ctx, x, eng, kind, param, dt, sj, hop, pool):
             n0 = x.shape[-1]
-            P = torch.empty(tuple(x.shape[:-1]) + (sj.size, n0 if hop is None else -(-n0 // hop)), dtype=x.dtype, device=x.device)
+            P = torch.empty(tuple(x.shape[:-1]) + (sj.size, pooled_columns(n0, hop, pool)), dtype=x.dtype, device=x.device)
             tol = _tolerance()
             _on_current_stream(torch, eng, x.device)
             eng.plan.set_tolerance(tol)
-            if hop is None:
+            if pool is not None:
+                eng.transform_pool(x, n0, pool, kind, param, dt, sj, P)
+            elif hop is None:
                 eng.transform_power(x, n0, None, kind, param, dt, sj, P, n0)
             else:
                 eng.transform_hop(x, n0, hop, eng.plan.OUT_POWER, kind, param, dt, sj, P)
             ctx.save_for_backward(x)                             # the signal and the geometry: nothing of rows x n0 elements
-            ctx.geometry = (eng, kind, param, dt, sj, tol, hop)
+            ctx.geometry = (eng, kind, param, dt, sj, tol, hop, pool)
             return P
 
         @staticmethod
         @once_differentiable
         def backward(ctx, gP):
             (x,) = ctx.saved_tensors
-            eng, kind, param, dt, sj, tol, hop = ctx.geometry
+            eng, kind, param, dt, sj, tol, hop, pool = ctx.geometry
             cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
             q = gP.to(x.dtype).contiguous()
+            if pool is not None:                                 # the cotangent of |W|^2 at the full rate: gP / c_m on every column of window m
+                q = spread_over_windows(q, x.shape[-1], pool)
             rows, n0 = q.shape[-2], x.shape[-1]
             nb = q.shape[0] if q.dim() == 3 else 1
             G = torch.empty(q.shape, dtype=cplx_t, device=q.device)
@@ -119,7 +133,7 @@ def _function(torch):
                 eng.transform_hop(x, n0, hop, eng.plan.OUT_WEIGHTED, kind, param, dt, sj, G, q, 2.0)
                 eng.adjoint_rows_hop(G, n0, hop, kind, param, dt, sj, xbar)
             del G
-            return xbar, None, None, None, None, None, None
+            return xbar, None, None, None, None, None, None, None
 
     def scale_backward(ctx, x, G, needs):
         """The backward of the two Functions below for the cotangent G of W (complex, contiguous): (xbar, grad_scales, grad_f0),
@@ -182,18 +196,21 @@ def _function(torch):
     class CwtPowerScales(torch.autograd.Function):
         """CwtPower with `scales` (and `f0`) as differentiable inputs."""
         @staticmethod
-        def forward(ctx, x, scales, f0, eng, kind, param, dt, sj, hop, keep):
+        def forward(ctx, x, scales, f0, eng, kind, param, dt, sj, hop, keep, pool):
             n0 = x.shape[-1]
-            P = torch.empty(tuple(x.shape[:-1]) + (sj.size, n0 if hop is None else -(-n0 // hop)), dtype=x.dtype, device=x.device)
+            P = torch.empty(tuple(x.shape[:-1]) + (sj.size, pooled_columns(n0, hop, pool)), dtype=x.dtype, device=x.device)
             tol = _tolerance()
             _on_current_stream(torch, eng, x.device)
             eng.plan.set_tolerance(tol)
-            if hop is None:
+            if pool is not None:
+                eng.transform_pool(x, n0, pool, kind, param, dt, sj, P)
+            elif hop is None:
                 eng.transform_power(x, n0, None, kind, param, dt, sj, P, n0)
             else:
                 eng.transform_hop(x, n0, hop, eng.plan.OUT_POWER, kind, param, dt, sj, P)
             ctx.save_for_backward(x)
             ctx.geometry = (eng, kind, param, dt, sj, tol, hop, n0, keep, scales, f0)
+            ctx.pool = pool
             return P
 
         @staticmethod
@@ -203,6 +220,8 @@ def _function(torch):
             eng, kind, param, dt, sj, tol, hop, n0 = ctx.geometry[:8]
             cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
             q = gP.to(x.dtype).contiguous()
+            if ctx.pool is not None:                             # (hop is None then: the undecimated backward on gP / c_m spread over the windows)
+                q = spread_over_windows(q, n0, ctx.pool)
             G = torch.empty(q.shape, dtype=cplx_t, device=q.device)
             _on_current_stream(torch, eng, q.device)
             eng.plan.set_tolerance(tol)
@@ -212,7 +231,7 @@ def _function(torch):
                 eng.transform_hop(x, n0, hop, eng.plan.OUT_WEIGHTED, kind, param, dt, sj, G, q, 2.0)
             out = scale_backward(ctx, x, G, ctx.needs_input_grad[:3])
             del G
-            return out + (None,) * 7
+            return out + (None,) * 8
 
     return CwtRows, CwtPower, CwtRowsScales, CwtPowerScales
 
@@ -332,7 +351,8 @@ def cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=T
     return W, sj, freqs, coi
 
 
-def cwt_power_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=True, hop=None, *, scales=None, f0=None):
+def cwt_power_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=True, hop=None, *, scales=None, f0=None,
+                    pool=None):
     """The scalogram ``|W|^2`` of a torch tensor, differentiable with respect to it: ``cwt_torch(x, ...)[0].abs() ** 2`` without
     W -- neither written by the forward nor kept for the backward.
 
@@ -347,17 +367,32 @@ def cwt_power_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None,
     adjoint (``cwt_adjoint_rows_hop``) are all of rows x ceil(n0 / h) elements; x alone is saved.
 
     scales=, f0= (keyword only) as in ``cwt_torch``: P is differentiable with respect to them; the backward builds the same
-    G = 2 gP W and hands it to ``cwt_adjoint_rows_scales``."""
+    G = 2 gP W and hands it to ``cwt_adjoint_rows_scales``.
+
+    pool=h (keyword only; a power of two, 2 <= h <= padded length; not together with hop): P has ceil(n0 / h) columns, the
+    MEANS of |W|^2 over windows of h columns (the last window over its own columns), and coi is the minimum of coi over each
+    window.  The forward is ``cwt_transform_pool``: the rows of polynomial form sum their windows in the kernel, nothing of
+    rows x n0 elements is written for them, and x alone is saved.  The backward is NOT that small: the cotangent of W is
+    G[j, n] = (2 / c_m) gP[j, n // h] W[j, n], built from what exists -- gP / c_m spread to n0 columns (Q, rows x n0 reals: 8 B
+    per element in float64), ``cwt_transform_weighted`` with alpha = 2 (G, rows x n0 complex: 16 B per element), then
+    ``cwt_adjoint_rows`` (with scales= / f0=: ``cwt_adjoint_rows_scales``) -- so it holds rows x n0 elements of Q and of G
+    transiently, 24 B per element in float64, freed when it returns.  Once differentiable, like its siblings."""
     global _fn
+    if pool is not None and hop is not None:
+        _check_pool(pool, 2, hop=hop)
     if scales is not None or f0 is not None:
         torch, eng, kind, param, sj, freqs, coi, hop, keep = _prepare("cwt_power_torch", x, dt, dj, s0, J, wavelet, freqs, pad, hop, scales,
                                                                       f0)
+        if pool is not None:
+            pool, coi = _check_pool(pool, eng.plan.nfft), _pool_coi(coi, pool)
         if _fn is None:
             _fn = _function(torch)
-        P = _fn[3].apply(x.contiguous(), scales, f0, eng, kind, param, float(dt), sj, hop, keep)
+        P = _fn[3].apply(x.contiguous(), scales, f0, eng, kind, param, float(dt), sj, hop, keep, pool)
         return P, sj, freqs, coi
     torch, eng, kind, param, sj, freqs, coi, hop = _prepare("cwt_power_torch", x, dt, dj, s0, J, wavelet, freqs, pad, hop)
+    if pool is not None:
+        pool, coi = _check_pool(pool, eng.plan.nfft), _pool_coi(coi, pool)
     if _fn is None:
         _fn = _function(torch)
-    P = _fn[1].apply(x.contiguous(), eng, kind, param, float(dt), sj, hop)
+    P = _fn[1].apply(x.contiguous(), eng, kind, param, float(dt), sj, hop, pool)
     return P, sj, freqs, coi

@@ -365,7 +365,7 @@ int cwt_plan_destroy(cwt_plan* p) {
   for (auto& t : p->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   for (auto e : p->free_events) (void)hipEventDestroy(e);
   void* bufs[] = {p->tw_all, p->twn_lo, p->weights_dev, p->Z, p->xs, p->xm, p->xsa, p->pcoef, p->pband, p->range_dev, p->hx, p->hxhat, p->hW,
-                  p->bs_khat[0], p->bs_khat[1], p->bs_a, p->bs_spec, p->bs_par, p->adj_spec, p->adj_acc, p->hop_z, p->sgrad_part};
+                  p->bs_khat[0], p->bs_khat[1], p->bs_a, p->bs_spec, p->bs_par, p->adj_spec, p->adj_acc, p->hop_z, p->sgrad_part, p->pool_s};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (auto& t : p->slots) {
     if (t.gt_dev) (void)hipFree(t.gt_dev);
@@ -377,6 +377,9 @@ int cwt_plan_destroy(cwt_plan* p) {
     if (t.adj_dev) (void)hipFree(t.adj_dev);
     if (t.adj_pinned) (void)hipHostFree(t.adj_pinned);
     if (t.adj_uploaded) (void)hipEventDestroy(t.adj_uploaded);
+    if (t.pool_dev) (void)hipFree(t.pool_dev);
+    if (t.pool_pinned) (void)hipHostFree(t.pool_pinned);
+    if (t.pool_uploaded) (void)hipEventDestroy(t.pool_uploaded);
   }
   if (p->hstage) (void)hipHostFree(p->hstage);
   for (int i = 0; i < 2; ++i) {
@@ -851,6 +854,43 @@ int cwt_adjoint_rows_hop(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_b
     return adjoint_hop_impl<decltype(t)>(p, G_dev, nbatch, g_batch_ld, ldg, ncols_h, logM, n0, mother_of(mother, param), nrows, xbar_dev,
                                          xbar_ld, accumulate, nullptr);
   });
+}
+
+// ---- time-pooled scalogram: window means of |W|^2 (cwt_hip.h) --------------------------------------------------------------------
+int cwt_transform_pool(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, int mother, double param, double dt,
+                       const double* scales, int nrows, int64_t pool, void* xhat_dev, void* P_dev, int64_t ldp, int64_t ncols_p) {
+  if (!p || !x_dev || !scales || !P_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (mother == MOTHER_TABLE) return fail(CWT_EINVAL, "pooled transform: a built-in mother is needed");
+  if (nbatch < 1 || nrows < 1 || int64_t(nbatch) * nrows > p->max_rows) return fail(CWT_EINVAL, "need nbatch*nrows <= max_rows");
+  if (n0 < 1 || n0 > p->N) return fail(CWT_EINVAL, "n0 must be in [1, nfft]");
+  if (nbatch > 1 && x_ld < n0) return fail(CWT_EINVAL, "x_ld must be >= n0");
+  if (pool < 2 || (pool & (pool - 1)) || pool > p->N) return fail(CWT_EINVAL, "pool must be a power of two in [2, nfft]");
+  if (ncols_p != (n0 + pool - 1) / pool) return fail(CWT_EINVAL, "ncols_p must be ceil(n0 / pool)");
+  if (ldp < ncols_p) return fail(CWT_EINVAL, "ldp must be >= ncols_p");
+  HIPCHECK(hipSetDevice(p->device));
+  // the table of cwt_transform / cwt_transform_power for these scales and n0 columns (neither the output nor the pool is part of its key)
+  int rc = prepare_rows_table(p, true, mother, param, dt, scales, nrows, n0, n0);
+  if (!rc && p->logN >= 18 && !p->profile) rc = ensure_distinct_queues(p);
+  if (rc) return rc;
+  const bool only_ols = !xhat_dev && p->rt->n_ols == nrows;      // no row needs a spectrum
+  if (!xhat_dev && !only_ols) {                                  // the caller has no use for the spectra: one signal's, in plan scratch
+    rc = grow(&p->hxhat, &p->hxhat_bytes, size_t(p->N) * 2 * p->esize(), p->stream);
+    if (rc) return rc;
+  }
+  const Mother mo = mother_of(mother, param);
+  const int logh = ilog2(pool);
+  CallScope scope(p);
+  if (xhat_dev || only_ols)
+    return scope.done(by_precision(p, [&](auto t) {
+      return transform_pool_impl<decltype(t)>(p, x_dev, nbatch, x_ld, n0, xhat_dev, mo, nrows, logh, P_dev, ldp);
+    }));
+  for (int b = 0; b < nbatch && !rc; ++b)                        // (every signal's spectrum through the same scratch, in stream order)
+    rc = by_precision(p, [&](auto t) {
+      using T = decltype(t);
+      return transform_pool_impl<T>(p, static_cast<const T*>(x_dev) + size_t(b) * size_t(x_ld), 1, 0, n0, p->hxhat, mo, nrows, logh,
+                                    static_cast<T*>(P_dev) + size_t(b) * size_t(nrows) * size_t(ldp), ldp);
+    });
+  return scope.done(rc);
 }
 
 // cwt_adjoint_rows (hop = 1) or cwt_adjoint_rows_hop with the gradients with respect to the scales and f0 beside xbar: the checks of

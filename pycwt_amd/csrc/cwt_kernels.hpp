@@ -856,3 +856,4 @@ k_pass_b_ct(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
 #include "cwt_kernels_callers.hpp"   // coherence helpers, Bluestein, icwt, spectrum range
 #include "cwt_kernels_hop.hpp"       // decimated output: folded spectrum, short row transforms, their adjoint
 #include "cwt_kernels_sgrad.hpp"     // gradients with respect to the scales and f0: one reduction over each row's band
+#include "cwt_kernels_pool.hpp"      // time-pooled scalogram: window means of |W|^2 (polynomial rows in the kernel, the others from scratch)

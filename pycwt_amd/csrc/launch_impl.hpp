@@ -11,6 +11,10 @@
 
 namespace cwtd {
 
+// The row descriptors the launchers of the call in progress read: the current table's, or (a pooled call) its copy with out_row
+// renumbered densely over the rows that are not of polynomial form
+inline const RowDesc* call_rows(const cwt_plan* p) { return p->call.rows ? p->call.rows : p->rt->rows_dev; }
+
 template <typename T>
 const cplx<T>* tw_table(const cwt_plan* p, int logL) {
   return static_cast<const cplx<T>*>(p->tw_all) + ((size_t(1) << logL) - 2);
@@ -114,7 +118,7 @@ void launch_narrow_ct_many(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, O
   for (int r0 = 0; r0 < n_many; r0 += kMaxGridY)
     hipLaunchKernelGGL((k_narrow_ct_many<T, LOGP, out_tag_t<OUT>>), dim3(1u << (p->logN - LOGP), std::min(kMaxGridY, n_many - r0)),
                        dim3(1 << (LOGP - 4)), (size_t(1) << LOGP) * sizeof(T), p->stream, xhat,
-                       p->rt->rows_dev + first + n_small_k + r0, mo, static_cast<const cplx<T>*>(p->tw_all),
+                       call_rows(p) + first + n_small_k + r0, mo, static_cast<const cplx<T>*>(p->tw_all),
                        twn_of<T>(p), p->logN, W, long(ldw), long(ncols));
 }
 
@@ -137,13 +141,13 @@ void launch_narrow_ct_all(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, OU
     for (int r0 = n_wave; r0 < n_half; r0 += kMaxGridY)
       hipLaunchKernelGGL((k_narrow_ct_all<T, LOGP - 1, out_tag_t<OUT>>), dim3(1u << (p->logN - LOGP + 1), std::min(kMaxGridY, n_half - r0)),
                          dim3(1 << (LOGP - 5)), (size_t(1) << (LOGP - 1)) * sizeof(T), p->stream, xhat,
-                         p->rt->rows_dev + first + r0, mo, static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
+                         call_rows(p) + first + r0, mo, static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
                          p->logN, W, long(ldw), long(ncols));
   }
   for (int r0 = std::max(n_half, n_wave); r0 < n_small_k; r0 += kMaxGridY)
     hipLaunchKernelGGL((k_narrow_ct_all<T, LOGP, out_tag_t<OUT>>), dim3(1u << (p->logN - LOGP), std::min(kMaxGridY, n_small_k - r0)),
                        dim3(1 << (LOGP - 4)), (size_t(1) << LOGP) * sizeof(T), p->stream, xhat,
-                       p->rt->rows_dev + first + r0, mo, static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
+                       call_rows(p) + first + r0, mo, static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
                        p->logN, W, long(ldw), long(ncols));
 }
 
@@ -156,7 +160,7 @@ void launch_narrow_ct_big(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, OU
     narrow_class_counts(p, &n_small_k, &n_big, &n_many);
     for (int r0 = 0; r0 < n_big; r0 += kMaxGridY)
       hipLaunchKernelGGL((k_narrow_ct_big<T, out_tag_t<OUT>>), dim3(1u << (p->logN - 14), std::min(kMaxGridY, n_big - r0)), dim3(1024),
-                         (size_t(1) << 14) * sizeof(T), p->stream, xhat, p->rt->rows_dev + first + n_small_k + n_many + r0, mo,
+                         (size_t(1) << 14) * sizeof(T), p->stream, xhat, call_rows(p) + first + n_small_k + n_many + r0, mo,
                          static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p), p->logN, W, long(ldw), long(ncols));
   }
 }
@@ -381,7 +385,7 @@ int launch_ols_rows_p(cwt_plan* p, int g, OUT W, int64_t ldw, int64_t ncols, hip
   const size_t lds = ((size_t(1) << LOGP) + (size_t(1) << (LOGP - 4))) * (ols_pairs(sizeof(T), LOGP) ? sizeof(pairf) : sizeof(T));
   return timed_launch(p, g == 0 ? KC_OLS_SMALL : KC_OLS, [&] {
     hipLaunchKernelGGL((k_ols_ct<T, LOGP, out_tag_t<OUT>>), dim3(unsigned(count)), dim3(1 << (LOGP - 4)), lds, st,
-                       static_cast<const cplx<T>*>(p->xs), rt->rows_dev + rt->ols_first + G.row_first,
+                       static_cast<const cplx<T>*>(p->xs), call_rows(p) + rt->ols_first + G.row_first,
                        static_cast<const cplx<T>*>(rt->gt_dev), static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
                        p->logN, G.cls, W, long(ldw), long(ncols), unsigned(first));
   }, st);
@@ -433,7 +437,7 @@ int launch_aols_p(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, int64_t
     const int cnt = std::min(chunk, nb - b0);
     bool ok = true;
     if (phase != 2) rc = timed_launch(p, KC_AOLS_PRE, [&] {
-      ok = try_pass_a_ct<T, IN_SPECTRUM>(p, logR, xhat_dev, rt->rows_dev + rt->aux_first + b0, cnt, one, 0L, 0L, Z, st);
+      ok = try_pass_a_ct<T, IN_SPECTRUM>(p, logR, xhat_dev, call_rows(p) + rt->aux_first + b0, cnt, one, 0L, 0L, Z, st);
     }, st);
     if (!rc && !ok) rc = fail(CWT_EINVAL, "k_aols rows need the default geometry");
     if (!rc && phase != 2) rc = timed_launch(p, KC_AOLS_PRE, [&] {
@@ -453,7 +457,7 @@ int launch_aols_p(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, int64_t
     }
     if (!rc) rc = timed_launch(p, KC_AOLS, [&] {
       hipLaunchKernelGGL((k_aols_rows<T, LOGP, out_tag_t<OUT>>), dim3(unsigned(rt->aols_wgs), unsigned(cnt)), dim3(1 << (LOGP - 4)), lds_rows, st,
-                         static_cast<const cplx<T>*>(p->xsa), rt->rows_dev + rt->aols_first + long(b0) * g.nrows,
+                         static_cast<const cplx<T>*>(p->xsa), call_rows(p) + rt->aols_first + long(b0) * g.nrows,
                          static_cast<const T*>(rt->agt_dev), static_cast<const cplx<T>*>(p->tw_all), g,
                          static_cast<const cplx<T>*>(xhat_dev), long(p->N >> 1), W, long(ldw), long(ncols));
     }, st);
@@ -481,7 +485,7 @@ int launch_aols_second(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, in
   if (!rc) rc = timed_launch(p, KC_AOLS, [&] {
     hipLaunchKernelGGL((k_aols_rows<T, LOGP, out_tag_t<OUT>>), dim3(unsigned(rt->aols2_wgs), 1u), dim3(1 << (LOGP - 4)),
                        aols_pairs(sizeof(T)) ? 2 * lds : lds, st,
-                       static_cast<const cplx<T>*>(p->xsa), rt->rows_dev + rt->aols2_first, static_cast<const T*>(rt->agt_dev),
+                       static_cast<const cplx<T>*>(p->xsa), call_rows(p) + rt->aols2_first, static_cast<const T*>(rt->agt_dev),
                        static_cast<const cplx<T>*>(p->tw_all), g, static_cast<const cplx<T>*>(xhat_dev), long(p->N >> 1), W,
                        long(ldw), long(ncols));
   }, st);
@@ -511,7 +515,7 @@ int launch_poly_coef(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, int chu
   if (rc) return rc;
   static const bool once = (allow_big_lds(&k_poly_coef<T, 13>), allow_big_lds(&k_poly_coef<T, 14>), true);
   (void)once;
-  const RowDesc* rows = rt->rows_dev + rt->poly_first + ch.row_first;
+  const RowDesc* rows = call_rows(p) + rt->poly_first + ch.row_first;
   cplx<T>* coef = static_cast<cplx<T>*>(p->pcoef);
   cplx<T>* band = static_cast<cplx<T>*>(p->pband);
   rc = timed_launch(p, KC_POLY_COEF, [&] {
@@ -552,7 +556,7 @@ template <typename T, typename OUT>
 int launch_poly_rows(cwt_plan* p, int chunk, OUT W, int64_t ldw, int64_t ncols, hipStream_t st) {
   const cwt_plan::RowTable* rt = p->rt;
   const auto& ch = rt->poly_chunks[size_t(chunk)];
-  const RowDesc* rows = rt->rows_dev + rt->poly_first + ch.row_first;
+  const RowDesc* rows = call_rows(p) + rt->poly_first + ch.row_first;
   const cplx<T>* coef = static_cast<const cplx<T>*>(p->pcoef);
   const int64_t per_wg = 256 * (sizeof(T) == 8 ? 1 : 2) * POLY_PASSES;
   // LDS: the coefficient sets of the intervals one workgroup touches (shortest interval 2^POLY_MIN_LOGR samples)
@@ -563,6 +567,28 @@ int launch_poly_rows(cwt_plan* p, int chunk, OUT W, int64_t ldw, int64_t ncols, 
                          dim3(256), lds2, st, rows + r0, coef, twn_of<T>(p), p->logN, W, long(ldw), long(ncols),
                          p->poly_xcd ? CWT_POLY_XCD_LOG : 0);
   }, st);
+}
+
+// ... or, in a pooled call (p->call.pool = log2 h), pool_poly_rows: the same evaluation summed over the windows, straight into the
+// caller's Pbar; n0 = the columns of W
+template <typename T>
+int launch_pool_poly_rows(cwt_plan* p, int chunk, int64_t n0, hipStream_t st) {
+  const cwt_plan::RowTable* rt = p->rt;
+  const auto& ch = rt->poly_chunks[size_t(chunk)];
+  const RowDesc* rows = call_rows(p) + rt->poly_first + ch.row_first;
+  const int logh = p->call.pool;
+  const int64_t span = int64_t(1) << std::max(logh, POOL_LOG_SPAN);    // a workgroup: 4096 columns, or one longer window
+  return timed_launch(p, KC_POOL_POLY, [&] {
+    for (int r0 = 0; r0 < ch.nrows; r0 += kMaxGridY)
+      hipLaunchKernelGGL((pool_poly_rows<T>), dim3(unsigned((n0 + span - 1) / span), std::min(kMaxGridY, ch.nrows - r0)), dim3(POOL_THREADS),
+                         POOL_THREADS * sizeof(T), st, rows + r0, static_cast<const cplx<T>*>(p->pcoef), p->logN, logh,
+                         static_cast<T*>(p->call.pool_out), long(p->call.pool_ld), long(n0));
+  }, st);
+}
+template <typename T, typename OUT>
+int launch_poly_rows_of_call(cwt_plan* p, int chunk, OUT W, int64_t ldw, int64_t ncols, hipStream_t st) {
+  if (p->call.pool) return launch_pool_poly_rows<T>(p, chunk, ncols, st);
+  return launch_poly_rows<T>(p, chunk, W, ldw, ncols, st);
 }
 
 // Two-pass rows (forms T), chunk by chunk on the plan's stream through the one intermediate buffer.
@@ -578,7 +604,7 @@ int launch_wide_rows(cwt_plan* p, const void* xhat_dev, const Mother& mo, OUT W,
   cplx<T>* Z = static_cast<cplx<T>*>(p->Z);
   for (int c = 0; c < nchunks; ++c) {
     const int first = c * chunk, cnt = std::min(chunk, p->rt->n_wide - first);
-    const RowDesc* rows = p->rt->rows_dev + p->rt->wide_first + first;
+    const RowDesc* rows = call_rows(p) + p->rt->wide_first + first;
     rc = timed_launch(p, KC_PASS_A, [&] {
       if (try_pass_a_ct<T, IN_SPECTRUM>(p, logR, xhat_dev, rows, cnt, mo, 0L, 0L, Z, p->stream)) return;
       hipLaunchKernelGGL((k_pass_a<T, IN_SPECTRUM>), dim3(1u << (logN - logP), cnt), dim3(threads), lds, p->stream,
@@ -718,7 +744,7 @@ int rows_launch_serial_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, 
     HIPCHECK(hipStreamWaitEvent(M, p->ev_a[0], 0));
     const int nchunks = int(rt->poly_chunks.size());
     for (int c = 0; c < nchunks && !rc; ++c) {            // chunk c's rows, then chunk c + 1's coefficients
-      rc = launch_poly_rows<T>(p, c, W, ldw, ncols, M);
+      rc = launch_poly_rows_of_call<T>(p, c, W, ldw, ncols, M);
       if (!rc && c + 1 < nchunks) rc = launch_poly_coef<T>(p, xhat, mo, c + 1, M, nullptr);
     }
     if (rc) return rc;
@@ -785,7 +811,7 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
       const int total = nrows << logN;
       return timed_launch(p, KC_DIRECT, [&] {
         hipLaunchKernelGGL((k_direct<T, IN_SPECTRUM, out_tag_t<OUT>>), dim3((total + 63) / 64), dim3(64), 0, p->stream,
-                           xhat_dev, p->rt->rows_dev, nrows, mo, logN, 0L, 0L, W, long(ldw), long(ncols));
+                           xhat_dev, call_rows(p), nrows, mo, logN, 0L, 0L, W, long(ldw), long(ncols));
       });
     }
     // several rows per workgroup: aim at 4096 points (256 threads)
@@ -795,7 +821,7 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
     const size_t lds = (size_t(TB) << logN) * sizeof(T);
     return timed_launch(p, KC_SMALL, [&] {
       hipLaunchKernelGGL((k_small<T, IN_SPECTRUM, out_tag_t<OUT>>), dim3((nrows + TB - 1) / TB), dim3(threads), lds,
-                         p->stream, xhat_dev, p->rt->rows_dev, nrows, mo, tw_table<T>(p, logN), logN, logTB,
+                         p->stream, xhat_dev, call_rows(p), nrows, mo, tw_table<T>(p, logN), logN, logTB,
                          0L, 0L, W, long(ldw), long(ncols));
     });
   }
@@ -844,7 +870,7 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
     const int nchunks = int(p->rt->poly_chunks.size());
     int r = CWT_OK;
     for (int c = 0; c < nchunks && !r; ++c) {              // chunk c's rows, then chunk c + 1's coefficients, on one stream
-      r = launch_poly_rows<T>(p, c, W, ldw, ncols, ps);
+      r = launch_poly_rows_of_call<T>(p, c, W, ldw, ncols, ps);
       if (!r && c + 1 < nchunks) r = launch_poly_coef<T>(p, xhat, mo, c + 1, ps, poly_on_side ? p->side2 : nullptr);
     }
     return r;
@@ -910,7 +936,7 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
         rc = timed_launch(p, KC_NARROW, [&] {
           for (int r0 = 0; r0 < g.count; r0 += kMaxGridY)
             hipLaunchKernelGGL((k_narrow<T, out_tag_t<OUT>>), dim3(1u << (logN - logP), std::min(kMaxGridY, g.count - r0)),
-                               dim3(threads), lds, p->stream, xhat, p->rt->rows_dev + g.first + r0, mo,
+                               dim3(threads), lds, p->stream, xhat, call_rows(p) + g.first + r0, mo,
                                tw_table<T>(p, g.logK), twn_of<T>(p), logN, g.logK, logP - g.logK, W, long(ldw),
                                long(ncols));
         });
@@ -954,6 +980,78 @@ int transform_impl(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev, c
   int rc = ols_early ? launch_ols_early<T>(p, x_dev, n0, false) : CWT_OK;
   if (!rc && xhat_dev) rc = fft_rows_impl<T, IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev);
   return rc ? rc : rows_launch<T>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0, ols_early);
+}
+
+// ---- time-pooled scalogram (cwt_transform_pool; kernels: cwt_kernels_pool.hpp) ------------------------------------------------
+// The copy of the current table that the launchers of a pooled call read (cwt_plan::Call::rows), uploaded once per row table
+// through a staging buffer of its own: out_row of every entry that is not a polynomial row becomes the row's rank among the rows
+// that are not of polynomial form, so that plan scratch holds exactly those rows; behind the descriptors the ranks' out_rows.
+inline const int* pool_map_of(const cwt_plan* p) { return reinterpret_cast<const int*>(p->rt->pool_dev + table_capacity(p->max_rows)); }
+inline int upload_pool_rows(cwt_plan* p, int nrows) {
+  cwt_plan::RowTable* t = p->rt;
+  if (t->pool_dense >= 0) return CWT_OK;
+  if (int(t->base.size()) != nrows) return fail(CWT_EINVAL, "pooled transform: the row table does not describe this call");
+  const size_t cap = table_capacity(p->max_rows), bytes = cap * sizeof(RowDesc) + size_t(p->max_rows) * sizeof(int);
+  if (t->table.size() > cap) return fail(CWT_EINVAL, "pooled transform: row table larger than its capacity");
+  if (!t->pool_dev && hipMalloc(reinterpret_cast<void**>(&t->pool_dev), bytes) != hipSuccess) return fail(CWT_ENOMEM, "device allocation failed");
+  if (!t->pool_pinned && hipHostMalloc(reinterpret_cast<void**>(&t->pool_pinned), bytes) != hipSuccess)
+    return fail(CWT_ENOMEM, "pinned allocation failed");
+  if (!t->pool_uploaded) HIPCHECK(hipEventCreateWithFlags(&t->pool_uploaded, hipEventDisableTiming));
+  else HIPCHECK(hipEventSynchronize(t->pool_uploaded));       // (the slot's previous copy)
+  std::vector<int> rank(size_t(nrows), 0);
+  std::vector<char> poly(size_t(nrows), 0);
+  for (int i = 0; i < t->n_poly; ++i) poly[size_t(t->table[size_t(t->poly_first + i)].out_row)] = 1;
+  int* map = reinterpret_cast<int*>(t->pool_pinned + cap);
+  int nd = 0;
+  for (int j = 0; j < nrows; ++j) if (!poly[size_t(j)]) { rank[size_t(j)] = nd; map[nd++] = j; }
+  for (size_t i = 0; i < t->table.size(); ++i) {
+    RowDesc r = t->table[i];
+    const bool is_poly = int(i) >= t->poly_first && int(i) < t->poly_first + t->n_poly;
+    if (!is_poly && r.out_row >= 0 && r.out_row < nrows) r.out_row = rank[size_t(r.out_row)];
+    t->pool_pinned[i] = r;
+  }
+  HIPCHECK(hipMemcpyAsync(t->pool_dev, t->pool_pinned, t->table.size() * sizeof(RowDesc), hipMemcpyHostToDevice, p->stream));
+  if (nd) HIPCHECK(hipMemcpyAsync(t->pool_dev + cap, map, size_t(nd) * sizeof(int), hipMemcpyHostToDevice, p->stream));
+  HIPCHECK(hipEventRecord(t->pool_uploaded, p->stream));
+  t->pool_dense = nd;
+  return CWT_OK;
+}
+
+// cwt_transform_pool after its checks and the row table (inside its CallScope).  Signal by signal through transform_impl as a power
+// call: the schedule, the forms and the kernels of cwt_transform_power, with pool_poly_rows in the place of k_poly_rows and plan
+// scratch (rows not of polynomial form x n0 reals, one signal's) as the output of every other form; pool_rows follows on the
+// caller's stream, where both schedules have joined every kernel that writes the scratch.  xhat_dev: nbatch x nfft, or NULL
+// (no row needs a spectrum).
+template <typename T>
+int transform_pool_impl(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, void* xhat_dev, const Mother& mo, int nrows,
+                        int logh, void* P_dev, int64_t ldp) {
+  int rc = check_geometry(p);
+  if (!rc) rc = upload_pool_rows(p, nrows);
+  if (rc) return rc;
+  const int nd = p->rt->pool_dense;
+  const int64_t sld = (n0 + 15) & ~int64_t(15);                        // (pool_rows loads 4 aligned columns per lane)
+  if (nd) rc = grow(&p->pool_s, &p->pool_s_bytes, size_t(nd) * size_t(sld) * sizeof(T), p->stream);
+  if (rc) return rc;
+  const int64_t ncols_p = (n0 + (int64_t(1) << logh) - 1) >> logh;
+  for (int b = 0; b < nbatch; ++b) {
+    T* P = static_cast<T*>(P_dev) + size_t(b) * size_t(nrows) * size_t(ldp);
+    p->call.power = 1;
+    p->call.pool = logh;
+    p->call.pool_out = P;
+    p->call.pool_ld = ldp;
+    p->call.rows = p->rt->pool_dev;
+    rc = transform_impl<T>(p, static_cast<const T*>(x_dev) + size_t(b) * size_t(x_ld), n0,
+                           xhat_dev ? static_cast<cplx<T>*>(xhat_dev) + size_t(b) * size_t(p->N) : nullptr, mo, nrows, p->pool_s, sld, n0);
+    if (rc || !nd) { if (rc) return rc; continue; }
+    const int64_t work = logh <= POOL_LOG_TILE ? (int64_t(nd) * ((n0 + (1 << POOL_LOG_TILE) - 1) >> POOL_LOG_TILE) + POOL_TILES - 1) / POOL_TILES
+                                               : int64_t(nd) * ncols_p;
+    rc = timed_launch(p, KC_POOL_ROWS, [&] {
+      hipLaunchKernelGGL((pool_rows<T>), dim3(unsigned(work)), dim3(POOL_THREADS), POOL_THREADS * sizeof(T), p->stream,
+                         static_cast<const T*>(p->pool_s), long(sld), long(n0), nd, pool_map_of(p), logh, P, long(ldp));
+    });
+    if (rc) return rc;
+  }
+  return CWT_OK;
 }
 
 template <typename T>
@@ -1180,7 +1278,7 @@ int adjoint_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld,
     if (!xbar_dev) continue;
     for (size_t c = 0; use_poly && c < rt->poly_chunks.size(); ++c) {
       const auto& ch = rt->poly_chunks[c];
-      const RowDesc* rows = rt->rows_dev + rt->poly_first + ch.row_first;
+      const RowDesc* rows = call_rows(p) + rt->poly_first + ch.row_first;
       rc = timed_launch(p, KC_ADJOINT, [&] {
         for (int r0 = 0; r0 < ch.nrows; r0 += kMaxGridY)
           hipLaunchKernelGGL((k_poly_moments<T>), dim3(unsigned(std::max<int64_t>(1, N >> 14)), std::min(kMaxGridY, ch.nrows - r0)), dim3(256),
@@ -1592,6 +1690,7 @@ int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g
                         const ScaleGrad*);                                                                                          \
   X int transform_hop_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, const void*, int64_t, const Mother&, int, int, int, void*, \
                               const void*, double, int64_t, int64_t);                                                              \
+  X int transform_pool_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, void*, const Mother&, int, int, void*, int64_t);         \
   X int adjoint_hop_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int64_t, int, int64_t, const Mother&, int, void*, int64_t, int, \
                             const ScaleGrad*);
 

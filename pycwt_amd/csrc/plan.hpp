@@ -45,7 +45,7 @@ int fail(int code, const std::string& msg);
 
 enum KernelClass { KC_FWD_SMALL, KC_FWD_A, KC_FWD_B, KC_SMALL, KC_DIRECT, KC_NARROW, KC_NARROW_MANY, KC_NARROW_BIG,
                    KC_PASS_A, KC_PASS_B, KC_ICWT, KC_ELEMENTWISE, KC_OLS_FWD, KC_OLS, KC_OLS_SMALL, KC_AOLS_PRE, KC_AOLS,
-                   KC_POLY_COEF, KC_POLY, KC_ADJOINT, KC_HOP_FOLD, KC_HOP_ROWS, KC_SGRAD, KC_COUNT };
+                   KC_POLY_COEF, KC_POLY, KC_ADJOINT, KC_HOP_FOLD, KC_HOP_ROWS, KC_SGRAD, KC_POOL_POLY, KC_POOL_ROWS, KC_COUNT };
 extern const char* const kClassNames[KC_COUNT];
 
 int ilog2(int64_t v);
@@ -87,6 +87,13 @@ struct cwt_plan {
     int weighted = 0;                      // the *_weighted entry points: the row kernels write (alpha Q) W, Q read at the store's [j, n]
     const void* q = nullptr;               // ... Q (reals of the plan's precision, the leading dimension and batch stride of the output)
     double alpha = 0.0;
+    // cwt_transform_pool (a power call besides): window means of h = 2^pool columns.  The polynomial rows sum their windows in
+    // pool_poly_rows and write pool_out; every other launcher gets plan scratch as its output and `rows`, the table's descriptors with
+    // out_row renumbered densely over the rows that are not of polynomial form (RowTable::pool_dev)
+    int pool = 0;                          // log2 h; 0: not a pooled call
+    void* pool_out = nullptr;              // Pbar of the signal in progress ...
+    int64_t pool_ld = 0;                   // ... and its leading dimension
+    const cwt::RowDesc* rows = nullptr;
   };
   Call call;
   // options
@@ -172,6 +179,8 @@ struct cwt_plan {
   size_t adj_acc_bytes = 0;
   void* hop_z = nullptr;    // cwt_transform_hop: folded spectra of a chunk of signals (signals x rows x M complex)
   size_t hop_z_bytes = 0;
+  void* pool_s = nullptr;   // cwt_transform_pool: full-rate power of the rows that are not of polynomial form (those rows x n0 reals)
+  size_t pool_s_bytes = 0;
   void* sgrad_part = nullptr;   // cwt_adjoint_rows_scales: the slice sums of sgrad_partial (signals x rows x slices x 2 reals)
   size_t sgrad_part_bytes = 0;
   void* xm = nullptr;       // band-passed complex signal x_M of the k_aols rows (N complex)
@@ -253,6 +262,12 @@ struct cwt_plan {
     hipEvent_t adj_uploaded = nullptr;
     int adj_poly = -1;
     std::vector<int> adj_rows;           // their out_rows
+    // cwt_transform_pool: the table again with out_row of every row that is not of polynomial form replaced by its rank among those
+    // rows (the polynomial rows keep theirs), and behind it the ranks' out_rows (pool_map: n_dense ints); uploaded once per table
+    cwt::RowDesc* pool_dev = nullptr;
+    cwt::RowDesc* pool_pinned = nullptr;
+    hipEvent_t pool_uploaded = nullptr;
+    int pool_dense = -1;                 // rows not of polynomial form; -1: not uploaded since the table was built
   };
   RowTable slots[4];
   RowTable* rt = &slots[0];

@@ -17,7 +17,7 @@ int fail(int code, const std::string& msg) {
 const char* const kClassNames[KC_COUNT] = {"fwd_small", "fwd_pass_a",  "fwd_pass_b", "small",  "direct", "narrow",
                                            "narrow_many", "narrow_big", "pass_a",     "pass_b", "icwt",   "elementwise",
                                            "ols_fwd", "ols", "ols_small", "aols_pre", "aols", "poly_coef", "poly",
-                                           "adjoint", "hop_fold", "hop_rows", "sgrad"};
+                                           "adjoint", "hop_fold", "hop_rows", "sgrad", "pool_poly", "pool_rows"};
 
 int ilog2(int64_t v) {
   int l = 0;
@@ -1348,6 +1348,7 @@ int upload_row_table(cwt_plan* p, const std::vector<double>& key) {
                           p->stream));
   HIPCHECK(hipEventRecord(t->uploaded, p->stream));
   t->adj_poly = -1;
+  t->pool_dense = -1;
   t->key = key;
   return CWT_OK;
 }

@@ -157,6 +157,14 @@ class HipEngine:
         self.plan.transform_hop(x.data_ptr(), nb, x.shape[-1], n0, kind, param, dt, sj, hop, None, output, out.data_ptr(),
                                 out.shape[-1], None if Q is None else Q.data_ptr(), alpha)
 
+    def transform_pool(self, x, n0, pool, kind, param, dt, sj, P):
+        """Means of |W|^2 over windows of `pool` columns (cwt_transform_pool): P (rows, ld) or (batch, rows, ld) real with
+        ld >= ceil(n0 / pool), contiguous.  The spectra go to plan scratch."""
+        if not P.is_contiguous():
+            raise ValueError("transform_pool: P must be contiguous")
+        nb = 1 if x.dim() == 1 else x.shape[0]
+        self.plan.transform_pool(x.data_ptr(), nb, x.shape[-1], n0, kind, param, dt, sj, pool, None, P.data_ptr(), P.shape[-1])
+
     def adjoint_rows_hop(self, G, n0, hop, kind, param, dt, sj, xbar, accumulate=False):
         """xbar (+)= Re A_h^H G (cwt_adjoint_rows_hop): G (rows, ld) or (batch, rows, ld) complex, xbar (n0,) or (batch, ld_x)."""
         nb = 1 if G.dim() == 2 else G.shape[0]

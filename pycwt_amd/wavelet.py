@@ -161,6 +161,61 @@ def _transform_hop(plan, x_host, xd_ptr, nb, n0, kind, param, dt, sj, hop, xh_pt
     plan.transform_hop(xd_ptr, nb, n0, n0, kind, param, dt, sj, hop, xh_ptr, output, out_ptr, -(-n0 // hop))
 
 
+def _check_pool(pool, N, mother=None, pad=True, hop=None):
+    """`pool=` of the power calls, the rules of cwt_transform_pool: a power of two with 2 <= pool <= N (N the padded length),
+    built-in mothers, pad=True; not together with `hop=`."""
+    if hop is not None:
+        raise ValueError("pool and hop cannot be combined (pool averages |W|^2 over its window, hop samples W)")
+    if isinstance(pool, bool) or int(pool) != pool:
+        raise ValueError("pool must be an integer")
+    pool = int(pool)
+    if pool < 2 or pool & (pool - 1):
+        raise ValueError("pool must be a power of two >= 2")
+    if not pad or N & (N - 1):
+        raise ValueError("pool needs pad=True (no pooled output at lengths that are not a power of two)")
+    if pool > N:
+        raise ValueError(f"pool must not exceed the padded length, got {pool} > {N}")
+    if mother is not None and not hasattr(mother, "device_id"):
+        raise ValueError("pool: only the built-in mothers (Morlet, Paul, DOG) have a pooled transform")
+    return pool
+
+
+def _pool_coi(coi, pool):
+    """One value per window: the minimum over its columns (a window counts as outside the cone as soon as one column is)."""
+    coi = np.asarray(coi, dtype=np.float64)
+    ncols = -(-coi.size // pool)
+    padded = np.full(ncols * pool, np.inf)
+    padded[:coi.size] = coi
+    return padded.reshape(ncols, pool).min(axis=1)
+
+
+def _transform_pool(plan, x_host, xd_ptr, nb, n0, kind, param, dt, sj, pool, xh_ptr, P_ptr, auto=True):
+    """Signals (uploaded at xd_ptr, nb x n0) -> spectra and window means of |W|^2 (cwt_transform_pool; P nb x rows x
+    ceil(n0 / pool)).  The pooled call computes time-compact rows from the signal itself, as `cwt_transform` does, so a signal
+    with a non-finite sample is not handed to it: its spectrum comes from the forward transform (all NaN) and its P is filled
+    with NaN here, as the reference's would be.  The automatic tolerance applies as in `_transform`."""
+    x_host = np.atleast_2d(x_host)
+    finite = np.isfinite(x_host).all(axis=1)
+    if nb == 1 and auto and plan.nfft > 4096 and finite[0]:
+        target = _auto(plan)
+        if target:
+            plan.forward_fft(xd_ptr, n0, xh_ptr)
+            plan.set_tolerance(plan.auto_tolerance(xh_ptr, target))
+    if finite.all():
+        plan.transform_pool(xd_ptr, nb, n0, n0, kind, param, dt, sj, pool, xh_ptr, P_ptr, -(-n0 // pool))
+        return
+    es = np.dtype(plan.real).itemsize
+    ncols = -(-n0 // pool)
+    nan = np.full(len(sj) * ncols, np.nan, dtype=plan.real)
+    for b in range(nb):
+        xb, hb, pb = xd_ptr + b * n0 * es, xh_ptr + b * plan.nfft * 2 * es, P_ptr + b * len(sj) * ncols * es
+        if finite[b]:
+            plan.transform_pool(xb, 1, n0, n0, kind, param, dt, sj, pool, hb, pb, ncols)
+        else:
+            plan.forward_fft(xb, n0, hb)
+            plan.lib.check(plan.lib.cwt_memcpy_h2d(plan.h, _hip._P(pb), nan.ctypes.data_as(_hip._P), nan.nbytes))
+
+
 def _cwt_builtin(x, dt, sj, kind, param, N, precision, device, finite, power=False):
     """W (rows x n0) and the spectrum (N) for a built-in mother through the device-resident entry points; power=True:
     |W|^2 (rows x n0 reals) from the power entry points instead of W."""
@@ -581,7 +636,8 @@ def cwt_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None,
     return (W, sj, freqs, coi, xhat[:, 1:N // 2] / N ** 0.5, ftfreqs[1:N // 2] / (2 * np.pi))
 
 
-def cwt_power(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0, pad=True, hop=None):
+def cwt_power(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0, pad=True, hop=None,
+              pool=None):
     """``cwt`` that returns the wavelet power ``|W|^2`` in place of ``W``: ``(power, sj, freqs, coi, fft, fftfreqs)``.
 
     ``power`` is float64 of shape (rows, n0) and equals ``np.abs(cwt(...)[0]) ** 2`` to rounding; the other five values are
@@ -595,11 +651,16 @@ def cwt_power(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, 
     is computed and downloaded -- ``power`` has ceil(n0 / h) columns equal to columns ``::h`` of the undecimated power to
     rounding, ``coi`` is ``coi[::h]``, everything else is unchanged.  The columns are SAMPLES of |W|^2, not its mean over the
     hop: choosing h against the smallest scale is the caller's business.
+
+    pool=h (a power of two, 2 <= h <= padded length; real signals, built-in mothers, pad=True; not together with hop):
+    ``power`` has ceil(n0 / h) columns, the MEANS of |W|^2 over windows of h columns (``cwt_transform_pool``; the last window
+    may be short and is averaged over its own columns; no padded column enters a mean).  ``coi`` is the minimum of ``coi`` over
+    each window -- a window counts as outside the cone as soon as one of its columns is; everything else is unchanged.
     """
     mother = _check_parameter_wavelet(wavelet)
     precision = _default_precision() if precision is None else int(precision)
-    if hop is not None:
-        return _cwt_power_hop(signal, dt, dj, s0, J, mother, freqs, precision, device, pad, hop)
+    if hop is not None or pool is not None:
+        return _cwt_power_hop(signal, dt, dj, s0, J, mother, freqs, precision, device, pad, hop, pool)
     if np.iscomplexobj(signal):
         W, sj, freqs, coi, fft5, fftfreqs = cwt(signal, dt, dj, s0, J, mother, freqs, precision=precision, device=device,
                                                 pad=pad)
@@ -641,22 +702,26 @@ def cwt_power(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, 
     return (P, np.array(sj), freqs, np.array(coi), fft5, np.array(fftfreqs))
 
 
-def _cwt_power_hop(signal, dt, dj, s0, J, mother, freqs, precision, device, pad, hop):
-    """`cwt_power(hop=)`: the power of every hop-th column through cwt_transform_hop."""
+def _cwt_power_hop(signal, dt, dj, s0, J, mother, freqs, precision, device, pad, hop, pool=None):
+    """`cwt_power(hop=)`: the power of every hop-th column through cwt_transform_hop; `cwt_power(pool=)`: the window means of
+    the power through cwt_transform_pool."""
     if np.iscomplexobj(signal):
-        raise ValueError("hop: real signals only")
+        raise ValueError(("pool" if pool is not None else "hop") + ": real signals only")
     in_dtype = getattr(signal, "dtype", None)
     n0 = len(signal)
     user_freqs = freqs is not None
     N, sj, freqs, coi, fftfreqs, bad = _geometry(mother, n0, dt, dj, s0, J, freqs, pad)
-    hop = _check_hop(hop, N, mother, pad)
+    if pool is not None:
+        pool = _check_pool(pool, N, mother, pad, hop)
+    else:
+        hop = _check_hop(hop, N, mother, pad)
     plan_real = np.float64 if precision == 64 else np.float32
     x = np.ascontiguousarray(signal, dtype=plan_real)
     finite = bool(np.isfinite(x).all())
     if bad is not None and not bad.all() and finite:       # (see cwt)
         sj, freqs = sj[~bad], np.asarray(freqs)[~bad]
     kind, param = mother.device_id()
-    ncols = -(-n0 // hop)
+    ncols = -(-n0 // (pool or hop))
     plan = _plan(N, precision, device, sj.size)
     es = np.dtype(plan.real).itemsize
     sc = _Scratch(device)
@@ -664,7 +729,10 @@ def _cwt_power_hop(signal, dt, dj, s0, J, mother, freqs, precision, device, pad,
         xd, xh, Pd = sc.new(n0 * es), sc.new(N * 2 * es), sc.new(sj.size * ncols * es)
         with plan.lock:
             xd.upload(plan, x)
-            _transform_hop(plan, x, xd.ptr, 1, n0, kind, param, dt, sj, hop, xh.ptr, plan.OUT_POWER, Pd.ptr)
+            if pool is not None:
+                _transform_pool(plan, x, xd.ptr, 1, n0, kind, param, dt, sj, pool, xh.ptr, Pd.ptr)
+            else:
+                _transform_hop(plan, x, xd.ptr, 1, n0, kind, param, dt, sj, hop, xh.ptr, plan.OUT_POWER, Pd.ptr)
             P = Pd.download(plan, (sj.size, ncols), plan.real).astype(np.float64)
             xhat = xh.download(plan, (N,), plan.cplx).astype(np.complex128, copy=False)
     finally:
@@ -676,7 +744,8 @@ def _cwt_power_hop(signal, dt, dj, s0, J, mother, freqs, precision, device, pad,
         fft5 = fft5.astype(np.complex64)
     if not user_freqs:
         freqs = np.array(freqs)
-    return (P, np.array(sj), freqs, np.array(coi)[::hop], fft5, np.array(fftfreqs))
+    coi = _pool_coi(coi, pool) if pool is not None else np.array(coi)[::hop]
+    return (P, np.array(sj), freqs, coi, fft5, np.array(fftfreqs))
 
 
 class DevicePower(_DeviceResult):
@@ -700,10 +769,13 @@ class DevicePower(_DeviceResult):
         return self._vector(n0, lambda p: self._plan.reduce_scales(self._buf.ptr, n0, n0, w, 2, coeff, p))
 
 
-def cwt_power_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0, hop=None):
+def cwt_power_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0, hop=None,
+                     pool=None):
     """`cwt_device` with the power output: returns a `DevicePower` (attributes sj, freqs, coi, fft, fftfreqs as in
     `cwt_device`; methods power(), global_power(), scale_average(), close(); device_ptr).  hop=h as in `cwt_device`: the
-    power of every h-th column, ceil(n0 / h) of them -- samples of |W|^2, not its mean over the hop."""
+    power of every h-th column, ceil(n0 / h) of them -- samples of |W|^2, not its mean over the hop.  pool=h as in `cwt_power`:
+    the means of |W|^2 over windows of h columns, ceil(n0 / h) of them, `coi` its minimum over each window; the reductions act
+    on the window means (with a short last window, `global_power()` is the mean of the means, not of the columns)."""
     mother = _check_parameter_wavelet(wavelet)
     precision = _default_precision() if precision is None else int(precision)
     n0 = len(signal)
@@ -714,7 +786,10 @@ def cwt_power_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs
     plan = _plan(N, precision, device, sj.size)
     es = np.dtype(plan.real).itemsize
     ncols = n0
-    if hop is not None:
+    if pool is not None:
+        pool = _check_pool(pool, N, mother, True, hop)
+        ncols, coi = -(-n0 // pool), _pool_coi(coi, pool)
+    elif hop is not None:
         hop = _check_hop(hop, N, mother)
         ncols, coi = -(-n0 // hop), np.asarray(coi)[::hop]
     xd, xh = _hip.DeviceBuffer(n0 * es, device), _hip.DeviceBuffer(N * 2 * es, device)
@@ -723,7 +798,9 @@ def cwt_power_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs
         with plan.lock:
             xs_host = np.ascontiguousarray(signal, dtype=plan.real)
             xd.upload(plan, xs_host)
-            if hop is None:
+            if pool is not None:
+                _transform_pool(plan, xs_host, xd.ptr, 1, n0, kind, param, dt, sj, pool, xh.ptr, Pd.ptr)
+            elif hop is None:
                 _transform(plan, xs_host, xd.ptr, n0, kind, param, dt, sj, xh.ptr, Pd.ptr, power=True)
             else:
                 _transform_hop(plan, xs_host, xd.ptr, 1, n0, kind, param, dt, sj, hop, xh.ptr, plan.OUT_POWER, Pd.ptr)
@@ -743,11 +820,12 @@ def cwt_power_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs
 
 
 def cwt_power_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None,
-                    device=0, max_batch_bytes=8 << 30, hop=None):
+                    device=0, max_batch_bytes=8 << 30, hop=None, pool=None):
     """`cwt_batch` with the power output: `(power, sj, freqs, coi, fft, fftfreqs)` with `power` float64 of shape
     (batch, rows, n0).  Slabs of at most `max_batch_bytes` of power; a slab with a non-finite sample goes through the
     spectra (every coefficient of that signal NaN, as in `cwt_batch`).  hop=h as in `cwt_power`: (batch, rows, ceil(n0 / h))
-    samples of the power at columns ``::h`` and ``coi[::h]``."""
+    samples of the power at columns ``::h`` and ``coi[::h]``.  pool=h as in `cwt_power`: (batch, rows, ceil(n0 / h)) window
+    means of the power, each signal through the single-signal path (its bits do not depend on the batch or the slabs)."""
     mother = _check_parameter_wavelet(wavelet)
     precision = _default_precision() if precision is None else int(precision)
     X = np.atleast_2d(np.asarray(signals))
@@ -761,7 +839,10 @@ def cwt_power_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs
     rows = sj.size
     es = 8 if precision == 64 else 4
     ncols = n0
-    if hop is not None:
+    if pool is not None:
+        pool = _check_pool(pool, N, mother, True, hop)
+        ncols = -(-n0 // pool)
+    elif hop is not None:
         hop = _check_hop(hop, N, mother)
         ncols = -(-n0 // hop)
     slab = int(max(1, min(nb, max_batch_bytes // (rows * ncols * es))))
@@ -777,7 +858,9 @@ def cwt_power_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs
             with plan.lock:
                 xs = np.ascontiguousarray(X[b0:b0 + cnt], dtype=plan.real)
                 xd.upload(plan, xs)
-                if hop is not None:
+                if pool is not None:
+                    _transform_pool(plan, xs, xd.ptr, cnt, n0, kind, param, dt, sj, pool, xh.ptr, Pd.ptr, auto=False)
+                elif hop is not None:
                     # (auto=False: like the call without hop, a batch runs at the plan's tolerance -- a signal's bits do not depend on the slabs)
                     _transform_hop(plan, xs, xd.ptr, cnt, n0, kind, param, dt, sj, hop, xh.ptr, plan.OUT_POWER, Pd.ptr, auto=False)
                 elif np.isfinite(xs).all():
@@ -793,7 +876,9 @@ def cwt_power_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs
     finally:
         sc.free()
     coi = _coi(mother, n0, dt)
-    if hop is not None:
+    if pool is not None:
+        coi = _pool_coi(coi, pool)
+    elif hop is not None:
         coi = np.asarray(coi)[::hop]
     ftfreqs = 2 * np.pi * np.fft.fftfreq(N, dt)
     return (P, sj, freqs, coi, xhat[:, 1:N // 2] / N ** 0.5, ftfreqs[1:N // 2] / (2 * np.pi))
