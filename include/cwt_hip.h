@@ -431,6 +431,37 @@ int cwt_adjoint_rows_scales(cwt_plan* plan, const void* G_dev, int nbatch, int64
                             const double* scales_host, int nrows, void* xbar_dev, int64_t xbar_ld, int accumulate,
                             double* sgrad_dev);
 
+/* ---- synchrosqueezed transform: W reassigned along frequency (Daubechies, Lu and Wu 2011) -----------------------------------------
+ * The sharpened, band-wise invertible time-frequency map built on W: every entry W[j, n] is moved to the row of its own
+ * instantaneous frequency Im(dW / W) / 2 pi.  Two building blocks; the transforms in between are cwt_transform / cwt_transform_rows.
+ *
+ * cwt_spectrum_derivative: yhat[k] = i w_k xhat[k], w_k = 2 pi signed_bin(k) / (nfft dt) formed in double -- the spectrum of the
+ * derivative signal, so that cwt_transform_rows(yhat) is the time derivative dW of cwt_transform_rows(xhat), exactly (no finite
+ * difference).  The Nyquist bin nfft / 2 is written as 0: the derivative of a real signal stays real.  nfft complex each; yhat_dev
+ * may be xhat_dev (in place: the same bits).
+ *
+ * cwt_ssq_reassign: W_dev and dW_dev are nrows x ld complex of the plan's precision T, weights_host nrows doubles (rounded to T),
+ * the output grid is logarithmic, f_k = f_lo 2^(k dv), 0 <= k < nf.  For every entry (j, n), n < ncols:
+ *     a2  = Re W^2 + Im W^2                              (in T, every operation rounded once: no fused multiply-add)
+ *     q   = (Im dW Re W - Re dW Im W) / a2               (in T; = Im(dW / W), radians per time unit)
+ *     pos = log2(q / (2 pi f_lo)) / dv                   (in double, evaluated as (log2 q - log2(2 pi f_lo)) * (1 / dv))
+ *     k   = floor(pos + 0.5)
+ * The entry is KEPT iff a2 > gamma^2 (in double), q is finite, q > 0 and 0 <= k < nf; everything else is dropped: zeros, NaN in W
+ * or dW, negative instantaneous frequencies, entries outside the grid.  Output, T_dev nf x ldt complex:
+ *     T[k, n] = sum_{j kept, k(j, n) = k} w_j W[j, n],   added in ascending j, one product and one addition in T per entry.
+ * With w_j = 1 / sqrt(s_j), dj sqrt(dt) / (cdelta psi0(0)) sum_k Re T[k, n] is TC98 eq. 11 over the kept entries (gamma = 0 and a
+ * grid wide enough: cwt_icwt_reduce of W); the sum over the k of a band extracts a component (cwt_reduce_scales with unit weights).
+ * accumulate = 0: columns < ncols of the nf rows of T are zero-filled on the stream first; 1: T is added to -- the second and later
+ * row chunks of one transform (dW is needed one chunk at a time).  The bits of T do not depend on how the rows are split over
+ * calls.  Columns ncols .. ldt - 1 are never touched.  One thread owns a column: no atomics, the same bits on every run.
+ * Both queue on the plan's stream without host synchronisation.  Refused with CWT_EINVAL before anything is queued: NULL pointers,
+ * dt not positive and finite; nrows outside [1, max_rows], ncols < 1, ld < ncols, ldt < ncols, nf < 1, gamma / f_lo / dv not
+ * finite, gamma < 0, f_lo <= 0, dv <= 0, T overlapping W or dW.                                                               */
+int cwt_spectrum_derivative(cwt_plan* plan, const void* xhat_dev, double dt, void* yhat_dev);
+int cwt_ssq_reassign(cwt_plan* plan, const void* W_dev, const void* dW_dev, int64_t ld, int64_t ncols, int nrows,
+                     const double* weights_host, double gamma, double f_lo, double dv, int nf, void* T_dev, int64_t ldt,
+                     int accumulate);
+
 /* The same two steps at a transform length n0 that is NOT a power of two -- what the reference computes when pyfftw is
  * installed: helpers.py:15-19 then passes n = len(signal), i.e. no zero padding and circular edges -- by Bluestein's
  * chirp-z identity on this plan's power-of-two engine.  The plan must have nfft >= 2*n0 - 1.  xhat_dev: n0 complex

@@ -87,6 +87,9 @@ SYMBOLS = [
                                   C.c_double, _P]),
     ("cwt_reduce_scales", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_int,
                                     C.c_double, _P]),
+    ("cwt_spectrum_derivative", C.c_int, [_P, _P, C.c_double, _P]),
+    ("cwt_ssq_reassign", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                   C.c_double, C.c_int, _P, C.c_int64, C.c_int]),
     ("cwt_time_mean_power", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
     ("cwt_time_mean_real", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
     ("cwt_coherence_histogram", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, C.c_int64, C.c_int, _P]),
@@ -614,6 +617,20 @@ class Plan:
         w = np.ascontiguousarray(weights, dtype=np.float64)
         self.lib.check(self.lib.cwt_reduce_scales(self.h, _P(W_dev), ldw, ncols, w.size, _dptr(w), int(power),
                                                   float(coeff), _P(out_dev)))
+
+    @_locked
+    def spectrum_derivative(self, xhat_dev: int, dt: float, yhat_dev: int):
+        """yhat = i w xhat, the spectrum of the derivative signal (cwt_spectrum_derivative); yhat_dev may be xhat_dev."""
+        self.lib.check(self.lib.cwt_spectrum_derivative(self.h, _P(xhat_dev), float(dt), _P(yhat_dev)))
+
+    @_locked
+    def ssq_reassign(self, W_dev: int, dW_dev: int, ld: int, ncols: int, weights, gamma: float, f_lo: float, dv: float, nf: int,
+                     T_dev: int, ldt: int, accumulate: bool = False):
+        """T[k, n] (+)= sum of weights[j] W[j, n] over the kept entries whose instantaneous frequency Im(dW / W) / 2 pi rounds to
+        bin k of f_lo 2^(k dv) (cwt_ssq_reassign); one weight per row of W and dW."""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        self.lib.check(self.lib.cwt_ssq_reassign(self.h, _P(W_dev), _P(dW_dev), ld, ncols, w.size, _dptr(w), float(gamma),
+                                                 float(f_lo), float(dv), int(nf), _P(T_dev), ldt, int(bool(accumulate))))
 
     @_locked
     def time_mean_power(self, W_dev: int, ldw: int, ncols: int, nrows: int, out_dev: int):

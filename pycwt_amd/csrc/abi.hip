@@ -1090,6 +1090,36 @@ int cwt_abs2(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols, int nro
   });
 }
 
+int cwt_spectrum_derivative(cwt_plan* p, const void* xhat_dev, double dt, void* yhat_dev) {
+  if (!p || !xhat_dev || !yhat_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (!(dt > 0) || !std::isfinite(dt)) return fail(CWT_EINVAL, "dt must be positive");
+  HIPCHECK(hipSetDevice(p->device));
+  return by_precision(p, [&](auto t) { return spectrum_derivative_impl<decltype(t)>(p, xhat_dev, dt, yhat_dev); });
+}
+
+int cwt_ssq_reassign(cwt_plan* p, const void* W_dev, const void* dW_dev, int64_t ld, int64_t ncols, int nrows,
+                     const double* weights, double gamma, double f_lo, double dv, int nf, void* T_dev, int64_t ldt,
+                     int accumulate) {
+  if (!p || !W_dev || !dW_dev || !weights || !T_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (nrows < 1 || nrows > p->max_rows) return fail(CWT_EINVAL, "nrows must be in [1, max_rows]");
+  if (ncols < 1 || ld < ncols || ldt < ncols) return fail(CWT_EINVAL, "need ncols >= 1, ld >= ncols and ldt >= ncols");
+  if (nf < 1) return fail(CWT_EINVAL, "nf must be >= 1");
+  if (!std::isfinite(gamma) || !std::isfinite(f_lo) || !std::isfinite(dv) || gamma < 0 || !(f_lo > 0) || !(dv > 0))
+    return fail(CWT_EINVAL, "need finite gamma >= 0, f_lo > 0 and dv > 0");
+  const size_t cs = 2 * p->esize();
+  const size_t in_bytes = ((size_t(nrows) - 1) * size_t(ld) + size_t(ncols)) * cs;
+  const size_t out_bytes = ((size_t(nf) - 1) * size_t(ldt) + size_t(ncols)) * cs;
+  const uintptr_t t0 = reinterpret_cast<uintptr_t>(T_dev);
+  for (const void* in : {W_dev, dW_dev}) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in);
+    if (a < t0 + out_bytes && t0 < a + in_bytes) return fail(CWT_EINVAL, "T overlaps W or dW");
+  }
+  HIPCHECK(hipSetDevice(p->device));
+  return by_precision(p, [&](auto t) {
+    return ssq_reassign_impl<decltype(t)>(p, W_dev, dW_dev, ld, ncols, nrows, weights, gamma, f_lo, dv, nf, T_dev, ldt, accumulate);
+  });
+}
+
 int cwt_coherence_histogram(cwt_plan* p, const void* r2_dev, int64_t ld, int nrows, const int64_t* lo_dev,
                             const int64_t* hi_dev, int64_t max_span, int nbins, uint64_t* hist_dev) {
   if (!p || !r2_dev || !lo_dev || !hi_dev || !hist_dev) return fail(CWT_EINVAL, "NULL argument");

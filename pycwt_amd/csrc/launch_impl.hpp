@@ -1533,6 +1533,39 @@ int reduce_scales_impl(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncol
   });
 }
 
+// Synchrosqueezing (cwt_kernels_ssq.hpp): the spectrum of the derivative signal, and the reassignment of W along frequency
+template <typename T>
+int spectrum_derivative_impl(cwt_plan* p, const void* xhat_dev, double dt, void* yhat_dev) {
+  const double w1 = 2.0 * 3.14159265358979323846 / (double(p->N) * dt);
+  return timed_launch(p, KC_SSQ_DERIV, [&] {
+    hipLaunchKernelGGL((ssq_spec_deriv<T>), dim3(unsigned((p->N + 255) / 256)), dim3(256), 0, p->stream,
+                       static_cast<const cplx<T>*>(xhat_dev), int(p->N), w1, static_cast<cplx<T>*>(yhat_dev));
+  });
+}
+
+template <typename T>
+int ssq_reassign_impl(cwt_plan* p, const void* W_dev, const void* dW_dev, int64_t ld, int64_t ncols, int nrows,
+                      const double* weights, double gamma, double f_lo, double dv, int nf, void* S_dev, int64_t ldt,
+                      int accumulate) {
+  int rc = upload_reals<T>(p, weights, nrows);
+  if (rc) return rc;
+  if (!accumulate) {
+    rc = timed_launch(p, KC_SSQ_ZERO, [&] {
+      for (int k0 = 0; k0 < nf; k0 += kMaxGridY)                 // (gridDim.y is limited to 65535: slabs of rows)
+        hipLaunchKernelGGL((ssq_zero<T>), dim3(unsigned((ncols + 255) / 256), unsigned(std::min(kMaxGridY, nf - k0))), dim3(256), 0,
+                           p->stream, static_cast<cplx<T>*>(S_dev) + size_t(k0) * size_t(ldt), long(ldt), long(ncols));
+    });
+    if (rc) return rc;
+  }
+  const double l0 = std::log2(2.0 * 3.14159265358979323846 * f_lo);
+  return timed_launch(p, KC_SSQ, [&] {
+    hipLaunchKernelGGL((ssq_reassign<T>), dim3(unsigned((ncols + SSQ_THREADS - 1) / SSQ_THREADS)), dim3(SSQ_THREADS), 0, p->stream,
+                       static_cast<const cplx<T>*>(W_dev), static_cast<const cplx<T>*>(dW_dev), long(ld), long(ncols), nrows,
+                       static_cast<const T*>(p->weights_dev), gamma * gamma, l0, 1.0 / dv, nf, static_cast<cplx<T>*>(S_dev),
+                       long(ldt));
+  });
+}
+
 // Chirp-kernel spectra for length n0 on this plan (N = M >= 2 n0 - 1), cached per n0.
 template <typename T>
 int bluestein_prepare(cwt_plan* p, int64_t n0) {
@@ -1682,6 +1715,9 @@ int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g
   X int coherence_impl<T>(cwt_plan*, const void*, const void*, int, int64_t, int64_t, void*);                                       \
   X int reduce_scales_impl<T, true>(cwt_plan*, const void*, int64_t, int64_t, int, const double*, double, void*);                   \
   X int reduce_scales_impl<T, false>(cwt_plan*, const void*, int64_t, int64_t, int, const double*, double, void*);                  \
+  X int spectrum_derivative_impl<T>(cwt_plan*, const void*, double, void*);                                                         \
+  X int ssq_reassign_impl<T>(cwt_plan*, const void*, const void*, int64_t, int64_t, int, const double*, double, double, double,     \
+                             int, void*, int64_t, int);                                                                             \
   X int random_normal_impl<T>(cwt_plan*, uint64_t, uint64_t, int64_t, double, void*);                                             \
   X int ar1_filter_impl<T>(cwt_plan*, const void*, int64_t, int64_t, double, void*);                                               \
   X int forward_fft_n_impl<T>(cwt_plan*, const void*, int64_t, void*);                                                              \

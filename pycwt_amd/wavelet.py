@@ -585,6 +585,209 @@ def cwt_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None,
     return DeviceTransform(plan, Wd, ro(sj), ro(freqs), ro(coi), None, ro(fftfreqs), mother, dt, n0, spectrum=xh, ncols=ncols)
 
 
+# ---- synchrosqueezed transform ---------------------------------------------------------------------------------------------------
+SSQ_CHUNK_ROWS = None      # rows of dW per chunk (tests); None: as many as the scratch pool's limit allows
+
+
+def _ssq_mother(wavelet, pad=True):
+    """The analytic built-in mothers: a real wavelet (DOG, MexicanHat) has no phase to differentiate, and a duck-typed mother
+    has no filter on the device for the derivative rows."""
+    mother = _check_parameter_wavelet(wavelet)
+    if not pad:
+        raise ValueError("ssq_cwt: pad=False (a transform length that is no power of two) is not built")
+    if not hasattr(mother, "device_id"):
+        raise ValueError(f"ssq_cwt needs a built-in mother (Morlet or Paul); got {type(mother).__name__} without device_id()")
+    if isinstance(mother, DOG) or mother.device_id()[0] not in (0, 1):
+        raise ValueError(f"ssq_cwt needs an analytic wavelet (Morlet or Paul): {type(mother).__name__} is real, "
+                         "its transform has no phase to differentiate")
+    return mother
+
+
+def _ssq_grid(freqs, dj, ssq_freqs, user_freqs):
+    """(f_lo, dv, nf) of the output grid f_k = f_lo 2^(k dv): the caller's, or the geometric grid of the kept rows"""
+    if ssq_freqs is None:
+        if user_freqs:
+            raise ValueError("ssq_cwt: freqs= needs an explicit ssq_freqs=(f_lo, dv, nf)")
+        f = np.asarray(freqs, dtype=np.float64)
+        f_lo, f_hi = float(f.min()), float(f.max())
+        return f_lo, float(dj), int(np.round(np.log2(f_hi / f_lo) / dj)) + 1
+    try:
+        f_lo, dv, nf = ssq_freqs
+        f_lo, dv, nf = float(f_lo), float(dv), int(nf)
+    except (TypeError, ValueError):
+        raise ValueError("ssq_freqs must be (f_lo, dv, nf)") from None
+    if not (np.isfinite(f_lo) and f_lo > 0 and np.isfinite(dv) and dv > 0 and nf >= 1):
+        raise ValueError("ssq_freqs: need f_lo > 0, dv > 0 and nf >= 1")
+    return f_lo, dv, nf
+
+
+def _band_weights(ssq_freqs, nf, band):
+    """unit weights on the bins with band[0] <= f_k < band[1] (all bins without a band)"""
+    if band is None:
+        return np.ones(nf)
+    if ssq_freqs is None:
+        raise ValueError("issq: a band needs the frequencies of the bins (ssq_freqs)")
+    f = np.asarray(ssq_freqs, dtype=np.float64)
+    if f.shape != (nf,):
+        raise ValueError("issq: ssq_freqs must hold one frequency per row of Tx")
+    return np.where((f >= band[0]) & (f < band[1]), 1.0, 0.0)
+
+
+class DeviceSynchrosqueezed(_DeviceResult):
+    """A synchrosqueezed transform that stays on the GPU: T (nf x n0 complex, bin k at ssq_freqs[k]) and the W it was made
+    from (rows x n0, the bits of `cwt_device`), with the grids of `cwt`."""
+
+    def __init__(self, Wbuf, ssq_freqs, *args, **kw):
+        super().__init__(*args, **kw)
+        self._Wbuf, self.ssq_freqs = Wbuf, ssq_freqs
+
+    def T(self):
+        return self._buf.download(self._plan, (self.ssq_freqs.size, self.n0), self._plan.cplx).astype(np.complex128, copy=False)
+
+    def W(self):
+        return self._Wbuf.download(self._plan, self.shape, self._plan.cplx).astype(np.complex128, copy=False)
+
+    @property
+    def W_ptr(self):
+        return self._Wbuf.ptr
+
+    def dW(self):
+        """The time derivative of W (rows x n0), recomputed from the kept spectrum in one call over all rows -- the bits the
+        reassignment saw when it ran in one chunk -- and downloaded.  Needs the spectrum: before `fft` is read or `close()`."""
+        if self._spectrum is None:
+            raise RuntimeError("dW(): the spectrum of this transform has been released")
+        plan, (rows, n0) = self._plan, self.shape
+        es = np.dtype(plan.real).itemsize
+        kind, param = self.mother.device_id()
+        sc = _Scratch(plan.device)
+        try:
+            yh, dWd = sc.new(plan.nfft * 2 * es), sc.new(rows * n0 * 2 * es)
+            with plan.lock:
+                plan.spectrum_derivative(self._spectrum.ptr, self.dt, yh.ptr)
+                plan.transform_rows(yh.ptr, kind, param, self.dt, self.sj, dWd.ptr, n0, n0)
+                return dWd.download(plan, (rows, n0), plan.cplx).astype(np.complex128, copy=False)
+        finally:
+            sc.free()
+
+    def issq(self, dj, band=None):
+        """The signal back from T: dj sqrt(dt) / (cdelta psi(0)) sum_k Re T[k, n] (TC98 eq. 11 over the kept entries); with
+        band=(f1, f2) the sum runs over the bins f1 <= f_k < f2 alone and gives that component."""
+        nf, n0 = self.ssq_freqs.size, self.n0
+        w = _band_weights(self.ssq_freqs, nf, band)
+        total = self._vector(n0, lambda p: self._plan.reduce_scales(self._buf.ptr, n0, n0, w, False, 1.0, p))
+        return dj * np.sqrt(self.dt) / (self.mother.cdelta * self.mother.psi(0)) * total
+
+    def close(self):
+        super().close()
+        if getattr(self, "_Wbuf", None) is not None:
+            self._Wbuf.free()
+            self._Wbuf = None
+
+    __del__ = close
+
+
+def ssq_cwt_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, gamma=None, ssq_freqs=None,
+                   precision=None, device=0, pad=True):
+    """Synchrosqueezed transform whose result stays on the GPU: returns a `DeviceSynchrosqueezed` (T(), W(), ssq_freqs, sj,
+    freqs, coi, issq(dj, band), close()).
+
+    W is `cwt_device`'s for the same call.  Its time derivative dW is the transform of the derivative signal (the spectrum times
+    i w: exact), computed in row chunks; every entry with |W| > gamma is added, as W / sqrt(s_j), into the bin of the logarithmic
+    grid ssq_freqs=(f_lo, dv, nf), f_k = f_lo 2^(k dv), that its instantaneous frequency Im(dW / W) / 2 pi rounds to; entries
+    whose frequency is not positive or lies outside the grid are dropped.  gamma=None: sqrt(eps) std(signal), eps of the
+    precision; ssq_freqs=None: the geometric grid of the kept rows (f_lo = min(freqs), dv = dj).  Morlet and Paul only."""
+    mother = _ssq_mother(wavelet, pad)
+    precision = _default_precision() if precision is None else int(precision)
+    n0 = len(signal)
+    kind, param = mother.device_id()
+    user_freqs = freqs is not None
+    N, sj, freqs, coi, fftfreqs, bad = _geometry(mother, n0, dt, dj, s0, J, freqs, True)
+    finite = bool(np.isfinite(np.asarray(signal, dtype=np.float64)).all())
+    if bad is not None and not bad.all() and finite:                                   # see cwt()
+        sj, freqs = sj[~bad], np.asarray(freqs)[~bad]
+    f_lo, dv, nf = _ssq_grid(freqs, dj, ssq_freqs, user_freqs)
+    grid = f_lo * 2.0 ** (dv * np.arange(nf))
+    rows = sj.size
+    plan = _plan(N, precision, device, max(rows, nf))
+    es = np.dtype(plan.real).itemsize
+    if gamma is None:
+        gamma = float(np.sqrt(np.finfo(plan.real).eps) * np.std(np.asarray(signal, dtype=np.float64))) if finite else 0.0
+    gamma = float(gamma)
+    if not (np.isfinite(gamma) and gamma >= 0):
+        raise ValueError("ssq_cwt: gamma must be finite and >= 0")
+    xd, xh = _hip.DeviceBuffer(n0 * es, device), _hip.DeviceBuffer(N * 2 * es, device)
+    Wd, Td = _hip.DeviceBuffer(rows * n0 * 2 * es, device), _hip.DeviceBuffer(nf * n0 * 2 * es, device)
+    sc = _Scratch(device)
+    try:
+        with plan.lock:
+            xs_host = np.ascontiguousarray(signal, dtype=plan.real)
+            xd.upload(plan, xs_host)
+            _transform(plan, xs_host, xd.ptr, n0, kind, param, dt, sj, xh.ptr, Wd.ptr)
+            if not finite:          # every element of W is NaN (as in cwt): so is every cell of T
+                Td.upload(plan, np.full((nf, n0), complex(np.nan, np.nan), dtype=plan.cplx))
+            else:
+                chunk = SSQ_CHUNK_ROWS or max(1, _pool_limit(plan.lib, device) // (n0 * 2 * es))
+                chunk = int(min(rows, chunk))
+                yh, dWd = sc.new(N * 2 * es), sc.new(chunk * n0 * 2 * es)
+                plan.spectrum_derivative(xh.ptr, dt, yh.ptr)
+                w = 1.0 / np.sqrt(sj)
+                for a in range(0, rows, chunk):
+                    b = min(rows, a + chunk)
+                    plan.transform_rows(yh.ptr, kind, param, dt, sj[a:b], dWd.ptr, n0, n0)
+                    plan.ssq_reassign(Wd.ptr + a * n0 * 2 * es, dWd.ptr, n0, n0, w[a:b], gamma, f_lo, dv, nf, Td.ptr, n0, a > 0)
+            plan.sync()
+    except Exception:
+        for b in (Wd, Td, xh):
+            b.free()
+        raise
+    finally:
+        xd.free()
+        sc.free()
+
+    def ro(a):
+        v = np.asarray(a).view()
+        v.flags.writeable = False
+        return v
+    return DeviceSynchrosqueezed(Wd, ro(grid), plan, Td, ro(sj), ro(freqs), ro(coi), None, ro(fftfreqs), mother, dt, n0, spectrum=xh)
+
+
+def ssq_cwt(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, gamma=None, ssq_freqs=None, precision=None,
+            device=0, pad=True):
+    """Synchrosqueezed wavelet transform (Daubechies, Lu and Wu 2011): returns ``(Tx, ssq_freqs, sj, freqs, coi)``, Tx
+    complex128 of shape nf x n0 with bin k at the ascending ``ssq_freqs[k]``; sj, freqs and coi as `cwt` returns them.  See
+    `ssq_cwt_device`; `issq_cwt` inverts."""
+    H = ssq_cwt_device(signal, dt, dj, s0, J, wavelet, freqs, gamma=gamma, ssq_freqs=ssq_freqs, precision=precision,
+                       device=device, pad=pad)
+    try:
+        return (H.T(), np.array(H.ssq_freqs), np.array(H.sj), np.array(H.freqs), np.array(H.coi))
+    finally:
+        H.close()
+
+
+def issq_cwt(Tx, dt, dj=1 / 12, wavelet="morlet", *, ssq_freqs=None, band=None, precision=None, device=0):
+    """Inverse of `ssq_cwt` from a host matrix: dj sqrt(dt) / (cdelta psi(0)) sum_k Re Tx[k, n]; band=(f1, f2) restricts the sum
+    to the bins f1 <= ssq_freqs[k] < f2 (a component of the signal)."""
+    mother = _check_parameter_wavelet(wavelet)
+    precision = _default_precision() if precision is None else int(precision)
+    Tx = np.asarray(Tx)
+    if Tx.ndim != 2:
+        raise ValueError("issq_cwt: Tx must be a matrix (bins x samples)")
+    nf, n0 = Tx.shape
+    w = _band_weights(ssq_freqs, nf, band)
+    plan = _reduction_plan(precision, device, nf)
+    es = np.dtype(plan.real).itemsize
+    Td, out = _hip.DeviceBuffer(nf * n0 * 2 * es, device), _hip.DeviceBuffer(n0 * es, device)
+    try:
+        with plan.lock:
+            Td.upload(plan, np.ascontiguousarray(Tx, dtype=plan.cplx))
+            plan.reduce_scales(Td.ptr, n0, n0, w, False, 1.0, out.ptr)
+            total = out.download(plan, (n0,), plan.real).astype(np.float64)
+    finally:
+        Td.free()
+        out.free()
+    return dj * np.sqrt(dt) / (mother.cdelta * mother.psi(0)) * total
+
+
 def cwt_batch(signals, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None,
               device=0, max_batch_bytes=8 << 30):
     """`cwt` of a batch of equally long signals (2-D array, one signal per row) with one scale grid --
