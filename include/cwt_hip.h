@@ -462,6 +462,34 @@ int cwt_ssq_reassign(cwt_plan* plan, const void* W_dev, const void* dW_dev, int6
                      const double* weights_host, double gamma, double f_lo, double dv, int nf, void* T_dev, int64_t ldt,
                      int accumulate);
 
+/* ---- gradient of the synchrosqueezed transform ---------------------------------------------------------------------------------
+ * Given the bin k(j, n) of every entry, T[k, n] = sum_{kept j, k(j, n) = k} w_j W[j, n] is linear in W; k(j, n) and the keep / drop
+ * decision are piecewise constant in W, dW and gamma.  So T is differentiable almost everywhere and the derivative runs through
+ * the values of W alone: for a cotangent gT of T (torch's convention for a map complex-linear in W with real weights)
+ *     gW[j, n] = w_j gT[k(j, n), n]   for a kept entry,   0 for a dropped one;   the derivative with respect to dW is zero.
+ * The forward records the bins, the backward gathers through them: neither W nor dW is needed again.
+ *
+ * cwt_ssq_reassign_bins: cwt_ssq_reassign -- the same arguments, rules, refusals and the same bits of T, in one call or split into
+ * row chunks with accumulate (the two calls share the decision, the accumulation and the walk of a column) -- that also writes
+ *     bins[j, n] = the bin k of a kept entry, -1 of a dropped one,   j < nrows, n < ncols,
+ * bins_dev nrows x ldb int16.  Columns ncols .. ldb - 1 of bins (as of T) are never touched.  Refused in addition, with CWT_EINVAL
+ * before anything is queued: nf > 32767, bins_dev NULL, ldb < ncols, bins overlapping W, dW or T.
+ *
+ * cwt_ssq_gather: for every j < nrows, n < ncols, with k = bins[j, n] (bins_dev nrows x ldb int16, gT_dev nf x ldt complex of the
+ * plan's precision T, G_dev nrows x ldg complex, weights_host nrows doubles rounded to T):
+ *     G[j, n] = (w_j Re gT[k, n], w_j Im gT[k, n])      one product per component in T, no fused multiply-add
+ *     G[j, n] = +0 exactly where k < 0 -- by selection, not by a multiplication: a NaN or Inf in a cell of gT reaches the entries of
+ *               that cell and no others.  k >= nf is the caller's error: treated as dropped, nothing outside gT is read.
+ * Columns ncols .. ldg - 1 of G are never touched.  Queued on the plan's stream without host synchronisation; every element of G
+ * is written by one thread: no atomics, the same bits on every run.  With the bins of cwt_ssq_reassign_bins the two are transposes:
+ * Re sum conj(gT) T = Re sum conj(G) W.  Refused with CWT_EINVAL before anything is queued: NULL pointers, nrows outside
+ * [1, max_rows], ncols < 1, nf < 1, nf > 32767, ldt / ldb / ldg < ncols, G overlapping gT or bins.                              */
+int cwt_ssq_reassign_bins(cwt_plan* plan, const void* W_dev, const void* dW_dev, int64_t ld, int64_t ncols, int nrows,
+                          const double* weights_host, double gamma, double f_lo, double dv, int nf, void* T_dev, int64_t ldt,
+                          int accumulate, void* bins_dev, int64_t ldb);
+int cwt_ssq_gather(cwt_plan* plan, const void* gT_dev, int64_t ldt, int nf, const void* bins_dev, int64_t ldb,
+                   const double* weights_host, int nrows, int64_t ncols, void* G_dev, int64_t ldg);
+
 /* The same two steps at a transform length n0 that is NOT a power of two -- what the reference computes when pyfftw is
  * installed: helpers.py:15-19 then passes n = len(signal), i.e. no zero padding and circular edges -- by Bluestein's
  * chirp-z identity on this plan's power-of-two engine.  The plan must have nfft >= 2*n0 - 1.  xhat_dev: n0 complex

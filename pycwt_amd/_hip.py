@@ -90,6 +90,9 @@ SYMBOLS = [
     ("cwt_spectrum_derivative", C.c_int, [_P, _P, C.c_double, _P]),
     ("cwt_ssq_reassign", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,
                                    C.c_double, C.c_int, _P, C.c_int64, C.c_int]),
+    ("cwt_ssq_reassign_bins", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,
+                                        C.c_double, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64]),
+    ("cwt_ssq_gather", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int64, _P, C.c_int64]),
     ("cwt_time_mean_power", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
     ("cwt_time_mean_real", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
     ("cwt_coherence_histogram", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, C.c_int64, C.c_int, _P]),
@@ -631,6 +634,24 @@ class Plan:
         w = np.ascontiguousarray(weights, dtype=np.float64)
         self.lib.check(self.lib.cwt_ssq_reassign(self.h, _P(W_dev), _P(dW_dev), ld, ncols, w.size, _dptr(w), float(gamma),
                                                  float(f_lo), float(dv), int(nf), _P(T_dev), ldt, int(bool(accumulate))))
+
+    @_locked
+    def ssq_reassign_bins(self, W_dev: int, dW_dev: int, ld: int, ncols: int, weights, gamma: float, f_lo: float, dv: float,
+                          nf: int, T_dev: int, ldt: int, accumulate: bool, bins_dev: int, ldb: int):
+        """`ssq_reassign` (the same bits of T) that also records bins[j, n], int16: the bin of a kept entry, -1 of a dropped one
+        (cwt_ssq_reassign_bins)."""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        self.lib.check(self.lib.cwt_ssq_reassign_bins(self.h, _P(W_dev), _P(dW_dev), ld, ncols, w.size, _dptr(w), float(gamma),
+                                                      float(f_lo), float(dv), int(nf), _P(T_dev), ldt, int(bool(accumulate)),
+                                                      _P(bins_dev), ldb))
+
+    @_locked
+    def ssq_gather(self, gT_dev: int, ldt: int, nf: int, bins_dev: int, ldb: int, weights, ncols: int, G_dev: int, ldg: int):
+        """G[j, n] = weights[j] gT[bins[j, n], n], +0 where the bin is negative (cwt_ssq_gather): the transpose of the
+        reassignment through the bins it recorded; one weight per row of bins and G."""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        self.lib.check(self.lib.cwt_ssq_gather(self.h, _P(gT_dev), ldt, int(nf), _P(bins_dev), ldb, _dptr(w), w.size, ncols,
+                                               _P(G_dev), ldg))
 
     @_locked
     def time_mean_power(self, W_dev: int, ldw: int, ncols: int, nrows: int, out_dev: int):

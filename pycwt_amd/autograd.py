@@ -10,7 +10,8 @@ import numpy as np
 
 from . import _hip
 from .parallel import HipEngine
-from .wavelet import _check_hop, _check_pool, _pool_coi, _check_parameter_wavelet, _coi, _device_id, _geometry, _nan_rows, _next_pow2
+from .wavelet import (_band_weights, _check_hop, _check_pool, _pool_coi, _check_parameter_wavelet, _coi, _device_id, _geometry, _nan_rows,
+                      _next_pow2, _ssq_grid, _ssq_mother)
 
 _engines: dict = {}       # (nfft, precision, device, library) -> HipEngine: keeps the plan and its cached row tables
 _engines_lock = threading.Lock()
@@ -233,7 +234,68 @@ def _function(torch):
             del G
             return out + (None,) * 8
 
-    return CwtRows, CwtPower, CwtRowsScales, CwtPowerScales
+    class SsqRows(torch.autograd.Function):
+        """The synchrosqueezed transform of x (n0,) or (B, n0), signal by signal.  Between forward and backward only the map of
+        bins (int16, ... x rows x n0) and the geometry are held: neither x, W nor dW."""
+        @staticmethod
+        def forward(ctx, x, eng, kind, param, dt, sj, grid, gammas):
+            from . import wavelet
+            f_lo, dv, nf = grid
+            n0, rows = x.shape[-1], sj.size
+            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+            Tx = torch.empty(tuple(x.shape[:-1]) + (nf, n0), dtype=cplx_t, device=x.device)
+            bins = torch.empty(tuple(x.shape[:-1]) + (rows, n0), dtype=torch.int16, device=x.device)
+            tol = _tolerance()
+            _on_current_stream(torch, eng, x.device)
+            eng.plan.set_tolerance(tol)
+            es = 8 if x.dtype == torch.float64 else 4
+            chunk = wavelet.SSQ_CHUNK_ROWS or max(1, wavelet._pool_limit(eng.plan.lib, x.device.index or 0) // (n0 * 2 * es))
+            chunk = int(min(rows, chunk))
+            w = 1.0 / np.sqrt(sj)
+            W = torch.empty((rows, n0), dtype=cplx_t, device=x.device)
+            dW = torch.empty((chunk, n0), dtype=cplx_t, device=x.device)
+            xhat = torch.empty((eng.plan.nfft,), dtype=cplx_t, device=x.device)
+            for xb, Tb, bb, gamma in zip(x.reshape(-1, n0), Tx.reshape(-1, nf, n0), bins.reshape(-1, rows, n0), gammas):
+                if gamma is None:                                # a non-finite sample: every element of W is NaN, so is every cell of T
+                    Tb.fill_(complex(float("nan"), float("nan")))
+                    bb.fill_(-1)
+                    continue
+                eng.transform(xb, n0, xhat, kind, param, dt, sj, W, n0)                    # W as CwtRows.forward computes it
+                eng.plan.spectrum_derivative(xhat.data_ptr(), dt, xhat.data_ptr())        # the spectrum times i w, in place
+                for a in range(0, rows, chunk):
+                    b = min(rows, a + chunk)
+                    eng.rows(xhat, kind, param, dt, sj[a:b], dW[:b - a], n0)
+                    eng.ssq_reassign_bins(W[a:b], dW[:b - a], w[a:b], gamma, f_lo, dv, Tb, a > 0, bb[a:b])
+            del W, dW, xhat
+            ctx.save_for_backward(bins)
+            ctx.geometry = (eng, kind, param, dt, sj, tol, nf, n0, [g is not None for g in gammas])
+            ctx.ssq_map = True                                   # (what _ssq_saved_bins recognises the node by)
+            return Tx
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gT):
+            (bins,) = ctx.saved_tensors
+            eng, kind, param, dt, sj, tol, nf, n0, finite = ctx.geometry
+            real_t = torch.float64 if gT.dtype in (torch.complex128, torch.float64) else torch.float32
+            cplx_t = torch.complex128 if real_t == torch.float64 else torch.complex64
+            g = gT.to(cplx_t).resolve_conj().contiguous()        # (a lazily conjugated cotangent keeps its bits unconjugated in memory)
+            rows = sj.size
+            xbar = torch.empty(tuple(g.shape[:-2]) + (n0,), dtype=real_t, device=g.device)
+            _on_current_stream(torch, eng, g.device)
+            eng.plan.set_tolerance(tol)
+            w = 1.0 / np.sqrt(sj)
+            G = torch.empty((rows, n0), dtype=cplx_t, device=g.device)      # one signal's rows x n0, whatever the batch
+            for gb, bb, xb, ok in zip(g.reshape(-1, nf, n0), bins.reshape(-1, rows, n0), xbar.reshape(-1, n0), finite):
+                if not ok:
+                    xb.fill_(float("nan"))
+                    continue
+                eng.ssq_gather(gb, bb, w, G)
+                eng.plan.adjoint_rows(G.data_ptr(), 1, rows * n0, n0, n0, kind, param, dt, sj, xb.data_ptr(), n0)
+            del G
+            return xbar, None, None, None, None, None, None, None
+
+    return CwtRows, CwtPower, CwtRowsScales, CwtPowerScales, SsqRows
 
 
 _fn = None
@@ -396,3 +458,68 @@ def cwt_power_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None,
         _fn = _function(torch)
     P = _fn[1].apply(x.contiguous(), eng, kind, param, float(dt), sj, hop, pool)
     return P, sj, freqs, coi
+
+
+def ssq_cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, gamma=None, ssq_freqs=None):
+    """Synchrosqueezed wavelet transform of a torch tensor, differentiable with respect to it.
+
+    x: (n0,) or (B, n0), float64 or float32, on a GPU (CPU tensors only under the CPU emulation of the library, as ``cwt_torch``).
+    Returns ``(Tx, ssq_freqs, sj, freqs, coi)``: Tx complex, (nf, n0) or (B, nf, n0), on x's device and produced on torch's
+    current stream, bin k at the ascending ``ssq_freqs[k]``; the grids are NumPy arrays as ``ssq_cwt`` returns them for the same
+    call, the default ``ssq_freqs`` and the default gamma (``sqrt(eps) std(x)``, of every signal by itself) are those of
+    ``ssq_cwt_device``.  Refusals as ``ssq_cwt``: DOG / MexicanHat and duck-typed mothers, ``freqs=`` without an explicit
+    ``ssq_freqs=(f_lo, dv, nf)``; and nf > 32767 (the map of bins is int16).  A signal with a non-finite sample gives NaN in all of
+    its Tx and NaN in its gradient.  Whether the signals are finite (and, by default, their standard deviations) is read back
+    to the host: one synchronisation per call.
+
+    Forward, signal by signal: W as ``cwt_torch`` computes it, dW from the spectrum times i w in row chunks
+    (``cwt_transform_rows``), ``cwt_ssq_reassign_bins`` per chunk; W and dW are freed before it returns.  Given the bin of every
+    entry T is linear in W, and the bins are piecewise constant in x: the gradient is exact almost everywhere and runs through
+    the values of W alone.  Saved for the backward: the bins (int16, 2 B per entry of W) and the geometry -- not x, W or dW.
+    Backward, signal by signal: ``cwt_ssq_gather`` of the cotangent through the bins into G (one signal's rows x n0), then
+    ``cwt_adjoint_rows`` of G.  Once differentiable; no gradient with respect to the scales, gamma or the grid."""
+    global _fn
+    mother = _ssq_mother(wavelet)
+    user_freqs = freqs is not None
+    torch, eng, kind, param, sj, freqs, coi, _ = _prepare("ssq_cwt_torch", x, dt, dj, s0, J, mother, freqs, True)
+    f_lo, dv, nf = _ssq_grid(freqs, dj, ssq_freqs, user_freqs)
+    if nf > 32767:
+        raise ValueError("ssq_cwt_torch: at most 32767 bins (the map saved for the backward is int16)")
+    xs = x.detach().reshape(-1, x.shape[-1])
+    finite = torch.isfinite(xs).all(dim=1)
+    if gamma is None:
+        eps = float(np.finfo(np.float64 if x.dtype == torch.float64 else np.float32).eps)
+        stat = torch.stack([finite.to(torch.float64), xs.to(torch.float64).std(dim=1, unbiased=False)]).cpu().numpy()
+        gammas = [float(np.sqrt(eps) * s) if ok else None for ok, s in zip(stat[0], stat[1])]
+    else:
+        gamma = float(gamma)
+        if not (np.isfinite(gamma) and gamma >= 0):
+            raise ValueError("ssq_cwt: gamma must be finite and >= 0")
+        gammas = [gamma if ok else None for ok in finite.cpu().numpy()]
+    if _fn is None:
+        _fn = _function(torch)
+    Tx = _fn[4].apply(x.contiguous(), eng, kind, param, float(dt), sj, (f_lo, dv, nf), gammas)
+    return Tx, f_lo * 2.0 ** (dv * np.arange(nf)), sj, freqs, coi
+
+
+def issq_cwt_torch(Tx, dt, dj=1 / 12, wavelet="morlet", *, ssq_freqs=None, band=None):
+    """Inverse of ``ssq_cwt_torch`` in plain torch operations (it differentiates by itself): ``dj sqrt(dt) / (cdelta psi(0))
+    sum_k Re Tx[k, n]`` for Tx (nf, n0) or (B, nf, n0); band=(f1, f2) restricts the sum to the bins f1 <= ssq_freqs[k] < f2 (a
+    component of the signal), the rule of ``issq_cwt``.  Real where the mother's psi(0) is."""
+    import torch
+    mother = _check_parameter_wavelet(wavelet)
+    if not torch.is_tensor(Tx) or not Tx.is_complex() or Tx.dim() not in (2, 3):
+        raise ValueError("issq_cwt_torch: Tx must be a complex tensor (bins x samples) or (B x bins x samples)")
+    w = torch.as_tensor(_band_weights(ssq_freqs, Tx.shape[-2], band), dtype=Tx.real.dtype, device=Tx.device)
+    total = (Tx.real * w[:, None]).sum(dim=-2)
+    coeff = complex(dj * np.sqrt(dt) / (mother.cdelta * mother.psi(0)))
+    return total * (coeff.real if coeff.imag == 0 else coeff)
+
+
+def _ssq_saved_bins(Tx):
+    """The map a ``Tx`` of ``ssq_cwt_torch`` holds for its backward (tests): int16, (..., rows, n0), the bin of every kept entry
+    of W and -1 of every dropped one.  Only a Tx that requires a gradient holds one."""
+    fn = getattr(Tx, "grad_fn", None)
+    if fn is None or not getattr(fn, "ssq_map", False):
+        raise ValueError("not the output of ssq_cwt_torch for an input that requires a gradient")
+    return fn.saved_tensors[0]

@@ -1097,9 +1097,9 @@ int cwt_spectrum_derivative(cwt_plan* p, const void* xhat_dev, double dt, void* 
   return by_precision(p, [&](auto t) { return spectrum_derivative_impl<decltype(t)>(p, xhat_dev, dt, yhat_dev); });
 }
 
-int cwt_ssq_reassign(cwt_plan* p, const void* W_dev, const void* dW_dev, int64_t ld, int64_t ncols, int nrows,
-                     const double* weights, double gamma, double f_lo, double dv, int nf, void* T_dev, int64_t ldt,
-                     int accumulate) {
+// what cwt_ssq_reassign refuses (cwt_ssq_reassign_bins: the same, then its own)
+static int ssq_reassign_check(cwt_plan* p, const void* W_dev, const void* dW_dev, int64_t ld, int64_t ncols, int nrows,
+                              const double* weights, double gamma, double f_lo, double dv, int nf, void* T_dev, int64_t ldt) {
   if (!p || !W_dev || !dW_dev || !weights || !T_dev) return fail(CWT_EINVAL, "NULL argument");
   if (nrows < 1 || nrows > p->max_rows) return fail(CWT_EINVAL, "nrows must be in [1, max_rows]");
   if (ncols < 1 || ld < ncols || ldt < ncols) return fail(CWT_EINVAL, "need ncols >= 1, ld >= ncols and ldt >= ncols");
@@ -1114,9 +1114,65 @@ int cwt_ssq_reassign(cwt_plan* p, const void* W_dev, const void* dW_dev, int64_t
     const uintptr_t a = reinterpret_cast<uintptr_t>(in);
     if (a < t0 + out_bytes && t0 < a + in_bytes) return fail(CWT_EINVAL, "T overlaps W or dW");
   }
+  return CWT_OK;
+}
+
+int cwt_ssq_reassign(cwt_plan* p, const void* W_dev, const void* dW_dev, int64_t ld, int64_t ncols, int nrows,
+                     const double* weights, double gamma, double f_lo, double dv, int nf, void* T_dev, int64_t ldt,
+                     int accumulate) {
+  const int rc = ssq_reassign_check(p, W_dev, dW_dev, ld, ncols, nrows, weights, gamma, f_lo, dv, nf, T_dev, ldt);
+  if (rc) return rc;
   HIPCHECK(hipSetDevice(p->device));
   return by_precision(p, [&](auto t) {
-    return ssq_reassign_impl<decltype(t)>(p, W_dev, dW_dev, ld, ncols, nrows, weights, gamma, f_lo, dv, nf, T_dev, ldt, accumulate);
+    return ssq_reassign_impl<decltype(t)>(p, W_dev, dW_dev, ld, ncols, nrows, weights, gamma, f_lo, dv, nf, T_dev, ldt, accumulate,
+                                          nullptr, 0);
+  });
+}
+
+// [a, a + na) and [b, b + nb) share a byte
+static bool blocks_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + nb && y < x + na;
+}
+
+int cwt_ssq_reassign_bins(cwt_plan* p, const void* W_dev, const void* dW_dev, int64_t ld, int64_t ncols, int nrows,
+                          const double* weights, double gamma, double f_lo, double dv, int nf, void* T_dev, int64_t ldt,
+                          int accumulate, void* bins_dev, int64_t ldb) {
+  const int rc = ssq_reassign_check(p, W_dev, dW_dev, ld, ncols, nrows, weights, gamma, f_lo, dv, nf, T_dev, ldt);
+  if (rc) return rc;
+  if (!bins_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (nf > 32767) return fail(CWT_EINVAL, "the map of bins is int16: nf must be <= 32767");
+  if (ldb < ncols) return fail(CWT_EINVAL, "need ldb >= ncols");
+  const size_t cs = 2 * p->esize();
+  const size_t in_bytes = ((size_t(nrows) - 1) * size_t(ld) + size_t(ncols)) * cs;
+  const size_t out_bytes = ((size_t(nf) - 1) * size_t(ldt) + size_t(ncols)) * cs;
+  const size_t bin_bytes = ((size_t(nrows) - 1) * size_t(ldb) + size_t(ncols)) * sizeof(int16_t);
+  if (blocks_overlap(bins_dev, bin_bytes, W_dev, in_bytes) || blocks_overlap(bins_dev, bin_bytes, dW_dev, in_bytes) ||
+      blocks_overlap(bins_dev, bin_bytes, T_dev, out_bytes))
+    return fail(CWT_EINVAL, "bins overlaps W, dW or T");
+  HIPCHECK(hipSetDevice(p->device));
+  return by_precision(p, [&](auto t) {
+    return ssq_reassign_impl<decltype(t)>(p, W_dev, dW_dev, ld, ncols, nrows, weights, gamma, f_lo, dv, nf, T_dev, ldt, accumulate,
+                                          bins_dev, ldb);
+  });
+}
+
+int cwt_ssq_gather(cwt_plan* p, const void* gT_dev, int64_t ldt, int nf, const void* bins_dev, int64_t ldb, const double* weights,
+                   int nrows, int64_t ncols, void* G_dev, int64_t ldg) {
+  if (!p || !gT_dev || !bins_dev || !weights || !G_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (nrows < 1 || nrows > p->max_rows) return fail(CWT_EINVAL, "nrows must be in [1, max_rows]");
+  if (ncols < 1 || ldt < ncols || ldb < ncols || ldg < ncols)
+    return fail(CWT_EINVAL, "need ncols >= 1, ldt >= ncols, ldb >= ncols and ldg >= ncols");
+  if (nf < 1 || nf > 32767) return fail(CWT_EINVAL, "nf must be in [1, 32767]");
+  const size_t cs = 2 * p->esize();
+  const size_t g_bytes = ((size_t(nrows) - 1) * size_t(ldg) + size_t(ncols)) * cs;
+  const size_t t_bytes = ((size_t(nf) - 1) * size_t(ldt) + size_t(ncols)) * cs;
+  const size_t bin_bytes = ((size_t(nrows) - 1) * size_t(ldb) + size_t(ncols)) * sizeof(int16_t);
+  if (blocks_overlap(G_dev, g_bytes, gT_dev, t_bytes) || blocks_overlap(G_dev, g_bytes, bins_dev, bin_bytes))
+    return fail(CWT_EINVAL, "G overlaps gT or bins");
+  HIPCHECK(hipSetDevice(p->device));
+  return by_precision(p, [&](auto t) {
+    return ssq_gather_impl<decltype(t)>(p, gT_dev, ldt, nf, bins_dev, ldb, weights, nrows, ncols, G_dev, ldg);
   });
 }
 

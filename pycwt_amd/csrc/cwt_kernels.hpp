@@ -858,3 +858,4 @@ k_pass_b_ct(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
 #include "cwt_kernels_sgrad.hpp"     // gradients with respect to the scales and f0: one reduction over each row's band
 #include "cwt_kernels_pool.hpp"      // time-pooled scalogram: window means of |W|^2 (polynomial rows in the kernel, the others from scratch)
 #include "cwt_kernels_ssq.hpp"       // synchrosqueezed transform: spectrum of the derivative signal, reassignment of W along frequency
+#include "cwt_kernels_ssq_grad.hpp"  // gradient of the synchrosqueezed transform: reassignment that records the bins, gather through them

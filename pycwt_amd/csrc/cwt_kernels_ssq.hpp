@@ -52,20 +52,26 @@ __global__ void ssq_zero(cplx<T>* __restrict__ S, long ldt, long ncols) {
   if (n < ncols) S[long(blockIdx.y) * ldt + n] = mk<T>(T(0), T(0));
 }
 
-// One entry (v = W[j, n], d = dW[j, n], weight wj) into the column whose first element is col; cur = the bin of the cell held in
-// acc (-1: none yet)
+// One entry (v = W[j, n], d = dW[j, n]) in two steps, shared with the kernel of cwt_kernels_ssq_grad.hpp that also records the bins:
+//   ssq_bin   the decision: the bin k of a kept entry, -1 of a dropped one
+//   ssq_add   the accumulation of a kept entry (weight wj) into the column whose first element is col; cur = the bin of the cell
+//             held in acc (-1: none yet)
 template <typename T>
-__device__ __forceinline__ void ssq_entry(const cplx<T> v, const cplx<T> d, const T wj, double g2, double l0, double inv_dv,
-                                          int nf, cplx<T>* col, long ldt, int& cur, cplx<T>& acc) {
+__device__ __forceinline__ int ssq_bin(const cplx<T> v, const cplx<T> d, double g2, double l0, double inv_dv, int nf) {
 #pragma clang fp contract(off)
   const T rr = v.x * v.x, ii = v.y * v.y;
   const T a2 = rr + ii;
   const T p1 = d.y * v.x, p2 = d.x * v.y;
   const T q = (p1 - p2) / a2;
-  if (!(double(a2) > g2) || !(q > T(0))) return;                      // (a NaN fails either comparison)
+  if (!(double(a2) > g2) || !(q > T(0))) return -1;                   // (a NaN fails either comparison)
   const double kf = floor((log2(double(q)) - l0) * inv_dv + 0.5);
-  if (!(kf >= 0.0 && kf < double(nf))) return;                        // (q = inf ends here)
-  const int k = int(kf);
+  if (!(kf >= 0.0 && kf < double(nf))) return -1;                     // (q = inf ends here)
+  return int(kf);
+}
+
+template <typename T>
+__device__ __forceinline__ void ssq_add(const cplx<T> v, const T wj, const int k, cplx<T>* col, long ldt, int& cur, cplx<T>& acc) {
+#pragma clang fp contract(off)
   if (k != cur) {
     if (cur >= 0) col[long(cur) * ldt] = acc;
     acc = col[long(k) * ldt];
@@ -76,15 +82,15 @@ __device__ __forceinline__ void ssq_entry(const cplx<T> v, const cplx<T> d, cons
   acc.y += ti;
 }
 
+// The walk of one thread down its column (W, dW, col and bcol point at the column's first element): rows ascending, SSQ_INFLIGHT
+// rows in flight, the current cell in registers.  BINS: bcol[j ldb] = the bin of entry j as int16, -1 for a dropped one (2 B
+// written beside the 2 x 16 B read; nf <= 32767 is the caller's business); without BINS bcol is not touched.
 constexpr int SSQ_THREADS = 128, SSQ_INFLIGHT = 8;
-template <typename T>
-__global__ void __launch_bounds__(SSQ_THREADS)
-ssq_reassign(const cplx<T>* __restrict__ W, const cplx<T>* __restrict__ dW, long ld, long ncols, int nrows,
-             const T* __restrict__ w, double g2, double l0, double inv_dv, int nf, cplx<T>* S, long ldt) {
-  const long n = long(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (n >= ncols) return;
+template <typename T, bool BINS>
+__device__ __forceinline__ void ssq_column(const cplx<T>* __restrict__ W, const cplx<T>* __restrict__ dW, long ld, int nrows,
+                                           const T* __restrict__ w, double g2, double l0, double inv_dv, int nf, cplx<T>* col,
+                                           long ldt, short* bcol, long ldb) {
   constexpr int U = SSQ_INFLIGHT;
-  cplx<T>* col = S + n;
   int cur = -1;
   cplx<T> acc = mk<T>(T(0), T(0));
   int j = 0;
@@ -92,15 +98,32 @@ ssq_reassign(const cplx<T>* __restrict__ W, const cplx<T>* __restrict__ dW, long
     cplx<T> v[U], d[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      v[u] = load_once<T>(W + long(j + u) * ld + n);
-      d[u] = load_once<T>(dW + long(j + u) * ld + n);
+      v[u] = load_once<T>(W + long(j + u) * ld);
+      d[u] = load_once<T>(dW + long(j + u) * ld);
     }
 #pragma unroll
-    for (int u = 0; u < U; ++u) ssq_entry<T>(v[u], d[u], w[j + u], g2, l0, inv_dv, nf, col, ldt, cur, acc);
+    for (int u = 0; u < U; ++u) {
+      const int k = ssq_bin<T>(v[u], d[u], g2, l0, inv_dv, nf);
+      if (BINS) __builtin_nontemporal_store(short(k), bcol + long(j + u) * ldb);
+      if (k >= 0) ssq_add<T>(v[u], w[j + u], k, col, ldt, cur, acc);
+    }
   }
-  for (; j < nrows; ++j)
-    ssq_entry<T>(load_once<T>(W + long(j) * ld + n), load_once<T>(dW + long(j) * ld + n), w[j], g2, l0, inv_dv, nf, col, ldt, cur, acc);
+  for (; j < nrows; ++j) {
+    const cplx<T> v = load_once<T>(W + long(j) * ld), d = load_once<T>(dW + long(j) * ld);
+    const int k = ssq_bin<T>(v, d, g2, l0, inv_dv, nf);
+    if (BINS) __builtin_nontemporal_store(short(k), bcol + long(j) * ldb);
+    if (k >= 0) ssq_add<T>(v, w[j], k, col, ldt, cur, acc);
+  }
   if (cur >= 0) col[long(cur) * ldt] = acc;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(SSQ_THREADS)
+ssq_reassign(const cplx<T>* __restrict__ W, const cplx<T>* __restrict__ dW, long ld, long ncols, int nrows,
+             const T* __restrict__ w, double g2, double l0, double inv_dv, int nf, cplx<T>* S, long ldt) {
+  const long n = long(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (n >= ncols) return;
+  ssq_column<T, false>(W + n, dW + n, ld, nrows, w, g2, l0, inv_dv, nf, S + n, ldt, nullptr, 0);
 }
 
 }  // namespace cwt

@@ -1546,7 +1546,7 @@ int spectrum_derivative_impl(cwt_plan* p, const void* xhat_dev, double dt, void*
 template <typename T>
 int ssq_reassign_impl(cwt_plan* p, const void* W_dev, const void* dW_dev, int64_t ld, int64_t ncols, int nrows,
                       const double* weights, double gamma, double f_lo, double dv, int nf, void* S_dev, int64_t ldt,
-                      int accumulate) {
+                      int accumulate, void* bins_dev, int64_t ldb) {       // bins_dev: NULL, or the map cwt_ssq_reassign_bins records
   int rc = upload_reals<T>(p, weights, nrows);
   if (rc) return rc;
   if (!accumulate) {
@@ -1558,11 +1558,34 @@ int ssq_reassign_impl(cwt_plan* p, const void* W_dev, const void* dW_dev, int64_
     if (rc) return rc;
   }
   const double l0 = std::log2(2.0 * 3.14159265358979323846 * f_lo);
+  const dim3 grid(unsigned((ncols + SSQ_THREADS - 1) / SSQ_THREADS));
   return timed_launch(p, KC_SSQ, [&] {
-    hipLaunchKernelGGL((ssq_reassign<T>), dim3(unsigned((ncols + SSQ_THREADS - 1) / SSQ_THREADS)), dim3(SSQ_THREADS), 0, p->stream,
-                       static_cast<const cplx<T>*>(W_dev), static_cast<const cplx<T>*>(dW_dev), long(ld), long(ncols), nrows,
-                       static_cast<const T*>(p->weights_dev), gamma * gamma, l0, 1.0 / dv, nf, static_cast<cplx<T>*>(S_dev),
-                       long(ldt));
+    if (bins_dev)
+      hipLaunchKernelGGL((ssqg_reassign_bins<T>), grid, dim3(SSQ_THREADS), 0, p->stream, static_cast<const cplx<T>*>(W_dev),
+                         static_cast<const cplx<T>*>(dW_dev), long(ld), long(ncols), nrows, static_cast<const T*>(p->weights_dev),
+                         gamma * gamma, l0, 1.0 / dv, nf, static_cast<cplx<T>*>(S_dev), long(ldt), static_cast<short*>(bins_dev),
+                         long(ldb));
+    else
+      hipLaunchKernelGGL((ssq_reassign<T>), grid, dim3(SSQ_THREADS), 0, p->stream,
+                         static_cast<const cplx<T>*>(W_dev), static_cast<const cplx<T>*>(dW_dev), long(ld), long(ncols), nrows,
+                         static_cast<const T*>(p->weights_dev), gamma * gamma, l0, 1.0 / dv, nf, static_cast<cplx<T>*>(S_dev),
+                         long(ldt));
+  });
+}
+
+// G[j, n] = w_j gT[bins[j, n], n] (cwt_kernels_ssq_grad.hpp): the transpose of the reassignment, through the recorded bins
+template <typename T>
+int ssq_gather_impl(cwt_plan* p, const void* gT_dev, int64_t ldt, int nf, const void* bins_dev, int64_t ldb, const double* weights,
+                    int nrows, int64_t ncols, void* G_dev, int64_t ldg) {
+  int rc = upload_reals<T>(p, weights, nrows);
+  if (rc) return rc;
+  const int stretches = (nrows + SSQG_STRETCH - 1) / SSQG_STRETCH;
+  return timed_launch(p, KC_SSQ_GATHER, [&] {
+    for (int s0 = 0; s0 < stretches; s0 += kMaxGridY)          // (gridDim.y is limited to 65535: slabs of stretches of rows)
+      hipLaunchKernelGGL((ssqg_gather<T>), dim3(unsigned((ncols + SSQG_THREADS - 1) / SSQG_THREADS), unsigned(std::min(kMaxGridY, stretches - s0))),
+                         dim3(SSQG_THREADS), 0, p->stream, static_cast<const cplx<T>*>(gT_dev), long(ldt), nf,
+                         static_cast<const short*>(bins_dev), long(ldb), static_cast<const T*>(p->weights_dev), nrows, long(ncols),
+                         static_cast<cplx<T>*>(G_dev), long(ldg), s0);
   });
 }
 
@@ -1717,7 +1740,8 @@ int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g
   X int reduce_scales_impl<T, false>(cwt_plan*, const void*, int64_t, int64_t, int, const double*, double, void*);                  \
   X int spectrum_derivative_impl<T>(cwt_plan*, const void*, double, void*);                                                         \
   X int ssq_reassign_impl<T>(cwt_plan*, const void*, const void*, int64_t, int64_t, int, const double*, double, double, double,     \
-                             int, void*, int64_t, int);                                                                             \
+                             int, void*, int64_t, int, void*, int64_t);                                                             \
+  X int ssq_gather_impl<T>(cwt_plan*, const void*, int64_t, int, const void*, int64_t, const double*, int, int64_t, void*, int64_t); \
   X int random_normal_impl<T>(cwt_plan*, uint64_t, uint64_t, int64_t, double, void*);                                             \
   X int ar1_filter_impl<T>(cwt_plan*, const void*, int64_t, int64_t, double, void*);                                               \
   X int forward_fft_n_impl<T>(cwt_plan*, const void*, int64_t, void*);                                                              \

@@ -46,7 +46,7 @@ int fail(int code, const std::string& msg);
 enum KernelClass { KC_FWD_SMALL, KC_FWD_A, KC_FWD_B, KC_SMALL, KC_DIRECT, KC_NARROW, KC_NARROW_MANY, KC_NARROW_BIG,
                    KC_PASS_A, KC_PASS_B, KC_ICWT, KC_ELEMENTWISE, KC_OLS_FWD, KC_OLS, KC_OLS_SMALL, KC_AOLS_PRE, KC_AOLS,
                    KC_POLY_COEF, KC_POLY, KC_ADJOINT, KC_HOP_FOLD, KC_HOP_ROWS, KC_SGRAD, KC_POOL_POLY, KC_POOL_ROWS,
-                   KC_SSQ_DERIV, KC_SSQ_ZERO, KC_SSQ, KC_COUNT };
+                   KC_SSQ_DERIV, KC_SSQ_ZERO, KC_SSQ, KC_SSQ_GATHER, KC_COUNT };
 extern const char* const kClassNames[KC_COUNT];
 
 int ilog2(int64_t v);

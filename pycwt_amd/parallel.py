@@ -180,6 +180,17 @@ class HipEngine:
                                       xhat.shape[-1], kind, param, dt, sj, None if xbar is None else xbar.data_ptr(),
                                       n0 if xbar is None else xbar.shape[-1], sgrad.data_ptr(), accumulate)
 
+    def ssq_reassign_bins(self, W, dW, weights, gamma, f_lo, dv, T, accumulate, bins):
+        """T (+)= the reassignment of W along frequency, bins = the bin of every entry (cwt_ssq_reassign_bins): W, dW (rows, ld)
+        complex of one leading dimension, T (nf, ldt) complex, bins (rows, ldb) int16, all n0 = W.shape[-1] columns wide."""
+        self.plan.ssq_reassign_bins(W.data_ptr(), dW.data_ptr(), W.stride(0), W.shape[-1], weights, gamma, f_lo, dv, T.shape[0],
+                                    T.data_ptr(), T.stride(0), accumulate, bins.data_ptr(), bins.stride(0))
+
+    def ssq_gather(self, gT, bins, weights, G):
+        """G[j, n] = weights[j] gT[bins[j, n], n] (cwt_ssq_gather): gT (nf, ldt) complex, bins (rows, ldb) int16, G (rows, ldg)."""
+        self.plan.ssq_gather(gT.data_ptr(), gT.stride(0), gT.shape[0], bins.data_ptr(), bins.stride(0), weights, G.shape[-1],
+                             G.data_ptr(), G.stride(0))
+
     def classify(self, kind, param, dt, sj, ncols):
         return self.plan.classify(kind, param, dt, sj, ncols, True)
 
