@@ -106,12 +106,13 @@ int prepare_rows_table(cwt_plan* p, bool have_signal, int mother, double param, 
   return prepare_table(p, c);
 }
 
-// Every row of the current row table, as a call of its own; power: the rows' power instead of W (the call's only state)
+// Every row of the current row table, as a call of its own; power: the rows' power instead of W (all the call decides)
 int queue_rows(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw, int64_t ncols,
                int power = 0) {
-  CallScope scope(p);
-  p->call.power = power;
-  return scope.done(by_precision(p, [&](auto t) { return rows_impl<decltype(t)>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols); }));
+  Call call;
+  call.power = power;
+  DrainOnFailure drain(p);
+  return drain.done(by_precision(p, [&](auto t) { return rows_impl<decltype(t)>(p, call, xhat_dev, mo, nrows, W_dev, ldw, ncols); }));
 }
 
 std::mutex g_pinned_mutex;
@@ -605,7 +606,7 @@ int cwt_forward_fft(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev) 
   if (!p || !x_dev || !xhat_dev) return fail(CWT_EINVAL, "NULL argument");
   if (n0 < 1 || n0 > p->N) return fail(CWT_EINVAL, "n0 must be in [1, nfft]");
   HIPCHECK(hipSetDevice(p->device));
-  return by_precision(p, [&](auto t) { return fft_rows_impl<decltype(t), IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev); });
+  return by_precision(p, [&](auto t) { return fft_rows_impl<decltype(t), IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev, p->stream); });
 }
 
 
@@ -652,6 +653,16 @@ int cwt_adjoint_rows(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch
 // The weights of a *_weighted call: Q (reals of the plan's precision, laid out as the output G) and alpha
 struct Weights { const void* q; double alpha; };
 
+// What a transform entry point decides about its call: the output (W, its power, or W under the weights *wq) and, for a batch, the
+// elements between its signals
+static Call call_of(int power, const Weights* wq, int64_t x_ld = 0) {
+  Call call;
+  call.ols_x_ld = x_ld;
+  call.power = power;
+  if (wq) { call.weighted = 1; call.q = wq->q; call.alpha = wq->alpha; }
+  return call;
+}
+
 // Q and G of a weighted call: nbatch * nrows rows of ld elements each, neither NULL, not overlapping
 static int check_weights(const cwt_plan* p, const Weights& wq, const void* G_dev, int nbatch, int nrows, int64_t ld, int64_t ncols) {
   if (!wq.q) return fail(CWT_EINVAL, "NULL argument");
@@ -681,11 +692,10 @@ static int transform_entry(cwt_plan* p, const void* x_dev, int64_t n0, int mothe
     xhat_dev = p->hxhat;
   }
   const Mother mo = mother_of(mother, param);
-  CallScope scope(p);
-  p->call.power = power;
-  if (wq) { p->call.weighted = 1; p->call.q = wq->q; p->call.alpha = wq->alpha; }
-  return scope.done(by_precision(p, [&](auto t) {
-    return transform_impl<decltype(t)>(p, x_dev, n0, xhat_dev, mo, nrows, W_dev, ldw, ncols);
+  const Call call = call_of(power, wq);
+  DrainOnFailure drain(p);
+  return drain.done(by_precision(p, [&](auto t) {
+    return transform_impl<decltype(t)>(p, call, x_dev, n0, xhat_dev, mo, nrows, W_dev, ldw, ncols);
   }));
 }
 
@@ -746,14 +756,12 @@ static int transform_batch_entry(cwt_plan* p, const void* x_dev, int nbatch, int
   int rc = prepare_table(p, c);
   if (rc) return rc;
   const Mother mo = mother_of(mother, param);
-  CallScope scope(p);
-  rc = by_precision(p, [&](auto t) { return fft_rows_impl<decltype(t), IN_REAL>(p, x_dev, x_ld, nbatch, n0, xhat_dev); });
+  const Call call = call_of(power, wq, x_ld);
+  DrainOnFailure drain(p);
+  rc = by_precision(p, [&](auto t) { return fft_rows_impl<decltype(t), IN_REAL>(p, x_dev, x_ld, nbatch, n0, xhat_dev, p->stream); });
   if (rc) return rc;
-  p->call.ols_x_ld = x_ld;
-  p->call.power = power;
-  if (wq) { p->call.weighted = 1; p->call.q = wq->q; p->call.alpha = wq->alpha; }
-  return scope.done(by_precision(p, [&](auto t) {
-    return rows_impl<decltype(t)>(p, xhat_dev, mo, nbatch * nrows, W_dev, ldw, ncols, x_dev, n0);
+  return drain.done(by_precision(p, [&](auto t) {
+    return rows_impl<decltype(t)>(p, call, xhat_dev, mo, nbatch * nrows, W_dev, ldw, ncols, x_dev, n0);
   }));
 }
 
@@ -817,10 +825,12 @@ static int transform_hop_entry(cwt_plan* p, const void* x_dev, int nbatch, int64
   }
   if (from_signal) xhat_ld = p->N;
   const Mother mo = mother_of(mother, param);
-  CallScope scope(p);
-  return scope.done(by_precision(p, [&](auto t) {
-    return transform_hop_impl<decltype(t)>(p, from_signal ? x_dev : nullptr, nbatch, x_ld, n0, xhat_dev, xhat_ld, mo, nrows, logM, output,
-                                           out_dev, Q_dev, alpha, ld, ncols_h);
+  const Weights wq{Q_dev, alpha};
+  const Call call = call_of(output == 1, output == 2 ? &wq : nullptr);
+  DrainOnFailure drain(p);
+  return drain.done(by_precision(p, [&](auto t) {
+    return transform_hop_impl<decltype(t)>(p, call, from_signal ? x_dev : nullptr, nbatch, x_ld, n0, xhat_dev, xhat_ld, mo, nrows, logM,
+                                           out_dev, ld, ncols_h);
   }));
 }
 
@@ -879,9 +889,9 @@ int cwt_transform_pool(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld,
   }
   const Mother mo = mother_of(mother, param);
   const int logh = ilog2(pool);
-  CallScope scope(p);
+  DrainOnFailure drain(p);
   if (xhat_dev || only_ols)
-    return scope.done(by_precision(p, [&](auto t) {
+    return drain.done(by_precision(p, [&](auto t) {
       return transform_pool_impl<decltype(t)>(p, x_dev, nbatch, x_ld, n0, xhat_dev, mo, nrows, logh, P_dev, ldp);
     }));
   for (int b = 0; b < nbatch && !rc; ++b)                        // (every signal's spectrum through the same scratch, in stream order)
@@ -890,7 +900,7 @@ int cwt_transform_pool(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld,
       return transform_pool_impl<T>(p, static_cast<const T*>(x_dev) + size_t(b) * size_t(x_ld), 1, 0, n0, p->hxhat, mo, nrows, logh,
                                     static_cast<T*>(P_dev) + size_t(b) * size_t(nrows) * size_t(ldp), ldp);
     });
-  return scope.done(rc);
+  return drain.done(rc);
 }
 
 // cwt_adjoint_rows (hop = 1) or cwt_adjoint_rows_hop with the gradients with respect to the scales and f0 beside xbar: the checks of
@@ -947,8 +957,8 @@ int cwt_fft_rows(cwt_plan* p, const void* in_dev, int in_complex, int nrows, int
   HIPCHECK(hipSetDevice(p->device));
   return by_precision(p, [&](auto t) {
     using T = decltype(t);
-    return in_complex ? fft_rows_impl<T, IN_CPLX>(p, in_dev, in_ld, nrows, ncols_in, spec_dev)
-                      : fft_rows_impl<T, IN_REAL>(p, in_dev, in_ld, nrows, ncols_in, spec_dev);
+    return in_complex ? fft_rows_impl<T, IN_CPLX>(p, in_dev, in_ld, nrows, ncols_in, spec_dev, p->stream)
+                      : fft_rows_impl<T, IN_REAL>(p, in_dev, in_ld, nrows, ncols_in, spec_dev, p->stream);
   });
 }
 
@@ -992,7 +1002,7 @@ int cwt_cross_spectrum(cwt_plan* p, const void* W1_dev, const void* W2_dev, int 
     return timed_launch(p, KC_ELEMENTWISE, [&] {
       hipLaunchKernelGGL((k_cross_spectrum<T>), grid, dim3(256), 0, p->stream, static_cast<const cplx<T>*>(W1_dev),
                          static_cast<const cplx<T>*>(W2_dev), long(ld), long(ncols), static_cast<cplx<T>*>(out_dev));
-    });
+    }, p->stream);
   });
 }
 
@@ -1030,7 +1040,7 @@ int cwt_reduce_scales(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols
         hipLaunchKernelGGL((k_icwt_real<T>), dim3(unsigned((ncols + ICWT_THREADS - 1) / ICWT_THREADS)), dim3(ICWT_THREADS), 0,
                            p->stream, static_cast<const T*>(W_dev), long(ldw), long(ncols), nrows,
                            static_cast<const T*>(p->weights_dev), T(coeff), static_cast<T*>(out_dev));
-      });
+      }, p->stream);
     }
     return power ? reduce_scales_impl<T, true>(p, W_dev, ldw, ncols, nrows, weights, coeff, out_dev)
                  : reduce_scales_impl<T, false>(p, W_dev, ldw, ncols, nrows, weights, coeff, out_dev);
@@ -1058,7 +1068,7 @@ int cwt_time_mean_power(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t nco
     return timed_launch(p, KC_ICWT, [&] {
       hipLaunchKernelGGL((k_time_mean<T>), dim3(nrows), dim3(256), 256 * sizeof(double), p->stream,
                          static_cast<const cplx<T>*>(W_dev), long(ldw), long(ncols), static_cast<T*>(out_dev));
-    });
+    }, p->stream);
   });
 }
 
@@ -1071,7 +1081,7 @@ int cwt_time_mean_real(cwt_plan* p, const void* P_dev, int64_t ldp, int64_t ncol
     return timed_launch(p, KC_ICWT, [&] {
       hipLaunchKernelGGL((k_time_mean_real<T>), dim3(nrows), dim3(256), 256 * sizeof(double), p->stream,
                          static_cast<const T*>(P_dev), long(ldp), long(ncols), static_cast<T*>(out_dev));
-    });
+    }, p->stream);
   });
 }
 
@@ -1086,7 +1096,7 @@ int cwt_abs2(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols, int nro
         hipLaunchKernelGGL((k_abs2<T>), dim3(unsigned((ncols + 255) / 256), unsigned(std::min(kMaxGridY, nrows - r0))), dim3(256), 0,
                            p->stream, static_cast<const cplx<T>*>(W_dev) + size_t(r0) * size_t(ldw), long(ldw), long(ncols),
                            static_cast<T*>(P_dev) + size_t(r0) * size_t(ldp), long(ldp));
-    });
+    }, p->stream);
   });
 }
 
@@ -1193,7 +1203,7 @@ int cwt_coherence_histogram(cwt_plan* p, const void* r2_dev, int64_t ld, int nro
                            static_cast<const T*>(r2_dev) + size_t(r0) * size_t(ld), long(ld),
                            reinterpret_cast<const long*>(lo_dev) + r0, reinterpret_cast<const long*>(hi_dev) + r0, nbins,
                            reinterpret_cast<unsigned long long*>(hist_dev) + size_t(r0) * size_t(nbins));
-    });
+    }, p->stream);
   });
 }
 

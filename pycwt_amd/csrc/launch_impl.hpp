@@ -1,8 +1,10 @@
 // launch_impl.hpp -- every kernel launch of the library, as templates over the arithmetic type T (float | double): twiddle
 // tables, forward FFT, the row forms (single workgroup, band-limited, two-pass, overlap-save, band-passed, polynomial) and
 // their scheduling over the plan's streams (rows_launch), filter tables, the callers' kernels (coherence helpers, reductions,
-// Bluestein).  Included by launch_f64.hip / launch_f32.hip, which instantiate it for ONE precision each (the two halves of the
-// device code compile side by side), and by abi.hip, which only sees the declarations (extern templates at the end).
+// Bluestein).  What a call decided (output mode, pooling, batch stride: struct Call, plan.hpp) and the stream of every launch
+// that a schedule may move to a side stream arrive as arguments; nothing here writes call state or a stream into the plan.
+// Included by launch_f64.hip / launch_f32.hip, which instantiate it for ONE precision each (the two halves of the device code
+// compile side by side), and by abi.hip, which only sees the declarations (extern templates at the end).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,9 +13,19 @@
 
 namespace cwtd {
 
-// The row descriptors the launchers of the call in progress read: the current table's, or (a pooled call) its copy with out_row
-// renumbered densely over the rows that are not of polynomial form
-inline const RowDesc* call_rows(const cwt_plan* p) { return p->call.rows ? p->call.rows : p->rt->rows_dev; }
+// The row descriptors the launchers of a call read: the current table's, or (a pooled call) its copy with out_row renumbered
+// densely over the rows that are not of polynomial form
+inline const RowDesc* call_rows(const cwt_plan* p, const Call& call) { return call.rows ? call.rows : p->rt->rows_dev; }
+
+// The call's output picks the instantiation of every row kernel.  f(handle) with the output out_dev typed as what the kernels
+// write: W under the weights alpha Q (weighted_ptr<T>: G, Q at the same element offsets, alpha), the power of W as reals (T*),
+// or W (cplx<T>*).
+template <typename T, class F>
+int with_output(const Call& call, void* out_dev, F&& f) {
+  if (call.weighted) return f(weighted_ptr<T>{static_cast<cplx<T>*>(out_dev), static_cast<const T*>(call.q), T(call.alpha)});
+  if (call.power) return f(static_cast<T*>(out_dev));
+  return f(static_cast<cplx<T>*>(out_dev));
+}
 
 template <typename T>
 const cplx<T>* tw_table(const cwt_plan* p, int logL) {
@@ -30,8 +42,8 @@ TwN<T> twn_of(const cwt_plan* p) {
 }
 
 
-// Runs `launch()` (which enqueues exactly one kernel class) and, when profiling, brackets it with
-// HIP events on the plan's stream.
+// Runs `launch()` (which enqueues exactly one kernel class on `stream`) and, when profiling, brackets it with HIP events on
+// that stream.
 template <class F>
 int timed_launch(cwt_plan* p, int cls, F&& launch, hipStream_t stream) {
   if (!p->profile) {
@@ -51,10 +63,6 @@ int timed_launch(cwt_plan* p, int cls, F&& launch, hipStream_t stream) {
   HIPCHECK(hipEventRecord(t.b, stream));
   p->timed.push_back(t);
   return CWT_OK;
-}
-template <class F>
-int timed_launch(cwt_plan* p, int cls, F&& launch) {
-  return timed_launch(p, cls, launch, p->stream);
 }
 
 template <typename T>
@@ -109,22 +117,22 @@ inline void narrow_class_counts(const cwt_plan* p, int* n_small_k, int* n_big, i
 }
 
 template <typename T, typename OUT>
-void launch_narrow_ct_many(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, OUT W, int64_t ldw,
-                           int64_t ncols) {
+void launch_narrow_ct_many(cwt_plan* p, const Call& call, const cplx<T>* xhat, const Mother& mo, OUT W, int64_t ldw,
+                           int64_t ncols, hipStream_t st) {
   constexpr int LOGP = default_logp<T>();
   const int first = p->rt->narrow_groups.front().first;
   int n_small_k, n_big, n_many;
   narrow_class_counts(p, &n_small_k, &n_big, &n_many);
   for (int r0 = 0; r0 < n_many; r0 += kMaxGridY)
     hipLaunchKernelGGL((k_narrow_ct_many<T, LOGP, out_tag_t<OUT>>), dim3(1u << (p->logN - LOGP), std::min(kMaxGridY, n_many - r0)),
-                       dim3(1 << (LOGP - 4)), (size_t(1) << LOGP) * sizeof(T), p->stream, xhat,
-                       call_rows(p) + first + n_small_k + r0, mo, static_cast<const cplx<T>*>(p->tw_all),
+                       dim3(1 << (LOGP - 4)), (size_t(1) << LOGP) * sizeof(T), st, xhat,
+                       call_rows(p, call) + first + n_small_k + r0, mo, static_cast<const cplx<T>*>(p->tw_all),
                        twn_of<T>(p), p->logN, W, long(ldw), long(ncols));
 }
 
 template <typename T, typename OUT>
-void launch_narrow_ct_all(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, OUT W, int64_t ldw,
-                          int64_t ncols) {
+void launch_narrow_ct_all(cwt_plan* p, const Call& call, const cplx<T>* xhat, const Mother& mo, OUT W, int64_t ldw,
+                          int64_t ncols, hipStream_t st) {
   constexpr int LOGP = default_logp<T>();
   const int first = p->rt->narrow_groups.front().first;
   int n_small_k, n_big;
@@ -140,27 +148,27 @@ void launch_narrow_ct_all(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, OU
     n_half = std::max(n_half, n_wave);
     for (int r0 = n_wave; r0 < n_half; r0 += kMaxGridY)
       hipLaunchKernelGGL((k_narrow_ct_all<T, LOGP - 1, out_tag_t<OUT>>), dim3(1u << (p->logN - LOGP + 1), std::min(kMaxGridY, n_half - r0)),
-                         dim3(1 << (LOGP - 5)), (size_t(1) << (LOGP - 1)) * sizeof(T), p->stream, xhat,
-                         call_rows(p) + first + r0, mo, static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
+                         dim3(1 << (LOGP - 5)), (size_t(1) << (LOGP - 1)) * sizeof(T), st, xhat,
+                         call_rows(p, call) + first + r0, mo, static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
                          p->logN, W, long(ldw), long(ncols));
   }
   for (int r0 = std::max(n_half, n_wave); r0 < n_small_k; r0 += kMaxGridY)
     hipLaunchKernelGGL((k_narrow_ct_all<T, LOGP, out_tag_t<OUT>>), dim3(1u << (p->logN - LOGP), std::min(kMaxGridY, n_small_k - r0)),
-                       dim3(1 << (LOGP - 4)), (size_t(1) << LOGP) * sizeof(T), p->stream, xhat,
-                       call_rows(p) + first + r0, mo, static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
+                       dim3(1 << (LOGP - 4)), (size_t(1) << LOGP) * sizeof(T), st, xhat,
+                       call_rows(p, call) + first + r0, mo, static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
                        p->logN, W, long(ldw), long(ncols));
 }
 
 template <typename T, typename OUT>
-void launch_narrow_ct_big(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, OUT W, int64_t ldw,
-                          int64_t ncols) {
+void launch_narrow_ct_big(cwt_plan* p, const Call& call, const cplx<T>* xhat, const Mother& mo, OUT W, int64_t ldw,
+                          int64_t ncols, hipStream_t st) {
   if constexpr (sizeof(T) == 8) {
     const int first = p->rt->narrow_groups.front().first;
     int n_small_k, n_big, n_many;
     narrow_class_counts(p, &n_small_k, &n_big, &n_many);
     for (int r0 = 0; r0 < n_big; r0 += kMaxGridY)
       hipLaunchKernelGGL((k_narrow_ct_big<T, out_tag_t<OUT>>), dim3(1u << (p->logN - 14), std::min(kMaxGridY, n_big - r0)), dim3(1024),
-                         (size_t(1) << 14) * sizeof(T), p->stream, xhat, call_rows(p) + first + n_small_k + n_many + r0, mo,
+                         (size_t(1) << 14) * sizeof(T), st, xhat, call_rows(p, call) + first + n_small_k + n_many + r0, mo,
                          static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p), p->logN, W, long(ldw), long(ncols));
   }
 }
@@ -177,7 +185,7 @@ void allow_big_lds(F kernel) {
 
 template <typename T, int LOGR, int MODE>
 void launch_pass_a_ct(cwt_plan* p, const void* in, const RowDesc* rows, int cnt, const Mother& mo, long n0,
-                      long in_ld, cplx<T>* Z, hipStream_t st) {
+                      long in_ld, cplx<T>* Z, hipStream_t st, bool half_tiles) {
   constexpr int LOGP = default_logp<T>();
   if constexpr (sizeof(T) == 8 && LOGR == 12) {
     if (p->big_tiles) {
@@ -191,7 +199,7 @@ void launch_pass_a_ct(cwt_plan* p, const void* in, const RowDesc* rows, int cnt,
     }
   }
   if constexpr (MODE == IN_REAL && LOGR <= LOGP - 1 && LOGR >= 8) {
-    if (p->call.fft_small) { // the serial schedule's forward FFT beside the overlap-save rows: half-size tiles get their turn on the CUs
+    if (half_tiles) {        // the serial schedule's forward FFT beside the overlap-save rows: half-size tiles get their turn on the CUs
       constexpr int LP = LOGP - 1;
       hipLaunchKernelGGL((k_pass_a_ct<T, LOGR, LP, MODE>), dim3(1u << (p->logN - LP), cnt), dim3(1 << (LP - 4)),
                          (size_t(1) << LP) * sizeof(T), st, in, rows, mo, tw_table<T>(p, LOGR), twn_of<T>(p), p->logN, n0, in_ld, Z);
@@ -229,15 +237,16 @@ void launch_pass_a_ct_rows(cwt_plan* p, const void* in, const RowDesc* rows, int
   launch_pass_a_ct_rows_lp<T, LOGR, LOGP>(p, in, rows, cnt, mo, Z, st);
 }
 
-// Compile-time pass A for every column length R = 2^4 .. 2^12 (i.e. every N the two-pass path handles).
+// Compile-time pass A for every column length R = 2^4 .. 2^12 (i.e. every N the two-pass path handles).  half_tiles: see
+// fft_rows_impl (a forward FFT of a real signal only).
 template <typename T, int MODE>
 bool try_pass_a_ct(cwt_plan* p, int logR, const void* in, const RowDesc* rows, int cnt, const Mother& mo,
-                   long n0, long in_ld, cplx<T>* Z, hipStream_t st) {
+                   long n0, long in_ld, cplx<T>* Z, hipStream_t st, bool half_tiles = false) {
   if (!default_tile_ct(p)) return false;
 #define CWT_CASE(LR)                                                                                  \
   case LR:                                                                                            \
     if constexpr (MODE == IN_SPECTRUM) launch_pass_a_ct_rows<T, LR>(p, in, rows, cnt, mo, Z, st);    \
-    else launch_pass_a_ct<T, LR, MODE>(p, in, rows, cnt, mo, n0, in_ld, Z, st);                       \
+    else launch_pass_a_ct<T, LR, MODE>(p, in, rows, cnt, mo, n0, in_ld, Z, st, half_tiles);           \
     return true;
   switch (logR) {
     CWT_CASE(4) CWT_CASE(5) CWT_CASE(6) CWT_CASE(7) CWT_CASE(8) CWT_CASE(9) CWT_CASE(10) CWT_CASE(11) CWT_CASE(12)
@@ -257,32 +266,35 @@ void launch_pass_b_ct_lp(cwt_plan* p, const RowDesc* rows, int cnt, OUT W, int64
 
 template <typename T, int LOGK, bool CONJ, typename OUT>
 void launch_pass_b_ct(cwt_plan* p, const RowDesc* rows, int cnt, OUT W, int64_t ldw, int64_t ncols,
-                      const cplx<T>* Z, hipStream_t st) {
+                      const cplx<T>* Z, hipStream_t st, bool half_tiles) {
   constexpr int LOGP = default_logp<T>();
   if constexpr (CONJ && LOGK <= LOGP - 1) {
-    if (p->call.fft_small) return launch_pass_b_ct_lp<T, LOGK, LOGP - 1, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st);
+    if (half_tiles) return launch_pass_b_ct_lp<T, LOGK, LOGP - 1, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st);
   }
   launch_pass_b_ct_lp<T, LOGK, LOGP, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st);
 }
 
-// Compile-time pass B for row lengths K = 2^9 .. 2^12 (K = 1024 for every N from 2^14 to 2^22).
+// Compile-time pass B for row lengths K = 2^9 .. 2^12 (K = 1024 for every N from 2^14 to 2^22).  half_tiles: see fft_rows_impl
+// (the forward FFT's pass B, CONJ, only).
 template <typename T, bool CONJ, typename OUT>
 bool try_pass_b_ct(cwt_plan* p, int logK, const RowDesc* rows, int cnt, OUT W, int64_t ldw,
-                   int64_t ncols, const cplx<T>* Z, hipStream_t st) {
+                   int64_t ncols, const cplx<T>* Z, hipStream_t st, bool half_tiles = false) {
   if (!default_tile_ct(p)) return false;
   switch (logK) {
-    case 9: launch_pass_b_ct<T, 9, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st); return true;
-    case 10: launch_pass_b_ct<T, 10, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st); return true;
-    case 11: launch_pass_b_ct<T, 11, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st); return true;
-    case 12: launch_pass_b_ct<T, 12, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st); return true;
+    case 9: launch_pass_b_ct<T, 9, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st, half_tiles); return true;
+    case 10: launch_pass_b_ct<T, 10, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st, half_tiles); return true;
+    case 11: launch_pass_b_ct<T, 11, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st, half_tiles); return true;
+    case 12: launch_pass_b_ct<T, 12, CONJ>(p, rows, cnt, W, ldw, ncols, Z, st, half_tiles); return true;
     default: return false;
   }
 }
 
 // Forward FFT of nrows rows (real, or complex for MODE = IN_CPLX), each zero padded from n0 to N:
-// out[r, k] = sum_n in[r, n] e^{-2 pi i k n / N}, computed as conj(inverse(conj(in))).
+// out[r, k] = sum_n in[r, n] e^{-2 pi i k n / N}, computed as conj(inverse(conj(in))), on stream st.  half_tiles: the two-pass
+// kernels of a real signal's transform on half-size workgroup tiles where the geometry has them.
 template <typename T, int MODE>
-int fft_rows_impl(cwt_plan* p, const void* in_dev, int64_t in_ld, int nrows, int64_t n0, void* out_dev) {
+int fft_rows_impl(cwt_plan* p, const void* in_dev, int64_t in_ld, int nrows, int64_t n0, void* out_dev, hipStream_t st,
+                  bool half_tiles = false) {
   const int logN = p->logN;
   if (int rc = check_geometry(p)) return rc;
   const Mother mo{MOTHER_MORLET, 0, 0.0, nullptr};
@@ -290,10 +302,10 @@ int fft_rows_impl(cwt_plan* p, const void* in_dev, int64_t in_ld, int nrows, int
   if (logN <= 3) {
     const int total = nrows << logN;
     return timed_launch(p, KC_FWD_SMALL, [&] {
-      hipLaunchKernelGGL((k_direct<T, MODE>), dim3((total + 63) / 64), dim3(64), 0, p->stream, in_dev,
+      hipLaunchKernelGGL((k_direct<T, MODE>), dim3((total + 63) / 64), dim3(64), 0, st, in_dev,
                          (const RowDesc*)nullptr, nrows, mo, logN, long(n0), long(in_ld), out, long(p->N),
                          long(p->N));
-    });
+    }, st);
   }
   if (logN <= p->loglmax) {
     const int logTB = nrows > 1 ? std::max(0, std::min(12, p->log_wg_points) - logN) : 0;
@@ -301,10 +313,10 @@ int fft_rows_impl(cwt_plan* p, const void* in_dev, int64_t in_ld, int nrows, int
     const int threads = TB << (logN - 4);
     const size_t lds = (size_t(TB) << logN) * sizeof(T);
     return timed_launch(p, KC_FWD_SMALL, [&] {
-      hipLaunchKernelGGL((k_small<T, MODE>), dim3((nrows + TB - 1) / TB), dim3(threads), lds, p->stream,
+      hipLaunchKernelGGL((k_small<T, MODE>), dim3((nrows + TB - 1) / TB), dim3(threads), lds, st,
                          in_dev, (const RowDesc*)nullptr, nrows, mo, tw_table<T>(p, logN), logN, logTB,
                          long(n0), long(in_ld), out, long(p->N), long(p->N));
-    });
+    }, st);
   }
   const int logK = two_pass_logk(p), logR = logN - logK;
   const int logP = std::min(p->log_wg_points, logN);
@@ -320,19 +332,19 @@ int fft_rows_impl(cwt_plan* p, const void* in_dev, int64_t in_ld, int nrows, int
     cplx<T>* o = out + size_t(first) * size_t(p->N);
     rc = timed_launch(p, KC_FWD_A, [&] {
       if (try_pass_a_ct<T, MODE>(p, logR, in, nullptr, cnt, mo, long(n0), long(in_ld),
-                                 static_cast<cplx<T>*>(p->Z), p->stream)) return;
-      hipLaunchKernelGGL((k_pass_a<T, MODE>), dim3(1u << (logN - logP), cnt), dim3(threads), lds, p->stream,
+                                 static_cast<cplx<T>*>(p->Z), st, half_tiles)) return;
+      hipLaunchKernelGGL((k_pass_a<T, MODE>), dim3(1u << (logN - logP), cnt), dim3(threads), lds, st,
                          in, (const RowDesc*)nullptr, mo, tw_table<T>(p, logR), twn_of<T>(p), logN, logK,
                          logP - logR, long(n0), long(in_ld), static_cast<cplx<T>*>(p->Z));
-    });
+    }, st);
     if (rc) return rc;
     rc = timed_launch(p, KC_FWD_B, [&] {
-      if (try_pass_b_ct<T, true>(p, logK, nullptr, cnt, o, p->N, p->N, static_cast<const cplx<T>*>(p->Z),
-                                 p->stream)) return;
-      hipLaunchKernelGGL((k_pass_b<T, true>), dim3(1u << (logN - logP), cnt), dim3(threads), lds, p->stream,
+      if (try_pass_b_ct<T, true>(p, logK, nullptr, cnt, o, p->N, p->N, static_cast<const cplx<T>*>(p->Z), st,
+                                 half_tiles)) return;
+      hipLaunchKernelGGL((k_pass_b<T, true>), dim3(1u << (logN - logP), cnt), dim3(threads), lds, st,
                          static_cast<const cplx<T>*>(p->Z), (const RowDesc*)nullptr, tw_table<T>(p, logK),
                          twn_of<T>(p), logN, logK, logP - logK, o, long(p->N), long(p->N));
-    });
+    }, st);
     if (rc) return rc;
   }
   return CWT_OK;
@@ -341,7 +353,7 @@ int fft_rows_impl(cwt_plan* p, const void* in_dev, int64_t in_ld, int nrows, int
 // Overlap-save rows of the current row table: block spectra of the real signal x_dev (k_ols_fwd_r; block length
 // 2^(LOGM + 1)) ...
 template <typename T, int LOGM>
-int launch_ols_fwd_r(cwt_plan* p, const void* x_dev, int64_t n0, long blocks, const OlsClasses& cls, hipStream_t st) {
+int launch_ols_fwd_r(cwt_plan* p, const Call& call, const void* x_dev, int64_t n0, long blocks, const OlsClasses& cls, hipStream_t st) {
   static const bool once = (allow_big_lds(&k_ols_fwd_r<T, LOGM>), true);
   (void)once;
   const size_t lds = ((size_t(1) << LOGM) + (size_t(1) << (LOGM - 4))) * sizeof(T);
@@ -349,12 +361,12 @@ int launch_ols_fwd_r(cwt_plan* p, const void* x_dev, int64_t n0, long blocks, co
     hipLaunchKernelGGL((k_ols_fwd_r<T, LOGM>), dim3(unsigned(blocks), unsigned(p->rt->ols_nbatch)), dim3(1 << (LOGM - 4)),
                        lds, st, static_cast<const T*>(x_dev), long(n0), p->logN, cls,
                        static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p), static_cast<cplx<T>*>(p->xs),
-                       long(p->call.ols_x_ld), p->rt->ols_xs_sig);
+                       long(call.ols_x_ld), p->rt->ols_xs_sig);
   }, st);
 }
 // (g_only / d_only >= 0: only that tile group / only its blocks of 2^d tiles)
 template <typename T>
-int launch_ols_fwd(cwt_plan* p, const void* x_dev, int64_t n0, hipStream_t st, int g_only = -1, int d_only = -1) {
+int launch_ols_fwd(cwt_plan* p, const Call& call, const void* x_dev, int64_t n0, hipStream_t st, int g_only = -1, int d_only = -1) {
   int rc = CWT_OK;
   for (int g = 0; g < 2 && !rc; ++g) {
     const auto& G = p->rt->ols_grp[g];
@@ -362,9 +374,9 @@ int launch_ols_fwd(cwt_plan* p, const void* x_dev, int64_t n0, hipStream_t st, i
     for (int d = 0; d < 2 && !rc; ++d) {
       if (!G.fwd_blocks[d] || (d_only >= 0 && d != d_only)) continue;
       switch (G.logp + d) {                                   // log2 of the block length
-        case 12: rc = launch_ols_fwd_r<T, 11>(p, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
-        case 13: rc = launch_ols_fwd_r<T, 12>(p, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
-        case 14: rc = launch_ols_fwd_r<T, 13>(p, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
+        case 12: rc = launch_ols_fwd_r<T, 11>(p, call, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
+        case 13: rc = launch_ols_fwd_r<T, 12>(p, call, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
+        case 14: rc = launch_ols_fwd_r<T, 13>(p, call, x_dev, n0, G.fwd_blocks[d], G.cls, st); break;
         default: return fail(CWT_EINVAL, "overlap-save block length");
       }
     }
@@ -374,7 +386,7 @@ int launch_ols_fwd(cwt_plan* p, const void* x_dev, int64_t n0, hipStream_t st, i
 // ... and the rows themselves (k_ols_ct)
 // part: -1 = every class of the group in one launch, 0 = the classes on blocks of one tile, 1 = the classes on longer blocks
 template <typename T, int LOGP, typename OUT>
-int launch_ols_rows_p(cwt_plan* p, int g, OUT W, int64_t ldw, int64_t ncols, hipStream_t st, int part = -1) {
+int launch_ols_rows_p(cwt_plan* p, const Call& call, int g, OUT W, int64_t ldw, int64_t ncols, hipStream_t st, int part = -1) {
   const cwt_plan::RowTable* rt = p->rt;
   const auto& G = rt->ols_grp[g];
   const long first = part == 1 ? G.wgs_base : 0, count = part == 0 ? G.wgs_base : G.wgs - first;
@@ -385,21 +397,21 @@ int launch_ols_rows_p(cwt_plan* p, int g, OUT W, int64_t ldw, int64_t ncols, hip
   const size_t lds = ((size_t(1) << LOGP) + (size_t(1) << (LOGP - 4))) * (ols_pairs(sizeof(T), LOGP) ? sizeof(pairf) : sizeof(T));
   return timed_launch(p, g == 0 ? KC_OLS_SMALL : KC_OLS, [&] {
     hipLaunchKernelGGL((k_ols_ct<T, LOGP, out_tag_t<OUT>>), dim3(unsigned(count)), dim3(1 << (LOGP - 4)), lds, st,
-                       static_cast<const cplx<T>*>(p->xs), call_rows(p) + rt->ols_first + G.row_first,
+                       static_cast<const cplx<T>*>(p->xs), call_rows(p, call) + rt->ols_first + G.row_first,
                        static_cast<const cplx<T>*>(rt->gt_dev), static_cast<const cplx<T>*>(p->tw_all), twn_of<T>(p),
                        p->logN, G.cls, W, long(ldw), long(ncols), unsigned(first));
   }, st);
 }
 template <typename T, typename OUT>
-int launch_ols_rows(cwt_plan* p, OUT W, int64_t ldw, int64_t ncols, hipStream_t st, int g_only = -1, int part = -1) {
+int launch_ols_rows(cwt_plan* p, const Call& call, OUT W, int64_t ldw, int64_t ncols, hipStream_t st, int g_only = -1, int part = -1) {
   int rc = CWT_OK;
   for (int g = 0; g < 2 && !rc; ++g) {        // the half-size tiles first (by far the longer launch since the rows with long
                                               // halos went to the polynomial form), then the default tile's rows
     const auto& G = p->rt->ols_grp[g];
     if (!G.nrows || (g_only >= 0 && g != g_only)) continue;
     switch (G.logp) {
-      case 12: rc = launch_ols_rows_p<T, 12>(p, g, W, ldw, ncols, st, part); break;
-      case 13: rc = launch_ols_rows_p<T, 13>(p, g, W, ldw, ncols, st, part); break;
+      case 12: rc = launch_ols_rows_p<T, 12>(p, call, g, W, ldw, ncols, st, part); break;
+      case 13: rc = launch_ols_rows_p<T, 13>(p, call, g, W, ldw, ncols, st, part); break;
       default: return fail(CWT_EINVAL, "overlap-save tile size");
     }
   }
@@ -411,7 +423,7 @@ int launch_ols_rows(cwt_plan* p, OUT W, int64_t ldw, int64_t ncols, hipStream_t 
 // phase: 0 = everything on st; the serial schedule (one signal) splits it in two: 1 = the band-passed signal and its block
 // spectra on st, `ready` recorded behind them, 2 = the rows on st, which the caller has made wait for `ready`
 template <typename T, int LOGP, typename OUT>
-int launch_aols_p(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, int64_t ncols, hipStream_t st, int phase = 0,
+int launch_aols_p(cwt_plan* p, const Call& call, const void* xhat_dev, OUT W, int64_t ldw, int64_t ncols, hipStream_t st, int phase = 0,
                   hipEvent_t ready = nullptr) {
   const cwt_plan::RowTable* rt = p->rt;
   const AolsGeom& g = rt->aols_geom;
@@ -437,7 +449,7 @@ int launch_aols_p(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, int64_t
     const int cnt = std::min(chunk, nb - b0);
     bool ok = true;
     if (phase != 2) rc = timed_launch(p, KC_AOLS_PRE, [&] {
-      ok = try_pass_a_ct<T, IN_SPECTRUM>(p, logR, xhat_dev, call_rows(p) + rt->aux_first + b0, cnt, one, 0L, 0L, Z, st);
+      ok = try_pass_a_ct<T, IN_SPECTRUM>(p, logR, xhat_dev, call_rows(p, call) + rt->aux_first + b0, cnt, one, 0L, 0L, Z, st);
     }, st);
     if (!rc && !ok) rc = fail(CWT_EINVAL, "k_aols rows need the default geometry");
     if (!rc && phase != 2) rc = timed_launch(p, KC_AOLS_PRE, [&] {
@@ -457,7 +469,7 @@ int launch_aols_p(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, int64_t
     }
     if (!rc) rc = timed_launch(p, KC_AOLS, [&] {
       hipLaunchKernelGGL((k_aols_rows<T, LOGP, out_tag_t<OUT>>), dim3(unsigned(rt->aols_wgs), unsigned(cnt)), dim3(1 << (LOGP - 4)), lds_rows, st,
-                         static_cast<const cplx<T>*>(p->xsa), call_rows(p) + rt->aols_first + long(b0) * g.nrows,
+                         static_cast<const cplx<T>*>(p->xsa), call_rows(p, call) + rt->aols_first + long(b0) * g.nrows,
                          static_cast<const T*>(rt->agt_dev), static_cast<const cplx<T>*>(p->tw_all), g,
                          static_cast<const cplx<T>*>(xhat_dev), long(p->N >> 1), W, long(ldw), long(ncols));
     }, st);
@@ -468,7 +480,7 @@ int launch_aols_p(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, int64_t
 // The second class of such rows (Paul continued through f = 0, 8192-point tiles; one signal): block spectra of the SAME
 // band-passed signal on its own block grid, then its rows -- on the stream of the first class, behind it (both use p->xsa).
 template <typename T, typename OUT>
-int launch_aols_second(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, int64_t ncols, hipStream_t st) {
+int launch_aols_second(cwt_plan* p, const Call& call, const void* xhat_dev, OUT W, int64_t ldw, int64_t ncols, hipStream_t st) {
   const cwt_plan::RowTable* rt = p->rt;
   const AolsGeom& g = rt->aols2_geom;
   constexpr int LOGP = 13, P = 1 << LOGP;
@@ -485,21 +497,21 @@ int launch_aols_second(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, in
   if (!rc) rc = timed_launch(p, KC_AOLS, [&] {
     hipLaunchKernelGGL((k_aols_rows<T, LOGP, out_tag_t<OUT>>), dim3(unsigned(rt->aols2_wgs), 1u), dim3(1 << (LOGP - 4)),
                        aols_pairs(sizeof(T)) ? 2 * lds : lds, st,
-                       static_cast<const cplx<T>*>(p->xsa), call_rows(p) + rt->aols2_first, static_cast<const T*>(rt->agt_dev),
+                       static_cast<const cplx<T>*>(p->xsa), call_rows(p, call) + rt->aols2_first, static_cast<const T*>(rt->agt_dev),
                        static_cast<const cplx<T>*>(p->tw_all), g, static_cast<const cplx<T>*>(xhat_dev), long(p->N >> 1), W,
                        long(ldw), long(ncols));
   }, st);
   return rc;
 }
 template <typename T, typename OUT>
-int launch_aols(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, int64_t ncols, hipStream_t st, int phase = 0,
+int launch_aols(cwt_plan* p, const Call& call, const void* xhat_dev, OUT W, int64_t ldw, int64_t ncols, hipStream_t st, int phase = 0,
                 hipEvent_t ready = nullptr) {
   int rc = CWT_OK;
   switch (p->rt->aols_logp) {
-    case 12: rc = launch_aols_p<T, 12>(p, xhat_dev, W, ldw, ncols, st, phase, ready); break;
+    case 12: rc = launch_aols_p<T, 12>(p, call, xhat_dev, W, ldw, ncols, st, phase, ready); break;
     default: return fail(CWT_EINVAL, "k_aols tile size");
   }
-  if (!rc && p->rt->n_aols2 && phase != 1) rc = launch_aols_second<T>(p, xhat_dev, W, ldw, ncols, st);
+  if (!rc && p->rt->n_aols2 && phase != 1) rc = launch_aols_second<T>(p, call, xhat_dev, W, ldw, ncols, st);
   return rc;
 }
 
@@ -507,7 +519,7 @@ int launch_aols(cwt_plan* p, const void* xhat_dev, OUT W, int64_t ldw, int64_t n
 // st2 != nullptr: the 8192- and 4096-point tiles on that second stream beside the 16384-point ones (three independent,
 // latency-bound launches of one round of workgroups each: 30 + 19 + 20 us back to back), joined into st again.
 template <typename T>
-int launch_poly_coef(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, int chunk, hipStream_t st, hipStream_t st2 = nullptr) {
+int launch_poly_coef(cwt_plan* p, const Call& call, const cplx<T>* xhat, const Mother& mo, int chunk, hipStream_t st, hipStream_t st2 = nullptr) {
   const cwt_plan::RowTable* rt = p->rt;
   const auto& ch = rt->poly_chunks[size_t(chunk)];
   int rc = grow(&p->pcoef, &p->pcoef_bytes, size_t(rt->poly_coef_elems) * sizeof(cplx<T>), st);
@@ -515,7 +527,7 @@ int launch_poly_coef(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, int chu
   if (rc) return rc;
   static const bool once = (allow_big_lds(&k_poly_coef<T, 13>), allow_big_lds(&k_poly_coef<T, 14>), true);
   (void)once;
-  const RowDesc* rows = call_rows(p) + rt->poly_first + ch.row_first;
+  const RowDesc* rows = call_rows(p, call) + rt->poly_first + ch.row_first;
   cplx<T>* coef = static_cast<cplx<T>*>(p->pcoef);
   cplx<T>* band = static_cast<cplx<T>*>(p->pband);
   rc = timed_launch(p, KC_POLY_COEF, [&] {
@@ -553,10 +565,10 @@ int launch_poly_coef(cwt_plan* p, const cplx<T>* xhat, const Mother& mo, int chu
 }
 // ... then the streaming kernel (k_poly_rows) over the rows of the chunk
 template <typename T, typename OUT>
-int launch_poly_rows(cwt_plan* p, int chunk, OUT W, int64_t ldw, int64_t ncols, hipStream_t st) {
+int launch_poly_rows(cwt_plan* p, const Call& call, int chunk, OUT W, int64_t ldw, int64_t ncols, hipStream_t st) {
   const cwt_plan::RowTable* rt = p->rt;
   const auto& ch = rt->poly_chunks[size_t(chunk)];
-  const RowDesc* rows = call_rows(p) + rt->poly_first + ch.row_first;
+  const RowDesc* rows = call_rows(p, call) + rt->poly_first + ch.row_first;
   const cplx<T>* coef = static_cast<const cplx<T>*>(p->pcoef);
   const int64_t per_wg = 256 * (sizeof(T) == 8 ? 1 : 2) * POLY_PASSES;
   // LDS: the coefficient sets of the intervals one workgroup touches (shortest interval 2^POLY_MIN_LOGR samples)
@@ -569,31 +581,31 @@ int launch_poly_rows(cwt_plan* p, int chunk, OUT W, int64_t ldw, int64_t ncols, 
   }, st);
 }
 
-// ... or, in a pooled call (p->call.pool = log2 h), pool_poly_rows: the same evaluation summed over the windows, straight into the
+// ... or, in a pooled call (call.pool = log2 h), pool_poly_rows: the same evaluation summed over the windows, straight into the
 // caller's Pbar; n0 = the columns of W
 template <typename T>
-int launch_pool_poly_rows(cwt_plan* p, int chunk, int64_t n0, hipStream_t st) {
+int launch_pool_poly_rows(cwt_plan* p, const Call& call, int chunk, int64_t n0, hipStream_t st) {
   const cwt_plan::RowTable* rt = p->rt;
   const auto& ch = rt->poly_chunks[size_t(chunk)];
-  const RowDesc* rows = call_rows(p) + rt->poly_first + ch.row_first;
-  const int logh = p->call.pool;
+  const RowDesc* rows = call_rows(p, call) + rt->poly_first + ch.row_first;
+  const int logh = call.pool;
   const int64_t span = int64_t(1) << std::max(logh, POOL_LOG_SPAN);    // a workgroup: 4096 columns, or one longer window
   return timed_launch(p, KC_POOL_POLY, [&] {
     for (int r0 = 0; r0 < ch.nrows; r0 += kMaxGridY)
       hipLaunchKernelGGL((pool_poly_rows<T>), dim3(unsigned((n0 + span - 1) / span), std::min(kMaxGridY, ch.nrows - r0)), dim3(POOL_THREADS),
                          POOL_THREADS * sizeof(T), st, rows + r0, static_cast<const cplx<T>*>(p->pcoef), p->logN, logh,
-                         static_cast<T*>(p->call.pool_out), long(p->call.pool_ld), long(n0));
+                         static_cast<T*>(call.pool_out), long(call.pool_ld), long(n0));
   }, st);
 }
 template <typename T, typename OUT>
-int launch_poly_rows_of_call(cwt_plan* p, int chunk, OUT W, int64_t ldw, int64_t ncols, hipStream_t st) {
-  if (p->call.pool) return launch_pool_poly_rows<T>(p, chunk, ncols, st);
-  return launch_poly_rows<T>(p, chunk, W, ldw, ncols, st);
+int launch_poly_rows_of_call(cwt_plan* p, const Call& call, int chunk, OUT W, int64_t ldw, int64_t ncols, hipStream_t st) {
+  if (call.pool) return launch_pool_poly_rows<T>(p, call, chunk, ncols, st);
+  return launch_poly_rows<T>(p, call, chunk, W, ldw, ncols, st);
 }
 
-// Two-pass rows (forms T), chunk by chunk on the plan's stream through the one intermediate buffer.
+// Two-pass rows (forms T), chunk by chunk on the caller's stream through the one intermediate buffer.
 template <typename T, typename OUT>
-int launch_wide_rows(cwt_plan* p, const void* xhat_dev, const Mother& mo, OUT W, int64_t ldw, int64_t ncols) {
+int launch_wide_rows(cwt_plan* p, const Call& call, const void* xhat_dev, const Mother& mo, OUT W, int64_t ldw, int64_t ncols) {
   const int logN = p->logN, logP = std::min(p->log_wg_points, logN), threads = 1 << (logP - 4);
   const size_t lds = (size_t(1) << logP) * sizeof(T);
   const int logK = two_pass_logk(p), logR = logN - logK;
@@ -604,51 +616,39 @@ int launch_wide_rows(cwt_plan* p, const void* xhat_dev, const Mother& mo, OUT W,
   cplx<T>* Z = static_cast<cplx<T>*>(p->Z);
   for (int c = 0; c < nchunks; ++c) {
     const int first = c * chunk, cnt = std::min(chunk, p->rt->n_wide - first);
-    const RowDesc* rows = call_rows(p) + p->rt->wide_first + first;
+    const RowDesc* rows = call_rows(p, call) + p->rt->wide_first + first;
     rc = timed_launch(p, KC_PASS_A, [&] {
       if (try_pass_a_ct<T, IN_SPECTRUM>(p, logR, xhat_dev, rows, cnt, mo, 0L, 0L, Z, p->stream)) return;
       hipLaunchKernelGGL((k_pass_a<T, IN_SPECTRUM>), dim3(1u << (logN - logP), cnt), dim3(threads), lds, p->stream,
                          xhat_dev, rows, mo, tw_table<T>(p, logR), twn_of<T>(p), logN, logK, logP - logR, 0L, 0L, Z);
-    });
+    }, p->stream);
     if (rc) return rc;
     rc = timed_launch(p, KC_PASS_B, [&] {
       if (try_pass_b_ct<T, false>(p, logK, rows, cnt, W, ldw, ncols, Z, p->stream)) return;
       hipLaunchKernelGGL((k_pass_b<T, false, out_tag_t<OUT>>), dim3(1u << (logN - logP), cnt), dim3(threads), lds, p->stream,
                          static_cast<const cplx<T>*>(Z), rows, tw_table<T>(p, logK), twn_of<T>(p), logN, logK,
                          logP - logK, W, long(ldw), long(ncols));
-    });
+    }, p->stream);
     if (rc) return rc;
   }
   return CWT_OK;
 }
 
-// Restores the plan's stream when a scope that redirected launches to a side stream is left on any path.
-struct StreamGuard {
-  cwt_plan* p;
-  hipStream_t keep;
-  explicit StreamGuard(cwt_plan* plan) : p(plan), keep(plan->stream) {}
-  ~StreamGuard() { p->stream = keep; }
-};
-
 // One call that queues rows (cwt_transform, cwt_transform_batch and every other way into rows_impl).  When it is left, on
-// any path, the per-call state p->call is cleared and the plan's stream restored; unless the call reported success through
-// done(), the side streams are drained first, so that no kernel forked to them still reads the row table, the block spectra
-// or the filter tables when the caller (or the next call) frees or rebuilds them.
-struct CallScope {
+// any path, without having reported success through done(), the side streams are drained, so that no kernel forked to them
+// still reads the row table, the block spectra or the filter tables when the caller (or the next call) frees or rebuilds them.
+// Nothing else is undone: a call leaves no state on the plan.
+struct DrainOnFailure {
   cwt_plan* p;
-  hipStream_t keep;
   bool ok = false;
-  explicit CallScope(cwt_plan* plan) : p(plan), keep(plan->stream) {}
+  explicit DrainOnFailure(cwt_plan* plan) : p(plan) {}
   int done(int rc) { ok = rc == CWT_OK; return rc; }
-  ~CallScope() {
-    if (!ok) {
-      const std::string msg = g_err;                       // the drain below must not overwrite the message
-      for (hipStream_t s : {p->side[0], p->side[1], p->side2}) if (s) (void)hipStreamSynchronize(s);
-      (void)hipGetLastError();
-      g_err = msg;
-    }
-    p->call = {};
-    p->stream = keep;
+  ~DrainOnFailure() {
+    if (ok) return;
+    const std::string msg = g_err;                         // the drain must not overwrite the message
+    for (hipStream_t s : {p->side[0], p->side[1], p->side2}) if (s) (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+    g_err = msg;
   }
 };
 
@@ -659,30 +659,31 @@ struct CallScope {
 // queues it:
 //   1. launch_ols_early: the block spectra of the half-size tiles' one-tile blocks on the caller's stream (their rows follow at
 //      a kernel boundary), the rest on side stream 1;
-//   2. transform_serial: the forward FFT on side stream 0, on half-size tiles;
+//   2. transform_serial: the forward FFT on side stream 0, on half-size tiles (fft_rows_impl's st and half_tiles, for this one launch);
 //   3. rows_launch_serial: bands + interval coefficients on side stream 0 (+ side2) behind the FFT; the band-passed signal and
 //      its block spectra on side stream 1 behind the block spectra; the rows on the caller's stream.
 // Why: heavy kernels side by side cost more than one after the other (EXPERIMENTS R5.2), a stream-to-stream hand-over costs
 // 15-20 us where the waiting stream is idle -- so the hand-overs sit where the event completed long before the wait is reached,
 // and the step ends on the caller's stream (the next call, or whatever the caller queues, follows at a kernel boundary instead
 // of a join).  The other entry points have the spectrum on the caller's stream already and no early block spectra: they take
-// step 3 alone, for tables without overlap-save rows (serial_schedule).
+// step 3 alone, for tables without overlap-save rows (serial_schedule).  Every launcher is told its stream; the plan's own
+// (the caller's) is never redirected.
 
 // Block spectra of the overlap-save rows, queued by cwt_transform before the forward FFT (option "ols_early"): they need the
 // signal only.  first_on_main (serial schedule): those of the half-size tiles' one-tile blocks on the caller's stream; the
 // rest, or all, on side stream 1, with ev_ols recorded behind them.
 template <typename T>
-int launch_ols_early(cwt_plan* p, const void* x_dev, int64_t n0, bool first_on_main) {
+int launch_ols_early(cwt_plan* p, const Call& call, const void* x_dev, int64_t n0, bool first_on_main) {
   int rc = grow(&p->xs, &p->xs_bytes, size_t(p->rt->ols_xs_elems) * sizeof(cplx<T>), p->stream);
   if (rc) return rc;
   HIPCHECK(hipEventRecord(p->ev_fork, p->stream));        // after the previous call's work and the row-table upload
   HIPCHECK(hipStreamWaitEvent(p->side[1], p->ev_fork, 0));
   if (first_on_main) {
-    rc = launch_ols_fwd<T>(p, x_dev, n0, p->stream, 0, 0);
-    if (!rc) rc = launch_ols_fwd<T>(p, x_dev, n0, p->side[1], 0, 1);    // (the half-size tiles' longer blocks)
-    if (!rc) rc = launch_ols_fwd<T>(p, x_dev, n0, p->side[1], 1);
+    rc = launch_ols_fwd<T>(p, call, x_dev, n0, p->stream, 0, 0);
+    if (!rc) rc = launch_ols_fwd<T>(p, call, x_dev, n0, p->side[1], 0, 1);    // (the half-size tiles' longer blocks)
+    if (!rc) rc = launch_ols_fwd<T>(p, call, x_dev, n0, p->side[1], 1);
   } else {
-    rc = launch_ols_fwd<T>(p, x_dev, n0, p->side[1]);
+    rc = launch_ols_fwd<T>(p, call, x_dev, n0, p->side[1]);
   }
   if (rc) return rc;
   HIPCHECK(hipEventRecord(p->ev_ols, p->side[1]));      // (the round-5 schedule records it again behind the rows there)
@@ -691,8 +692,8 @@ int launch_ols_early(cwt_plan* p, const void* x_dev, int64_t n0, bool first_on_m
 
 // Step 3.  spectrum_ready: recorded behind a forward FFT on side stream 0; nullptr: the spectrum is on the caller's stream.
 template <typename T, typename OUT>
-int rows_launch_serial_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, OUT W, int64_t ldw, int64_t ncols,
-                           hipEvent_t spectrum_ready) {
+int rows_launch_serial_out(cwt_plan* p, const Call& call, const void* xhat_dev, const Mother& mo, OUT W, int64_t ldw,
+                           int64_t ncols, hipEvent_t spectrum_ready) {
   const cwt_plan::RowTable* rt = p->rt;
   const cplx<T>* xhat = static_cast<const cplx<T>*>(xhat_dev);
   hipStream_t M = p->stream, S0 = p->side[0], S1 = p->side[1];
@@ -707,7 +708,7 @@ int rows_launch_serial_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, 
   }
   if (rt->n_poly) {
     HIPCHECK(hipStreamWaitEvent(S0, spectrum_ready, 0));
-    rc = launch_poly_coef<T>(p, xhat, mo, 0, S0, p->side2);
+    rc = launch_poly_coef<T>(p, call, xhat, mo, 0, S0, p->side2);
     if (rc) return rc;
     HIPCHECK(hipEventRecord(p->ev_a[0], S0));
   }
@@ -716,25 +717,25 @@ int rows_launch_serial_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, 
   // long done then: 130 of 250 us), instead of once per consumer: a wait costs the stream 7-8 us, a kernel boundary 2 [measured]
   if (rt->n_aols) {
     HIPCHECK(hipStreamWaitEvent(S1, spectrum_ready, 0));   // (the band-passed signal is made from the spectrum)
-    rc = launch_aols<T>(p, xhat_dev, W, ldw, ncols, S1, 1, p->ev_b[1]);
+    rc = launch_aols<T>(p, call, xhat_dev, W, ldw, ncols, S1, 1, p->ev_b[1]);
     if (rc) return rc;
   }
   // the rows of the half-size tiles' one-tile blocks first, behind their block spectra on this stream; those of the longer blocks
   // (block spectra on side stream 1) in a second launch
   const bool g0_split = rt->ols_grp[0].wgs > rt->ols_grp[0].wgs_base;
   if (rt->ols_grp[0].nrows) {
-    rc = launch_ols_rows<T>(p, W, ldw, ncols, M, 0, g0_split ? 0 : -1);
+    rc = launch_ols_rows<T>(p, call, W, ldw, ncols, M, 0, g0_split ? 0 : -1);
     if (rc) return rc;
   }
   if (rt->n_aols) HIPCHECK(hipStreamWaitEvent(M, p->ev_b[1], 0));
   if (rt->n_ols && (rt->ols_grp[1].nrows || g0_split)) {
     if (!rt->n_aols) HIPCHECK(hipStreamWaitEvent(M, p->ev_ols, 0));
-    if (g0_split) rc = launch_ols_rows<T>(p, W, ldw, ncols, M, 0, 1);
-    if (!rc && rt->ols_grp[1].nrows) rc = launch_ols_rows<T>(p, W, ldw, ncols, M, 1);
+    if (g0_split) rc = launch_ols_rows<T>(p, call, W, ldw, ncols, M, 0, 1);
+    if (!rc && rt->ols_grp[1].nrows) rc = launch_ols_rows<T>(p, call, W, ldw, ncols, M, 1);
     if (rc) return rc;
   }
   if (rt->n_aols) {
-    rc = launch_aols<T>(p, xhat_dev, W, ldw, ncols, M, 2);
+    rc = launch_aols<T>(p, call, xhat_dev, W, ldw, ncols, M, 2);
     if (rc) return rc;
   }
   // The polynomial rows BEFORE the two-pass rows: k_poly_rows starts every workgroup with a fetch of its coefficient sets and runs
@@ -744,40 +745,32 @@ int rows_launch_serial_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, 
     HIPCHECK(hipStreamWaitEvent(M, p->ev_a[0], 0));
     const int nchunks = int(rt->poly_chunks.size());
     for (int c = 0; c < nchunks && !rc; ++c) {            // chunk c's rows, then chunk c + 1's coefficients
-      rc = launch_poly_rows_of_call<T>(p, c, W, ldw, ncols, M);
-      if (!rc && c + 1 < nchunks) rc = launch_poly_coef<T>(p, xhat, mo, c + 1, M, nullptr);
+      rc = launch_poly_rows_of_call<T>(p, call, c, W, ldw, ncols, M);
+      if (!rc && c + 1 < nchunks) rc = launch_poly_coef<T>(p, call, xhat, mo, c + 1, M, nullptr);
     }
     if (rc) return rc;
   }
   if (rt->n_wide) {
     HIPCHECK(hipStreamWaitEvent(M, spectrum_ready, 0));
-    rc = launch_wide_rows<T>(p, xhat_dev, mo, W, ldw, ncols);
+    rc = launch_wide_rows<T>(p, call, xhat_dev, mo, W, ldw, ncols);
   }
   return rc;
 }
 
-// The output handle of a weighted call (p->call.weighted): G, the weights Q at the same element offsets, and alpha
 template <typename T>
-weighted_ptr<T> weighted_handle(const cwt_plan* p, void* G_dev) {
-  return weighted_ptr<T>{static_cast<cplx<T>*>(G_dev), static_cast<const T*>(p->call.q), T(p->call.alpha)};
-}
-
-// The call's output (p->call.power, p->call.weighted) picks the instantiation of every row kernel: W, its power as reals, or
-// W under the weights alpha Q
-template <typename T>
-int rows_launch_serial(cwt_plan* p, const void* xhat_dev, const Mother& mo, void* W_dev, int64_t ldw, int64_t ncols,
-                       hipEvent_t spectrum_ready) {
-  if (p->call.weighted) return rows_launch_serial_out<T>(p, xhat_dev, mo, weighted_handle<T>(p, W_dev), ldw, ncols, spectrum_ready);
-  if (p->call.power) return rows_launch_serial_out<T>(p, xhat_dev, mo, static_cast<T*>(W_dev), ldw, ncols, spectrum_ready);
-  return rows_launch_serial_out<T>(p, xhat_dev, mo, static_cast<cplx<T>*>(W_dev), ldw, ncols, spectrum_ready);
+int rows_launch_serial(cwt_plan* p, const Call& call, const void* xhat_dev, const Mother& mo, void* W_dev, int64_t ldw,
+                       int64_t ncols, hipEvent_t spectrum_ready) {
+  return with_output<T>(call, W_dev, [&](auto W) {
+    return rows_launch_serial_out<T>(p, call, xhat_dev, mo, W, ldw, ncols, spectrum_ready);
+  });
 }
 
 // Steps 1-3 for cwt_transform
 template <typename T>
-int transform_serial(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev, const Mother& mo, void* W_dev, int64_t ldw,
-                     int64_t ncols) {
+int transform_serial(cwt_plan* p, const Call& call, const void* x_dev, int64_t n0, void* xhat_dev, const Mother& mo, void* W_dev,
+                     int64_t ldw, int64_t ncols) {
   if (p->rt->n_ols) {
-    const int rc = launch_ols_early<T>(p, x_dev, n0, p->rt->ols_grp[0].nrows > 0);
+    const int rc = launch_ols_early<T>(p, call, x_dev, n0, p->rt->ols_grp[0].nrows > 0);
     if (rc) return rc;
   } else {
     HIPCHECK(hipEventRecord(p->ev_fork, p->stream));
@@ -785,24 +778,17 @@ int transform_serial(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev,
   // the forward FFT on side stream 0, so that the first overlap-save rows start on the caller's stream as soon as their block
   // spectra exist (the bands + coefficients of the polynomial rows follow it there)
   HIPCHECK(hipStreamWaitEvent(p->side[0], p->ev_fork, 0));
-  int rc;
-  {
-    StreamGuard caller(p);
-    p->stream = p->side[0];
-    p->call.fft_small = 1;
-    rc = fft_rows_impl<T, IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev);
-    p->call.fft_small = 0;
-  }
+  const int rc = fft_rows_impl<T, IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev, p->side[0], true);
   if (rc) return rc;
   HIPCHECK(hipEventRecord(p->ev_a[1], p->side[0]));
-  return rows_launch_serial<T>(p, xhat_dev, mo, W_dev, ldw, ncols, p->ev_a[1]);
+  return rows_launch_serial<T>(p, call, xhat_dev, mo, W_dev, ldw, ncols, p->ev_a[1]);
 }
 
 // ---- the round-5 schedule (serial_rows = 0, complex64 default; and every call the serial schedule does not take) ---------------
 // ols_early: cwt_transform has queued the block spectra of the overlap-save rows (launch_ols_early)
 template <typename T, typename OUT>
-int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, OUT W, int64_t ldw, int64_t ncols,
-                    const void* x_dev, int64_t n0, bool ols_early) {
+int rows_launch_out(cwt_plan* p, const Call& call, const void* xhat_dev, const Mother& mo, int nrows, OUT W, int64_t ldw,
+                    int64_t ncols, const void* x_dev, int64_t n0, bool ols_early) {
   const int logN = p->logN;
   const cplx<T>* xhat = static_cast<const cplx<T>*>(xhat_dev);
   int rc = CWT_OK;
@@ -811,8 +797,8 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
       const int total = nrows << logN;
       return timed_launch(p, KC_DIRECT, [&] {
         hipLaunchKernelGGL((k_direct<T, IN_SPECTRUM, out_tag_t<OUT>>), dim3((total + 63) / 64), dim3(64), 0, p->stream,
-                           xhat_dev, call_rows(p), nrows, mo, logN, 0L, 0L, W, long(ldw), long(ncols));
-      });
+                           xhat_dev, call_rows(p, call), nrows, mo, logN, 0L, 0L, W, long(ldw), long(ncols));
+      }, p->stream);
     }
     // several rows per workgroup: aim at 4096 points (256 threads)
     const int logTB = std::max(0, std::min(12, p->log_wg_points) - logN);
@@ -821,9 +807,9 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
     const size_t lds = (size_t(TB) << logN) * sizeof(T);
     return timed_launch(p, KC_SMALL, [&] {
       hipLaunchKernelGGL((k_small<T, IN_SPECTRUM, out_tag_t<OUT>>), dim3((nrows + TB - 1) / TB), dim3(threads), lds,
-                         p->stream, xhat_dev, call_rows(p), nrows, mo, tw_table<T>(p, logN), logN, logTB,
+                         p->stream, xhat_dev, call_rows(p, call), nrows, mo, tw_table<T>(p, logN), logN, logTB,
                          0L, 0L, W, long(ldw), long(ncols));
-    });
+    }, p->stream);
   }
   const int logP = std::min(p->log_wg_points, logN);
   const int threads = 1 << (logP - 4);
@@ -843,7 +829,7 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
   if (side_narrow) HIPCHECK(hipStreamWaitEvent(p->side[0], p->ev_fork, 0));   // starts after the spectrum exists
   if (ols_side) {
     HIPCHECK(hipStreamWaitEvent(p->side[1], p->ev_fork, 0));
-    rc = launch_ols_fwd<T>(p, x_dev, n0, p->side[1]);
+    rc = launch_ols_fwd<T>(p, call, x_dev, n0, p->side[1]);
     if (rc) return rc;
     HIPCHECK(hipEventRecord(p->ev_ols, p->side[1]));
   }
@@ -855,11 +841,11 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
   // the coefficients are done only leaves the chip idle: 0.916 against 0.898 ms at config 2 (EXPERIMENTS.md I.4).
   const bool poly_on_side = p->rt->n_poly && side_narrow;
   if (p->rt->n_poly) {
-    rc = launch_poly_coef<T>(p, xhat, mo, 0, poly_on_side ? p->side[0] : p->stream, poly_on_side ? p->side2 : nullptr);
+    rc = launch_poly_coef<T>(p, call, xhat, mo, 0, poly_on_side ? p->side[0] : p->stream, poly_on_side ? p->side2 : nullptr);
     if (rc) return rc;
   }
   if (ols_early) {                     // block spectra already queued on side stream 1 by cwt_transform
-    rc = launch_ols_rows<T>(p, W, ldw, ncols, p->side[1]);
+    rc = launch_ols_rows<T>(p, call, W, ldw, ncols, p->side[1]);
     if (rc) return rc;
     HIPCHECK(hipEventRecord(p->ev_ols, p->side[1]));
   }
@@ -870,8 +856,8 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
     const int nchunks = int(p->rt->poly_chunks.size());
     int r = CWT_OK;
     for (int c = 0; c < nchunks && !r; ++c) {              // chunk c's rows, then chunk c + 1's coefficients, on one stream
-      r = launch_poly_rows_of_call<T>(p, c, W, ldw, ncols, ps);
-      if (!r && c + 1 < nchunks) r = launch_poly_coef<T>(p, xhat, mo, c + 1, ps, poly_on_side ? p->side2 : nullptr);
+      r = launch_poly_rows_of_call<T>(p, call, c, W, ldw, ncols, ps);
+      if (!r && c + 1 < nchunks) r = launch_poly_coef<T>(p, call, xhat, mo, c + 1, ps, poly_on_side ? p->side2 : nullptr);
     }
     return r;
   };
@@ -880,19 +866,19 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
     if (rc) return rc;
   }
   if (p->rt->n_wide) {                 // two-pass rows, chunk by chunk on the plan's stream (one intermediate buffer)
-    rc = launch_wide_rows<T>(p, xhat_dev, mo, W, ldw, ncols);
+    rc = launch_wide_rows<T>(p, call, xhat_dev, mo, W, ldw, ncols);
     if (rc) return rc;
   }
   if (p->rt->n_aols) {                 // after the two-pass chain: both use the intermediate buffer
-    rc = launch_aols<T>(p, xhat_dev, W, ldw, ncols, p->stream);
+    rc = launch_aols<T>(p, call, xhat_dev, W, ldw, ncols, p->stream);
     if (rc) return rc;
   }
   if (ols_early) {
     HIPCHECK(hipStreamWaitEvent(p->stream, p->ev_ols, 0));
   } else if (p->rt->n_ols) {
     if (ols_side) HIPCHECK(hipStreamWaitEvent(p->stream, p->ev_ols, 0));
-    else rc = launch_ols_fwd<T>(p, x_dev, n0, p->stream);
-    if (!rc) rc = launch_ols_rows<T>(p, W, ldw, ncols, p->stream);
+    else rc = launch_ols_fwd<T>(p, call, x_dev, n0, p->stream);
+    if (!rc) rc = launch_ols_rows<T>(p, call, W, ldw, ncols, p->stream);
     if (rc) return rc;
   }
   // band-limited rows: on a side stream beside the two-pass chain (fills its kernel boundaries and
@@ -906,25 +892,19 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
   }
   if (p->rt->n_narrow) {
     if (narrow_ct_all_applies<T>(p)) {
-      StreamGuard guard(p);                                 // p->stream is redirected below; restored on every path
-      hipStream_t keep = p->stream;
       narrow_on_side = side_narrow;
-      if (narrow_on_side) p->stream = p->side[0];
+      const hipStream_t sn = narrow_on_side ? p->side[0] : p->stream;
       int n_small_k, n_big, n_many;
       narrow_class_counts(p, &n_small_k, &n_big, &n_many);
       rc = CWT_OK;
-      if (n_small_k) rc = timed_launch(p, KC_NARROW, [&] { launch_narrow_ct_all<T>(p, xhat, mo, W, ldw, ncols); });
+      if (n_small_k) rc = timed_launch(p, KC_NARROW, [&] { launch_narrow_ct_all<T>(p, call, xhat, mo, W, ldw, ncols, sn); }, sn);
       // the multi-term kernels (few rows, long workgroups) on a stream of their own: at small row counts (a rank's
       // share of 8) they would otherwise run alone at the end of the step
       const bool big_on_side2 = narrow_on_side && n_small_k && (n_many || n_big);
-      hipStream_t sbig = p->side2;
-      if (big_on_side2) {
-        HIPCHECK(hipStreamWaitEvent(sbig, p->ev_fork, 0));
-        p->stream = sbig;
-      }
-      if (!rc && n_many) rc = timed_launch(p, KC_NARROW_MANY, [&] { launch_narrow_ct_many<T>(p, xhat, mo, W, ldw, ncols); });
-      if (!rc && n_big) rc = timed_launch(p, KC_NARROW_BIG, [&] { launch_narrow_ct_big<T>(p, xhat, mo, W, ldw, ncols); });
-      p->stream = keep;
+      const hipStream_t sbig = big_on_side2 ? p->side2 : sn;
+      if (big_on_side2) HIPCHECK(hipStreamWaitEvent(sbig, p->ev_fork, 0));
+      if (!rc && n_many) rc = timed_launch(p, KC_NARROW_MANY, [&] { launch_narrow_ct_many<T>(p, call, xhat, mo, W, ldw, ncols, sbig); }, sbig);
+      if (!rc && n_big) rc = timed_launch(p, KC_NARROW_BIG, [&] { launch_narrow_ct_big<T>(p, call, xhat, mo, W, ldw, ncols, sbig); }, sbig);
       if (rc) return rc;
       if (big_on_side2) {
         HIPCHECK(hipEventRecord(p->ev_big, sbig));
@@ -936,10 +916,10 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
         rc = timed_launch(p, KC_NARROW, [&] {
           for (int r0 = 0; r0 < g.count; r0 += kMaxGridY)
             hipLaunchKernelGGL((k_narrow<T, out_tag_t<OUT>>), dim3(1u << (logN - logP), std::min(kMaxGridY, g.count - r0)),
-                               dim3(threads), lds, p->stream, xhat, call_rows(p) + g.first + r0, mo,
+                               dim3(threads), lds, p->stream, xhat, call_rows(p, call) + g.first + r0, mo,
                                tw_table<T>(p, g.logK), twn_of<T>(p), logN, g.logK, logP - g.logK, W, long(ldw),
                                long(ncols));
-        });
+        }, p->stream);
         if (rc) return rc;
       }
     }
@@ -949,41 +929,41 @@ int rows_launch_out(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nro
 }
 
 template <typename T>
-int rows_launch(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw, int64_t ncols,
-                const void* x_dev, int64_t n0, bool ols_early) {
-  if (p->call.weighted) return rows_launch_out<T>(p, xhat_dev, mo, nrows, weighted_handle<T>(p, W_dev), ldw, ncols, x_dev, n0, ols_early);
-  if (p->call.power) return rows_launch_out<T>(p, xhat_dev, mo, nrows, static_cast<T*>(W_dev), ldw, ncols, x_dev, n0, ols_early);
-  return rows_launch_out<T>(p, xhat_dev, mo, nrows, static_cast<cplx<T>*>(W_dev), ldw, ncols, x_dev, n0, ols_early);
+int rows_launch(cwt_plan* p, const Call& call, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw,
+                int64_t ncols, const void* x_dev, int64_t n0, bool ols_early) {
+  return with_output<T>(call, W_dev, [&](auto W) {
+    return rows_launch_out<T>(p, call, xhat_dev, mo, nrows, W, ldw, ncols, x_dev, n0, ols_early);
+  });
 }
 
-// Every row of the current row table from a spectrum on the caller's stream (inside a CallScope): every entry point but
+// Every row of the current row table from a spectrum on the caller's stream (inside a DrainOnFailure): every entry point but
 // cwt_transform.  No block spectra were queued early, so only a table without overlap-save rows takes the serial schedule.
 template <typename T>
-int rows_impl(cwt_plan* p, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw, int64_t ncols,
-              const void* x_dev = nullptr, int64_t n0 = 0) {
+int rows_impl(cwt_plan* p, const Call& call, const void* xhat_dev, const Mother& mo, int nrows, void* W_dev, int64_t ldw,
+              int64_t ncols, const void* x_dev = nullptr, int64_t n0 = 0) {
   if (int rc = check_geometry(p)) return rc;
-  if (serial_schedule(p, false)) return rows_launch_serial<T>(p, xhat_dev, mo, W_dev, ldw, ncols, nullptr);
-  return rows_launch<T>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0, false);
+  if (serial_schedule(p, false)) return rows_launch_serial<T>(p, call, xhat_dev, mo, W_dev, ldw, ncols, nullptr);
+  return rows_launch<T>(p, call, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0, false);
 }
 
-// cwt_transform after its row table (inside its CallScope): the call decides here, once, before anything is queued, whether
+// cwt_transform after its row table (inside its DrainOnFailure): the call decides here, once, before anything is queued, whether
 // the block spectra go early and whether it takes the serial schedule.  xhat_dev == nullptr: every row is an overlap-save row
 // and no spectrum is computed.
 template <typename T>
-int transform_impl(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_dev, const Mother& mo, int nrows, void* W_dev,
-                   int64_t ldw, int64_t ncols) {
+int transform_impl(cwt_plan* p, const Call& call, const void* x_dev, int64_t n0, void* xhat_dev, const Mother& mo, int nrows,
+                   void* W_dev, int64_t ldw, int64_t ncols) {
   if (int rc = check_geometry(p)) return rc;
   // the overlap-save rows need the signal only: their block spectra are queued on side stream 1 BEFORE the forward FFT, so that
   // they run beside it and beside the two-pass chain
   const bool ols_early = xhat_dev && p->rt->n_ols && p->ols_early && !p->profile;
-  if (serial_schedule(p, ols_early)) return transform_serial<T>(p, x_dev, n0, xhat_dev, mo, W_dev, ldw, ncols);
-  int rc = ols_early ? launch_ols_early<T>(p, x_dev, n0, false) : CWT_OK;
-  if (!rc && xhat_dev) rc = fft_rows_impl<T, IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev);
-  return rc ? rc : rows_launch<T>(p, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0, ols_early);
+  if (serial_schedule(p, ols_early)) return transform_serial<T>(p, call, x_dev, n0, xhat_dev, mo, W_dev, ldw, ncols);
+  int rc = ols_early ? launch_ols_early<T>(p, call, x_dev, n0, false) : CWT_OK;
+  if (!rc && xhat_dev) rc = fft_rows_impl<T, IN_REAL>(p, x_dev, 0, 1, n0, xhat_dev, p->stream);
+  return rc ? rc : rows_launch<T>(p, call, xhat_dev, mo, nrows, W_dev, ldw, ncols, x_dev, n0, ols_early);
 }
 
 // ---- time-pooled scalogram (cwt_transform_pool; kernels: cwt_kernels_pool.hpp) ------------------------------------------------
-// The copy of the current table that the launchers of a pooled call read (cwt_plan::Call::rows), uploaded once per row table
+// The copy of the current table that the launchers of a pooled call read (Call::rows), uploaded once per row table
 // through a staging buffer of its own: out_row of every entry that is not a polynomial row becomes the row's rank among the rows
 // that are not of polynomial form, so that plan scratch holds exactly those rows; behind the descriptors the ranks' out_rows.
 inline const int* pool_map_of(const cwt_plan* p) { return reinterpret_cast<const int*>(p->rt->pool_dev + table_capacity(p->max_rows)); }
@@ -1017,7 +997,7 @@ inline int upload_pool_rows(cwt_plan* p, int nrows) {
   return CWT_OK;
 }
 
-// cwt_transform_pool after its checks and the row table (inside its CallScope).  Signal by signal through transform_impl as a power
+// cwt_transform_pool after its checks and the row table (inside its DrainOnFailure).  Signal by signal through transform_impl as a power
 // call: the schedule, the forms and the kernels of cwt_transform_power, with pool_poly_rows in the place of k_poly_rows and plan
 // scratch (rows not of polynomial form x n0 reals, one signal's) as the output of every other form; pool_rows follows on the
 // caller's stream, where both schedules have joined every kernel that writes the scratch.  xhat_dev: nbatch x nfft, or NULL
@@ -1035,12 +1015,13 @@ int transform_pool_impl(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld
   const int64_t ncols_p = (n0 + (int64_t(1) << logh) - 1) >> logh;
   for (int b = 0; b < nbatch; ++b) {
     T* P = static_cast<T*>(P_dev) + size_t(b) * size_t(nrows) * size_t(ldp);
-    p->call.power = 1;
-    p->call.pool = logh;
-    p->call.pool_out = P;
-    p->call.pool_ld = ldp;
-    p->call.rows = p->rt->pool_dev;
-    rc = transform_impl<T>(p, static_cast<const T*>(x_dev) + size_t(b) * size_t(x_ld), n0,
+    Call call;                                                         // signal b's: a power call that pools into P
+    call.power = 1;
+    call.pool = logh;
+    call.pool_out = P;
+    call.pool_ld = ldp;
+    call.rows = p->rt->pool_dev;
+    rc = transform_impl<T>(p, call, static_cast<const T*>(x_dev) + size_t(b) * size_t(x_ld), n0,
                            xhat_dev ? static_cast<cplx<T>*>(xhat_dev) + size_t(b) * size_t(p->N) : nullptr, mo, nrows, p->pool_s, sld, n0);
     if (rc || !nd) { if (rc) return rc; continue; }
     const int64_t work = logh <= POOL_LOG_TILE ? (int64_t(nd) * ((n0 + (1 << POOL_LOG_TILE) - 1) >> POOL_LOG_TILE) + POOL_TILES - 1) / POOL_TILES
@@ -1048,7 +1029,7 @@ int transform_pool_impl(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld
     rc = timed_launch(p, KC_POOL_ROWS, [&] {
       hipLaunchKernelGGL((pool_rows<T>), dim3(unsigned(work)), dim3(POOL_THREADS), POOL_THREADS * sizeof(T), p->stream,
                          static_cast<const T*>(p->pool_s), long(sld), long(n0), nd, pool_map_of(p), logh, P, long(ldp));
-    });
+    }, p->stream);
     if (rc) return rc;
   }
   return CWT_OK;
@@ -1211,7 +1192,7 @@ int launch_sgrad_partial(cwt_plan* p, const ScaleGrad& sg, const cplx<T>* spec, 
                          p->stream, spec + (size_t(r0) << logM), xhat, rt->adj_dev + first + r0, mo, p->logN, logM, first + r0, nslices,
                          part);
     }
-  });
+  }, p->stream);
 }
 
 template <typename T>
@@ -1219,7 +1200,7 @@ int launch_sgrad_sum(cwt_plan* p, const ScaleGrad& sg, int nbatch, int nrows, in
   return timed_launch(p, KC_SGRAD, [&] {
     hipLaunchKernelGGL((sgrad_sum<T>), dim3(unsigned((nrows + SGRAD_THREADS - 1) / SGRAD_THREADS)), dim3(SGRAD_THREADS), 0, p->stream,
                        static_cast<const T*>(p->sgrad_part), p->rt->adj_dev, nrows, nbatch, nslices, accumulate, sg.out);
-  });
+  }, p->stream);
 }
 
 // xbar_b (+)= Re A^H G_b for every signal b (cwt_hip.h).  Per signal: the accumulator is zeroed; the general rows go in chunks of
@@ -1264,35 +1245,35 @@ int adjoint_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld,
         const int j0 = rt->adj_rows[size_t(first + i)];
         int run = 1;
         while (i + run < cnt && rt->adj_rows[size_t(first + i + run)] == j0 + run) ++run;
-        rc = fft_rows_impl<T, IN_CPLX>(p, G + size_t(j0) * size_t(ldg), ldg, run, ncols, spec + size_t(i) * size_t(N));
+        rc = fft_rows_impl<T, IN_CPLX>(p, G + size_t(j0) * size_t(ldg), ldg, run, ncols, spec + size_t(i) * size_t(N), p->stream);
         if (rc) return rc;
         i += run;
       }
       if (xbar_dev) rc = timed_launch(p, KC_ADJOINT, [&] {
         hipLaunchKernelGGL((k_adj_accum<T>), dim3(bins), dim3(256), 0, p->stream, static_cast<const cplx<T>*>(spec),
                            rt->adj_dev + first, cnt, mo, logN, acc);
-      });
+      }, p->stream);
       if (!rc && sg) rc = launch_sgrad_partial<T>(p, *sg, spec, b, first, cnt, nrows, mo, logN, nslices);
       if (rc) return rc;
     }
     if (!xbar_dev) continue;
     for (size_t c = 0; use_poly && c < rt->poly_chunks.size(); ++c) {
       const auto& ch = rt->poly_chunks[c];
-      const RowDesc* rows = call_rows(p) + rt->poly_first + ch.row_first;
+      const RowDesc* rows = rt->rows_dev + rt->poly_first + ch.row_first;
       rc = timed_launch(p, KC_ADJOINT, [&] {
         for (int r0 = 0; r0 < ch.nrows; r0 += kMaxGridY)
           hipLaunchKernelGGL((k_poly_moments<T>), dim3(unsigned(std::max<int64_t>(1, N >> 14)), std::min(kMaxGridY, ch.nrows - r0)), dim3(256),
                              256 * sizeof(cplx<T>), p->stream, G, long(ldg), long(ncols), rows + r0, twn_of<T>(p), logN, coef);
-      });
+      }, p->stream);
       if (!rc && ch.wgs[2]) rc = timed_launch(p, KC_POLY_COEF, [&] {
         hipLaunchKernelGGL((k_poly_coef<T, 14, true>), dim3(unsigned(ch.wgs[2])), dim3(1024), lds_of(14), p->stream,
-                           static_cast<const cplx<T>*>(nullptr), rows, tw, ch.cls, coef, rtab); });
+                           static_cast<const cplx<T>*>(nullptr), rows, tw, ch.cls, coef, rtab); }, p->stream);
       if (!rc && ch.wgs[1]) rc = timed_launch(p, KC_POLY_COEF, [&] {
         hipLaunchKernelGGL((k_poly_coef<T, 13, true>), dim3(unsigned(ch.wgs[1])), dim3(512), lds_of(13), p->stream,
-                           static_cast<const cplx<T>*>(nullptr), rows, tw, ch.cls, coef, rtab); });
+                           static_cast<const cplx<T>*>(nullptr), rows, tw, ch.cls, coef, rtab); }, p->stream);
       if (!rc && ch.wgs[0]) rc = timed_launch(p, KC_POLY_COEF, [&] {
         hipLaunchKernelGGL((k_poly_coef<T, 12, true>), dim3(unsigned(ch.wgs[0])), dim3(256), lds_of(12), p->stream,
-                           static_cast<const cplx<T>*>(nullptr), rows, tw, ch.cls, coef, rtab); });
+                           static_cast<const cplx<T>*>(nullptr), rows, tw, ch.cls, coef, rtab); }, p->stream);
       int ks0 = int(N / 2), ks1 = -int(N / 2);            // the union of the chunk's bands (narrow rows: a few thousand bins)
       for (int i = 0; i < ch.nrows; ++i) {
         const RowDesc& r = rt->table[size_t(rt->poly_first + ch.row_first + i)];
@@ -1302,16 +1283,16 @@ int adjoint_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch_ld,
       if (!rc && ks1 > ks0) rc = timed_launch(p, KC_ADJOINT, [&] {
         hipLaunchKernelGGL((k_poly_adj_accum<T>), dim3(unsigned((ks1 - ks0 + 255) / 256)), dim3(256), 0, p->stream,
                            static_cast<const cplx<T>*>(coef), rows, ch.nrows, mo, twn_of<T>(p), logN, rtab, ks0, ks1 - ks0, acc);
-      });
+      }, p->stream);
       if (rc) return rc;
     }
-    rc = fft_rows_impl<T, IN_CPLX>(p, acc, N, 1, N, spec);
+    rc = fft_rows_impl<T, IN_CPLX>(p, acc, N, 1, N, spec, p->stream);
     if (rc) return rc;
     rc = timed_launch(p, KC_ADJOINT, [&] {
       hipLaunchKernelGGL((k_adj_out<T>), dim3(unsigned((ncols + 255) / 256)), dim3(256), 0, p->stream,
                          static_cast<const cplx<T>*>(spec), long(ncols), static_cast<T*>(xbar_dev) + size_t(b) * size_t(xbar_ld),
                          accumulate);
-    });
+    }, p->stream);
     if (rc) return rc;
   }
   if (sg) return launch_sgrad_sum<T>(p, *sg, nbatch, nrows, nslices, accumulate);
@@ -1356,7 +1337,7 @@ int hop_rows_out(cwt_plan* p, const cplx<T>* xhat, int64_t xhat_ld, int nbatch, 
       hipLaunchKernelGGL((hop_fold<T>), dim3(1u << (logM - logTK), unsigned(cnt * nrows)), dim3(HOP_FOLD_THREADS),
                          HOP_FOLD_THREADS * sizeof(cplx<T>), p->stream, xh, long(xhat_ld), p->rt->adj_dev, nrows, mo, p->logN, logM,
                          p->hop_fuse_terms, Z);
-    });
+    }, p->stream);
     if (rc) return rc;
     OUT o = out + long(b0) * long(nrows) * long(ld);
     const int total = cnt * nrows;
@@ -1372,28 +1353,23 @@ int hop_rows_out(cwt_plan* p, const cplx<T>* xhat, int64_t xhat_ld, int nbatch, 
         case 11: launch_hop_rows<T, 11>(p, xh, xhat_ld, Z, nrows, total, mo, o, ld, ncols_h); break;
         default: launch_hop_rows<T, 12>(p, xh, xhat_ld, Z, nrows, total, mo, o, ld, ncols_h); break;
       }
-    });
+    }, p->stream);
     if (rc) return rc;
   }
   return CWT_OK;
 }
 
 // cwt_transform_hop / cwt_transform_rows_hop after their checks and the row table: the forward transforms of the signals (x_dev
-// given; spectra to xhat_dev, nbatch x N), then the rows.  output: 0 = W, 1 = |W|^2, 2 = (alpha Q) W.
+// given; spectra to xhat_dev, nbatch x N), then the rows.  Of the call, its output only: W, |W|^2 or (alpha Q) W.
 template <typename T>
-int transform_hop_impl(cwt_plan* p, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, const void* xhat_dev, int64_t xhat_ld,
-                       const Mother& mo, int nrows, int logM, int output, void* out_dev, const void* q, double alpha, int64_t ld,
-                       int64_t ncols_h) {
+int transform_hop_impl(cwt_plan* p, const Call& call, const void* x_dev, int nbatch, int64_t x_ld, int64_t n0, const void* xhat_dev,
+                       int64_t xhat_ld, const Mother& mo, int nrows, int logM, void* out_dev, int64_t ld, int64_t ncols_h) {
   if (x_dev) {
-    const int rc = fft_rows_impl<T, IN_REAL>(p, x_dev, x_ld, nbatch, n0, const_cast<void*>(xhat_dev));
+    const int rc = fft_rows_impl<T, IN_REAL>(p, x_dev, x_ld, nbatch, n0, const_cast<void*>(xhat_dev), p->stream);
     if (rc) return rc;
   }
   const cplx<T>* xhat = static_cast<const cplx<T>*>(xhat_dev);
-  if (output == 2)
-    return hop_rows_out<T>(p, xhat, xhat_ld, nbatch, mo, nrows, logM,
-                           weighted_ptr<T>{static_cast<cplx<T>*>(out_dev), static_cast<const T*>(q), T(alpha)}, ld, ncols_h);
-  if (output == 1) return hop_rows_out<T>(p, xhat, xhat_ld, nbatch, mo, nrows, logM, static_cast<T*>(out_dev), ld, ncols_h);
-  return hop_rows_out<T>(p, xhat, xhat_ld, nbatch, mo, nrows, logM, static_cast<cplx<T>*>(out_dev), ld, ncols_h);
+  return with_output<T>(call, out_dev, [&](auto out) { return hop_rows_out<T>(p, xhat, xhat_ld, nbatch, mo, nrows, logM, out, ld, ncols_h); });
 }
 
 // xbar_b (+)= Re A_h^H G_b (cwt_hip.h).  Per signal: the accumulator is zeroed; chunks of rows of G_h go through their M-point
@@ -1428,22 +1404,22 @@ int adjoint_hop_impl(cwt_plan* p, const void* G_dev, int nbatch, int64_t g_batch
         hipLaunchKernelGGL((k_small<T, IN_CPLX>), dim3(unsigned((cnt + TB - 1) / TB)), dim3(TB << (logM - 4)), (size_t(TB) << logM) * sizeof(T),
                            p->stream, static_cast<const void*>(G + size_t(first) * size_t(ldg)), (const RowDesc*)nullptr, cnt, none,
                            tw_table<T>(p, logM), logM, logTB, long(ncols_h), long(ldg), spec, long(M), long(M));
-      });
+      }, p->stream);
       if (!rc && xbar_dev) rc = timed_launch(p, KC_ADJOINT, [&] {
         hipLaunchKernelGGL((hop_adj_accum<T>), dim3(bins), dim3(256), 0, p->stream, static_cast<const cplx<T>*>(spec),
                            rt->adj_dev + first, cnt, mo, logN, logM, acc);
-      });
+      }, p->stream);
       if (!rc && sg) rc = launch_sgrad_partial<T>(p, *sg, spec, b, first, cnt, nrows, mo, logM, nslices);
       if (rc) return rc;
     }
     if (!xbar_dev) continue;
-    rc = fft_rows_impl<T, IN_CPLX>(p, acc, N, 1, N, spec);
+    rc = fft_rows_impl<T, IN_CPLX>(p, acc, N, 1, N, spec, p->stream);
     if (rc) return rc;
     rc = timed_launch(p, KC_ADJOINT, [&] {
       hipLaunchKernelGGL((k_adj_out<T>), dim3(unsigned((n0 + 255) / 256)), dim3(256), 0, p->stream,
                          static_cast<const cplx<T>*>(spec), long(n0), static_cast<T*>(xbar_dev) + size_t(b) * size_t(xbar_ld),
                          accumulate);
-    });
+    }, p->stream);
     if (rc) return rc;
   }
   if (sg) return launch_sgrad_sum<T>(p, *sg, nbatch, nrows, nslices, accumulate);
@@ -1480,7 +1456,7 @@ int wct_products_impl(cwt_plan* p, const void* W1, const void* W2, const double*
                          static_cast<const T*>(p->weights_dev) + r0, long(ld), long(ncols), static_cast<cplx<T>*>(P) + o,
                          static_cast<cplx<T>*>(C) + o, static_cast<T*>(A) + o);
     }
-  });
+  }, p->stream);
 }
 
 template <typename T>
@@ -1497,7 +1473,7 @@ int boxcar_impl(cwt_plan* p, const void* in, int nrows, int64_t ld, int64_t ncol
         hipLaunchKernelGGL((k_boxcar_scales_ring<T>), dim3(unsigned((ncols + 255) / 256), unsigned(std::min(kMaxGridY, strips - s0))),
                            dim3(256), ring_bytes, p->stream, static_cast<const cplx<T>*>(in), nrows, long(ld),
                            long(ncols), static_cast<const T*>(p->weights_dev), nwin, static_cast<cplx<T>*>(out), RB, s0);
-    });
+    }, p->stream);
   }
   // slabs of rows (gridDim.y is limited to 65535); every slab sees all nrows, so the taps reach across its edges
   return timed_launch(p, KC_ELEMENTWISE, [&] {
@@ -1505,7 +1481,7 @@ int boxcar_impl(cwt_plan* p, const void* in, int nrows, int64_t ld, int64_t ncol
       hipLaunchKernelGGL((k_boxcar_scales<T>), dim3(unsigned((ncols + 255) / 256), unsigned(std::min(kMaxGridY, nrows - r0))),
                          dim3(256), 0, p->stream, static_cast<const cplx<T>*>(in), nrows, long(ld), long(ncols),
                          static_cast<const T*>(p->weights_dev), nwin, static_cast<cplx<T>*>(out), r0);
-  });
+  }, p->stream);
 }
 
 template <typename T>
@@ -1517,7 +1493,7 @@ int coherence_impl(cwt_plan* p, const void* S, const void* S12, int nrows, int64
                          dim3(256), 0, p->stream, static_cast<const cplx<T>*>(S) + o, static_cast<const cplx<T>*>(S12) + o,
                          long(ld), long(ncols), static_cast<T*>(out) + o);
     }
-  });
+  }, p->stream);
 }
 
 template <typename T, bool POWER>
@@ -1530,7 +1506,7 @@ int reduce_scales_impl(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncol
     hipLaunchKernelGGL((k_icwt<T, POWER>), dim3(blocks), dim3(ICWT_THREADS), 0, p->stream,
                        static_cast<const cplx<T>*>(W_dev), long(ldw), long(ncols), nrows,
                        static_cast<const T*>(p->weights_dev), T(coeff), static_cast<T*>(out_dev));
-  });
+  }, p->stream);
 }
 
 // Synchrosqueezing (cwt_kernels_ssq.hpp): the spectrum of the derivative signal, and the reassignment of W along frequency
@@ -1540,7 +1516,7 @@ int spectrum_derivative_impl(cwt_plan* p, const void* xhat_dev, double dt, void*
   return timed_launch(p, KC_SSQ_DERIV, [&] {
     hipLaunchKernelGGL((ssq_spec_deriv<T>), dim3(unsigned((p->N + 255) / 256)), dim3(256), 0, p->stream,
                        static_cast<const cplx<T>*>(xhat_dev), int(p->N), w1, static_cast<cplx<T>*>(yhat_dev));
-  });
+  }, p->stream);
 }
 
 template <typename T>
@@ -1554,7 +1530,7 @@ int ssq_reassign_impl(cwt_plan* p, const void* W_dev, const void* dW_dev, int64_
       for (int k0 = 0; k0 < nf; k0 += kMaxGridY)                 // (gridDim.y is limited to 65535: slabs of rows)
         hipLaunchKernelGGL((ssq_zero<T>), dim3(unsigned((ncols + 255) / 256), unsigned(std::min(kMaxGridY, nf - k0))), dim3(256), 0,
                            p->stream, static_cast<cplx<T>*>(S_dev) + size_t(k0) * size_t(ldt), long(ldt), long(ncols));
-    });
+    }, p->stream);
     if (rc) return rc;
   }
   const double l0 = std::log2(2.0 * 3.14159265358979323846 * f_lo);
@@ -1570,7 +1546,7 @@ int ssq_reassign_impl(cwt_plan* p, const void* W_dev, const void* dW_dev, int64_
                          static_cast<const cplx<T>*>(W_dev), static_cast<const cplx<T>*>(dW_dev), long(ld), long(ncols), nrows,
                          static_cast<const T*>(p->weights_dev), gamma * gamma, l0, 1.0 / dv, nf, static_cast<cplx<T>*>(S_dev),
                          long(ldt));
-  });
+  }, p->stream);
 }
 
 // G[j, n] = w_j gT[bins[j, n], n] (cwt_kernels_ssq_grad.hpp): the transpose of the reassignment, through the recorded bins
@@ -1586,7 +1562,7 @@ int ssq_gather_impl(cwt_plan* p, const void* gT_dev, int64_t ldt, int nf, const 
                          dim3(SSQG_THREADS), 0, p->stream, static_cast<const cplx<T>*>(gT_dev), long(ldt), nf,
                          static_cast<const short*>(bins_dev), long(ldb), static_cast<const T*>(p->weights_dev), nrows, long(ncols),
                          static_cast<cplx<T>*>(G_dev), long(ldg), s0);
-  });
+  }, p->stream);
 }
 
 // Chirp-kernel spectra for length n0 on this plan (N = M >= 2 n0 - 1), cached per n0.
@@ -1603,7 +1579,7 @@ int bluestein_prepare(cwt_plan* p, int64_t n0) {
     hipLaunchKernelGGL((k_chirp_kernel<T>), dim3(blocks), dim3(256), 0, p->stream, long(n0), long(p->N), i == 0 ? +1 : -1,
                        static_cast<cplx<T>*>(p->bs_a));
     HIPCHECK(hipGetLastError());
-    rc = fft_rows_impl<T, IN_CPLX>(p, p->bs_a, p->N, 1, p->N, p->bs_khat[i]);
+    rc = fft_rows_impl<T, IN_CPLX>(p, p->bs_a, p->N, 1, p->N, p->bs_khat[i], p->stream);
   }
   if (rc) return rc;
   p->bs_n0 = n0;
@@ -1630,8 +1606,8 @@ int bluestein_convolve(cwt_plan* p, const void* spec, int nrows, int which, void
   set_split(p);
   Mother mo = mother_of(MOTHER_TABLE, 0.0);
   mo.table = p->bs_khat[which];
-  CallScope scope(p);
-  return scope.done(rows_impl<T>(p, spec, mo, nrows, out, ldo, n0));
+  DrainOnFailure drain(p);
+  return drain.done(rows_impl<T>(p, Call{}, spec, mo, nrows, out, ldo, n0));
 }
 
 template <typename T>
@@ -1645,7 +1621,7 @@ int forward_fft_n_impl(cwt_plan* p, const void* x_dev, int64_t n0, void* xhat_de
   hipLaunchKernelGGL((k_chirp_mul<T, IN_REAL>), grid, dim3(256), 0, p->stream, x_dev, long(n0), long(n0), -1, 1.0,
                      static_cast<cplx<T>*>(p->bs_a), long(n0));
   HIPCHECK(hipGetLastError());
-  rc = fft_rows_impl<T, IN_CPLX>(p, p->bs_a, n0, 1, n0, p->bs_spec);
+  rc = fft_rows_impl<T, IN_CPLX>(p, p->bs_a, n0, 1, n0, p->bs_spec, p->stream);
   if (!rc) rc = bluestein_convolve<T>(p, p->bs_spec, 1, 0, xhat_dev, n0, n0);
   if (rc) return rc;
   hipLaunchKernelGGL((k_chirp_mul<T, IN_CPLX>), grid, dim3(256), 0, p->stream, xhat_dev, long(n0), long(n0), -1, 1.0,
@@ -1688,7 +1664,7 @@ int transform_rows_n_impl(cwt_plan* p, const void* xhat_dev, int64_t n0, int mot
                        dpar + first, dpar + nrows + first, dpar + 2 * size_t(nrows) + first, mo, long(n0),
                        static_cast<cplx<T>*>(p->bs_a), long(n0));
     HIPCHECK(hipGetLastError());
-    rc = fft_rows_impl<T, IN_CPLX>(p, p->bs_a, n0, cnt, n0, p->bs_spec);
+    rc = fft_rows_impl<T, IN_CPLX>(p, p->bs_a, n0, cnt, n0, p->bs_spec, p->stream);
     cplx<T>* Wslab = static_cast<cplx<T>*>(W_dev) + size_t(first) * size_t(ldw);
     if (!rc) rc = bluestein_convolve<T>(p, p->bs_spec, cnt, 1, Wslab, ldw, n0);
     if (rc) return rc;
@@ -1707,7 +1683,7 @@ int random_normal_impl(cwt_plan* p, uint64_t seed, uint64_t offset, int64_t n, d
   return timed_launch(p, KC_ELEMENTWISE, [&] {
     hipLaunchKernelGGL((k_normal_fill<T>), dim3(blocks), dim3(256), 0, p->stream, (unsigned long long)seed,
                        (unsigned long long)offset, long(n), scale, static_cast<T*>(out));
-  });
+  }, p->stream);
 }
 template <typename T>
 int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g, void* out) {
@@ -1719,17 +1695,17 @@ int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g
   return timed_launch(p, KC_ELEMENTWISE, [&] {
     hipLaunchKernelGGL((k_ar1_filter<T>), dim3(blocks), dim3(256), 0, p->stream, static_cast<const T*>(e), long(tau), long(n), g,
                        long(warm), seg, static_cast<T*>(out));
-  });
+  }, p->stream);
 }
 
 // ---- one precision per translation unit ----------------------------------------------------------------------------------------
 #define CWT_LAUNCH_TEMPLATES(X, T)                                                                                                  \
   X int build_tables<T>(cwt_plan*);                                                                                                 \
   X int set_func_attrs<T>();                                                                                                        \
-  X int fft_rows_impl<T, IN_REAL>(cwt_plan*, const void*, int64_t, int, int64_t, void*);                                            \
-  X int fft_rows_impl<T, IN_CPLX>(cwt_plan*, const void*, int64_t, int, int64_t, void*);                                            \
-  X int rows_impl<T>(cwt_plan*, const void*, const Mother&, int, void*, int64_t, int64_t, const void*, int64_t);                    \
-  X int transform_impl<T>(cwt_plan*, const void*, int64_t, void*, const Mother&, int, void*, int64_t, int64_t);                \
+  X int fft_rows_impl<T, IN_REAL>(cwt_plan*, const void*, int64_t, int, int64_t, void*, hipStream_t, bool);                         \
+  X int fft_rows_impl<T, IN_CPLX>(cwt_plan*, const void*, int64_t, int, int64_t, void*, hipStream_t, bool);                         \
+  X int rows_impl<T>(cwt_plan*, const Call&, const void*, const Mother&, int, void*, int64_t, int64_t, const void*, int64_t);       \
+  X int transform_impl<T>(cwt_plan*, const Call&, const void*, int64_t, void*, const Mother&, int, void*, int64_t, int64_t);        \
   X int fill_ols_tables<T>(cwt_plan*, const Mother&);                                                                               \
   X int fill_aols_tables<T>(cwt_plan*, const Mother&);                                                                              \
   X int fill_poly_tables<T>(cwt_plan*);                                                                                             \
@@ -1748,8 +1724,8 @@ int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g
   X int transform_rows_n_impl<T>(cwt_plan*, const void*, int64_t, int, double, double, const double*, int, void*, int64_t);        \
   X int adjoint_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int64_t, const Mother&, int, void*, int64_t, int,     \
                         const ScaleGrad*);                                                                                          \
-  X int transform_hop_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, const void*, int64_t, const Mother&, int, int, int, void*, \
-                              const void*, double, int64_t, int64_t);                                                              \
+  X int transform_hop_impl<T>(cwt_plan*, const Call&, const void*, int, int64_t, int64_t, const void*, int64_t, const Mother&, int, int, \
+                              void*, int64_t, int64_t);                                                                            \
   X int transform_pool_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, void*, const Mother&, int, int, void*, int64_t);         \
   X int adjoint_hop_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int64_t, int, int64_t, const Mother&, int, void*, int64_t, int, \
                             const ScaleGrad*);

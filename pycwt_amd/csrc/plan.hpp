@@ -2,6 +2,7 @@
 //   plan_host.cpp    row classification (build_row_table: per-call gates, per-row form searches, one layout pass per form),
 //                    row-table cache, scratch buffers, host copies -- plain C++ against the HIP runtime API, no kernels
 //   launch_impl.hpp  every kernel launch, as templates over the precision; instantiated by launch_f64.hip / launch_f32.hip
+//                    (what one call decides travels down it as a Call value; the plan holds resources, options and caches only)
 //   abi.hip          the exported C functions (include/cwt_hip.h)
 // Everything here lives in namespace cwtd ("detail"); nothing is exported but the C ABI.
 #pragma once
@@ -70,6 +71,23 @@ struct RowRequest {
   int64_t out_ncols = 0;    // > 0: W's columns, for the rows on the band-passed signal (which need the spectrum only)
 };
 
+// What an entry point decides about one call that queues rows: built on the entry point's stack and passed by const reference
+// down the launch path (launch_impl.hpp).  The plan keeps none of it.
+struct Call {
+  int64_t ols_x_ld = 0;                  // cwt_transform_batch: elements between the signals of the batch
+  int power = 0;                         // the *_power entry points: the row kernels write |W|^2 as reals, not W
+  int weighted = 0;                      // the *_weighted entry points: the row kernels write (alpha Q) W, Q read at the store's [j, n]
+  const void* q = nullptr;               // ... Q (reals of the plan's precision, the leading dimension and batch stride of the output)
+  double alpha = 0.0;
+  // cwt_transform_pool (a power call besides): window means of h = 2^pool columns.  The polynomial rows sum their windows in
+  // pool_poly_rows and write pool_out; every other launcher gets plan scratch as its output and `rows`, the table's descriptors with
+  // out_row renumbered densely over the rows that are not of polynomial form (RowTable::pool_dev)
+  int pool = 0;                          // log2 h; 0: not a pooled call
+  void* pool_out = nullptr;              // Pbar of the signal in progress ...
+  int64_t pool_ld = 0;                   // ... and its leading dimension
+  const cwt::RowDesc* rows = nullptr;    // nullptr: the current table's own descriptors
+};
+
 }  // namespace cwtd
 
 struct cwt_plan {
@@ -78,25 +96,7 @@ struct cwt_plan {
   int64_t N = 0;
   int prec = 64;
   int max_rows = 0;
-  hipStream_t stream = nullptr;
-  // State of the one cwt_transform / cwt_transform_batch in progress, read by launches deep in launch_impl.hpp.  Written only
-  // inside that call's CallScope (launch_impl.hpp), which clears it again on every way out.
-  struct Call {
-    int fft_small = 0;                     // the serial schedule's forward FFT, queued on side stream 0, takes half-size tiles
-    int64_t ols_x_ld = 0;                  // cwt_transform_batch: elements between the signals of the batch
-    int power = 0;                         // the *_power entry points: the row kernels write |W|^2 as reals, not W
-    int weighted = 0;                      // the *_weighted entry points: the row kernels write (alpha Q) W, Q read at the store's [j, n]
-    const void* q = nullptr;               // ... Q (reals of the plan's precision, the leading dimension and batch stride of the output)
-    double alpha = 0.0;
-    // cwt_transform_pool (a power call besides): window means of h = 2^pool columns.  The polynomial rows sum their windows in
-    // pool_poly_rows and write pool_out; every other launcher gets plan scratch as its output and `rows`, the table's descriptors with
-    // out_row renumbered densely over the rows that are not of polynomial form (RowTable::pool_dev)
-    int pool = 0;                          // log2 h; 0: not a pooled call
-    void* pool_out = nullptr;              // Pbar of the signal in progress ...
-    int64_t pool_ld = 0;                   // ... and its leading dimension
-    const cwt::RowDesc* rows = nullptr;
-  };
-  Call call;
+  hipStream_t stream = nullptr;   // the caller's stream: written by cwt_plan_set_stream alone
   // options
   int chunk_rows = 0;      // rows per two-pass chunk; 0 = as many as fit 192 MiB of intermediate, which
                            // stays inside the 256 MiB Infinity Cache (12 rows at N = 2^20 fp64)
