@@ -580,6 +580,43 @@ int cwt_wct_coherence(cwt_plan* plan, const void* S_dev, const void* S12_dev, in
 int cwt_icwt_reduce(cwt_plan* plan, const void* W_dev, int64_t ldw, int64_t ncols, int nrows,
                     const double* scales_host, double coeff, void* out_dev);
 
+/* ---- wavelet shrinkage: exact row order statistics, thresholded inverse ------------------------------------------------------------
+ * cwt_row_order_statistics: out[j * ldo + i] = the ranks[i]-th smallest (0-based) of v[j, n], n < ncols, for every row j < nrows.
+ *     is_complex = 0:  v = A[j * ld + n], A_dev nrows x ld reals of the plan's precision T (a power matrix of the *_power functions)
+ *     is_complex = 1:  v = fma(re, re, im * im) of the complex entry, in T (A_dev nrows x ld complex: W): one rounded product and one
+ *                      fused multiply-add, the same bits in every pass and in cwt_icwt_shrink.
+ * out_dev: nrows x ldo reals of T, ldo >= nranks; elements nranks .. ldo - 1 of a row are never touched.  Columns ncols .. ld - 1 of
+ * A are never read; ncols is not tied to nfft.  1 <= nranks <= 8 (all ranks of a call share the reads of the row while their
+ * keys share a prefix), 0 <= ranks[i] < ncols; ANY nrows >= 1 (a launch covers at most 32768 rows, and as many as fit 64 MiB of
+ * plan scratch; more go out slab after slab, in order).  ranks_host is consumed before the call returns.  Queued on the plan's
+ * stream without host synchronisation (the data-dependent passes are decided on the device); work space from plan scratch.
+ * EXACT: the result is a value of the row itself -- never an interpolation, no tolerance.  Order: by the order-preserving map of
+ * the IEEE bit pattern to an unsigned key; -0.0 sorts directly below +0.0 (either may come out where both are candidates);
+ * every NaN, whatever its sign bit, sorts after +inf, so a rank at or beyond the row's non-NaN count returns (a quiet) NaN, as
+ * np.sort(row)[rank] does.  Method: most-significant-digit radix select, 11-bit digits, integer counts in LDS and in a per-row
+ * global histogram (integer atomics: exact whatever the order, the same result on every run); once at most 2048 candidates are
+ * left they are compacted and the remaining digits run on that set.  Continuous data: two counting reads and the compaction read
+ * of A; worst case (a row of identical values) key width / digit width = 6 (fp64) or 3 (fp32) reads; ncols <= 2048: one read.
+ * Refused with CWT_EINVAL before anything is queued: NULL pointers, is_complex not 0 or 1, nrows < 1, ncols < 1, ld < ncols, nranks
+ * outside [1, 8], ldo < nranks, a rank outside [0, ncols).
+ *
+ * cwt_icwt_shrink: cwt_icwt_reduce over shrunk coefficients,
+ *     out[n] = coeff * sum_j Re eta(W[j, n]; lambda_j) / sqrt(scales[j]),   n < ncols,
+ * lambda_dev: nrows reals of T ON THE DEVICE (>= 0; e.g. scaled order statistics of cwt_row_order_statistics, which never visit the
+ * host).  With v = fma(re, re, im * im) as above and l2 = lambda * lambda, both in T:
+ *     mode 0 (hard)     eta = W if v > l2, else 0
+ *     mode 1 (soft)     eta = W * max(0, 1 - lambda / sqrt(v))
+ *     mode 2 (garrote)  eta = W * max(0, 1 - l2 / v)
+ * (sqrt and the divisions correctly rounded).  v = 0 gives 0; lambda = 0 keeps everything; lambda = +inf drops the row; an entry
+ * with a NaN component, or a NaN lambda, gives NaN.  The read stream, the eight partial sums and their fold are those of
+ * cwt_icwt_reduce: with every lambda = 0 in mode 0 the output equals cwt_icwt_reduce's bit for bit.  W_dev: nrows x ldw complex;
+ * out_dev: ncols reals; queued on the plan's stream without host synchronisation.  Refused with CWT_EINVAL: NULL pointers, nrows
+ * outside [1, max_rows], ncols < 1, ldw < ncols, a scale that is not positive, mode outside 0 .. 2.                               */
+int cwt_row_order_statistics(cwt_plan* plan, const void* A_dev, int is_complex, int64_t ld, int64_t ncols, int nrows,
+                             const int64_t* ranks_host, int nranks, void* out_dev, int64_t ldo);
+int cwt_icwt_shrink(cwt_plan* plan, const void* W_dev, int64_t ldw, int64_t ncols, int nrows, const double* scales_host,
+                    const void* lambda_dev, int mode, double coeff, void* out_dev);
+
 /* Weighted reduction over scales with explicit weights:
  *   out[n] = coeff * sum_j g(W[j, n]) * weights[j],  g = Re (power = 0) or |.|^2 (power = 1).
  * power = 1 with weights 1/s_j on the selected scales (0 elsewhere) and coeff = dj*dt/cdelta is the

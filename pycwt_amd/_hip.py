@@ -93,6 +93,8 @@ SYMBOLS = [
     ("cwt_ssq_reassign_bins", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double,
                                         C.c_double, C.c_int, _P, C.c_int64, C.c_int, _P, C.c_int64]),
     ("cwt_ssq_gather", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int64, _P, C.c_int64]),
+    ("cwt_row_order_statistics", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int, _P, C.c_int64]),
+    ("cwt_icwt_shrink", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), _P, C.c_int, C.c_double, _P]),
     ("cwt_time_mean_power", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
     ("cwt_time_mean_real", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
     ("cwt_coherence_histogram", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, C.c_int64, C.c_int, _P]),
@@ -652,6 +654,24 @@ class Plan:
         w = np.ascontiguousarray(weights, dtype=np.float64)
         self.lib.check(self.lib.cwt_ssq_gather(self.h, _P(gT_dev), ldt, int(nf), _P(bins_dev), ldb, _dptr(w), w.size, ncols,
                                                _P(G_dev), ldg))
+
+    @_locked
+    def row_order_statistics(self, A_dev: int, is_complex: bool, ld: int, ncols: int, nrows: int, ranks, out_dev: int, ldo: int):
+        """out[j, i] = the ranks[i]-th smallest (0-based) of row j of A: of its reals, or (is_complex) of fma(re, re, im im) of its
+        complex entries (cwt_row_order_statistics); at most 8 ranks per call; out: nrows x ldo reals of the plan's precision."""
+        r = np.ascontiguousarray(ranks, dtype=np.int64)
+        self.lib.check(self.lib.cwt_row_order_statistics(self.h, _P(A_dev), int(bool(is_complex)), ld, ncols, nrows,
+                                                         r.ctypes.data_as(C.POINTER(C.c_int64)), r.size, _P(out_dev), ldo))
+
+    SHRINK_MODES = {"hard": 0, "soft": 1, "garrote": 2}
+
+    @_locked
+    def icwt_shrink(self, W_dev: int, ldw: int, ncols: int, scales, lambda_dev: int, mode, coeff: float, out_dev: int):
+        """out[n] = coeff sum_j Re eta(W[j, n]; lambda_j) / sqrt(scales[j]) (cwt_icwt_shrink); lambda_dev: one real of the plan's
+        precision per row, on the device; mode: "hard" | "soft" | "garrote" (or 0 | 1 | 2)."""
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        self.lib.check(self.lib.cwt_icwt_shrink(self.h, _P(W_dev), ldw, ncols, s.size, _dptr(s), _P(lambda_dev),
+                                                int(self.SHRINK_MODES.get(mode, mode)), float(coeff), _P(out_dev)))
 
     @_locked
     def time_mean_power(self, W_dev: int, ldw: int, ncols: int, nrows: int, out_dev: int):

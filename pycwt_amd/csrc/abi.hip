@@ -366,7 +366,7 @@ int cwt_plan_destroy(cwt_plan* p) {
   for (auto& t : p->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   for (auto e : p->free_events) (void)hipEventDestroy(e);
   void* bufs[] = {p->tw_all, p->twn_lo, p->weights_dev, p->Z, p->xs, p->xm, p->xsa, p->pcoef, p->pband, p->range_dev, p->hx, p->hxhat, p->hW,
-                  p->bs_khat[0], p->bs_khat[1], p->bs_a, p->bs_spec, p->bs_par, p->adj_spec, p->adj_acc, p->hop_z, p->sgrad_part, p->pool_s};
+                  p->bs_khat[0], p->bs_khat[1], p->bs_a, p->bs_spec, p->bs_par, p->adj_spec, p->adj_acc, p->hop_z, p->sgrad_part, p->pool_s, p->sel};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (auto& t : p->slots) {
     if (t.gt_dev) (void)hipFree(t.gt_dev);
@@ -1057,6 +1057,38 @@ int cwt_icwt_reduce(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols, 
     w[j] = 1.0 / std::sqrt(scales[j]);
   }
   return cwt_reduce_scales(p, W_dev, ldw, ncols, nrows, w.data(), 0, coeff, out_dev);
+}
+
+int cwt_icwt_shrink(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols, int nrows, const double* scales,
+                    const void* lambda_dev, int mode, double coeff, void* out_dev) {
+  if (!p || !W_dev || !scales || !lambda_dev || !out_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (nrows < 1 || nrows > p->max_rows) return fail(CWT_EINVAL, "nrows must be in [1, max_rows]");
+  if (ncols < 1 || ldw < ncols) return fail(CWT_EINVAL, "need ncols >= 1 and ldw >= ncols");
+  if (mode < 0 || mode > 2) return fail(CWT_EINVAL, "mode must be 0 (hard), 1 (soft) or 2 (garrote)");
+  std::vector<double> w(nrows);
+  for (int j = 0; j < nrows; ++j) {
+    if (!(scales[j] > 0)) return fail(CWT_EINVAL, "scales must be positive");
+    w[j] = 1.0 / std::sqrt(scales[j]);
+  }
+  HIPCHECK(hipSetDevice(p->device));
+  return by_precision(p, [&](auto t) {
+    return icwt_shrink_impl<decltype(t)>(p, W_dev, ldw, ncols, nrows, w.data(), lambda_dev, mode, coeff, out_dev);
+  });
+}
+
+int cwt_row_order_statistics(cwt_plan* p, const void* A_dev, int is_complex, int64_t ld, int64_t ncols, int nrows,
+                             const int64_t* ranks, int nranks, void* out_dev, int64_t ldo) {
+  if (!p || !A_dev || !ranks || !out_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (is_complex != 0 && is_complex != 1) return fail(CWT_EINVAL, "is_complex must be 0 or 1");
+  if (nrows < 1 || ncols < 1 || ld < ncols) return fail(CWT_EINVAL, "need nrows >= 1, ncols >= 1 and ld >= ncols");
+  if (nranks < 1 || nranks > SEL_MAX_RANKS) return fail(CWT_EINVAL, "nranks must be in [1, 8]");
+  if (ldo < nranks) return fail(CWT_EINVAL, "need ldo >= nranks");
+  for (int i = 0; i < nranks; ++i)
+    if (ranks[i] < 0 || ranks[i] >= ncols) return fail(CWT_EINVAL, "ranks must be in [0, ncols)");
+  HIPCHECK(hipSetDevice(p->device));
+  return by_precision(p, [&](auto t) {
+    return order_statistics_impl<decltype(t)>(p, A_dev, is_complex, ld, ncols, nrows, ranks, nranks, out_dev, ldo);
+  });
 }
 
 int cwt_time_mean_power(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols, int nrows, void* out_dev) {

@@ -859,3 +859,5 @@ k_pass_b_ct(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
 #include "cwt_kernels_pool.hpp"      // time-pooled scalogram: window means of |W|^2 (polynomial rows in the kernel, the others from scratch)
 #include "cwt_kernels_ssq.hpp"       // synchrosqueezed transform: spectrum of the derivative signal, reassignment of W along frequency
 #include "cwt_kernels_ssq_grad.hpp"  // gradient of the synchrosqueezed transform: reassignment that records the bins, gather through them
+#include "cwt_kernels_select.hpp"    // exact order statistics of every row: radix select on the keys of the values
+#include "cwt_kernels_shrink.hpp"    // thresholded inverse transform: k_icwt over hard / soft / garrote shrunk coefficients

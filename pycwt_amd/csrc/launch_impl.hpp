@@ -1565,6 +1565,72 @@ int ssq_gather_impl(cwt_plan* p, const void* gT_dev, int64_t ldt, int nf, const 
   }, p->stream);
 }
 
+// ---- exact row order statistics (cwt_row_order_statistics; kernels: cwt_kernels_select.hpp) -------------------------------------
+// Slabs of rows whose states, histograms and candidate buffers fit kSelectScratchBytes of plan scratch (and one launch: 32768
+// rows); per slab sel_init and then the rounds of sel_hist + sel_pick, all queued at once: a round whose ranks are all DONE costs
+// two empty launches.  A row is cut into pieces of about 16384 columns, smaller where there are too few rows to fill the card.
+constexpr size_t kSelectScratchBytes = size_t(64) << 20;
+
+template <typename T>
+int order_statistics_impl(cwt_plan* p, const void* A_dev, int is_complex, int64_t ld, int64_t ncols, int nrows, const int64_t* ranks,
+                          int nranks, void* out_dev, int64_t ldo) {
+  typedef typename sel_traits<T>::key K;
+  const size_t per_rank = sizeof(SelState) + SEL_BINS * sizeof(unsigned) + SEL_CAP * sizeof(K);
+  const int slab = int(std::max<size_t>(1, std::min<size_t>(size_t(std::min(nrows, kMaxGridY)), kSelectScratchBytes / (per_rank * size_t(nranks)))));
+  const size_t n_states = size_t(slab) * size_t(nranks);
+  const size_t state_bytes = (n_states * sizeof(SelState) + 255) / 256 * 256, hist_bytes = n_states * SEL_BINS * sizeof(unsigned);
+  int rc = grow(&p->sel, &p->sel_bytes, state_bytes + hist_bytes + n_states * SEL_CAP * sizeof(K), p->stream);
+  if (rc) return rc;
+  SelState* st = static_cast<SelState*>(p->sel);
+  unsigned* hist = reinterpret_cast<unsigned*>(static_cast<char*>(p->sel) + state_bytes);
+  K* cbuf = reinterpret_cast<K*>(static_cast<char*>(p->sel) + state_bytes + hist_bytes);
+  SelRanks rk{};
+  for (int i = 0; i < nranks; ++i) rk.r[i] = ranks[i];
+  const bool counting = ncols > SEL_CAP;
+  const int rounds = counting ? sel_rounds<T>() : 1;
+  const size_t esz = (is_complex ? 2 : 1) * sizeof(T);
+  for (int r0 = 0; r0 < nrows; r0 += slab) {
+    const int cnt = std::min(slab, nrows - r0);
+    int64_t pieces = (ncols + 16383) / 16384;
+    if (pieces * cnt < 1024) pieces = std::min<int64_t>((ncols + 2047) / 2048, (1024 + cnt - 1) / cnt);
+    pieces = std::max<int64_t>(1, std::min<int64_t>(pieces, 65535));
+    const char* A = static_cast<const char*>(A_dev) + size_t(r0) * size_t(ld) * esz;
+    T* out = static_cast<T*>(out_dev) + size_t(r0) * size_t(ldo);
+    if (counting) HIPCHECK(hipMemsetAsync(hist, 0, size_t(cnt) * size_t(nranks) * SEL_BINS * sizeof(unsigned), p->stream));
+    rc = timed_launch(p, KC_SELECT, [&] {
+      hipLaunchKernelGGL((sel_init<T>), dim3(unsigned((cnt * nranks + 255) / 256)), dim3(256), 0, p->stream, st, cnt, nranks, rk, long(ncols));
+      for (int round = 0; round < rounds; ++round) {
+        const dim3 grid{unsigned(pieces), unsigned(cnt)};
+        const size_t lds = counting ? size_t(nranks) * SEL_BINS * sizeof(unsigned) : 0;
+        if (is_complex)
+          hipLaunchKernelGGL((sel_hist<T, true>), grid, dim3(SEL_THREADS), lds, p->stream, static_cast<const void*>(A), long(ld), long(ncols),
+                             nranks, st, hist, cbuf);
+        else
+          hipLaunchKernelGGL((sel_hist<T, false>), grid, dim3(SEL_THREADS), lds, p->stream, static_cast<const void*>(A), long(ld), long(ncols),
+                             nranks, st, hist, cbuf);
+        hipLaunchKernelGGL((sel_pick<T>), dim3(unsigned(cnt)), dim3(SEL_THREADS), sel_pick_lds<T>(), p->stream, nranks, st, hist,
+                           static_cast<const K*>(cbuf), out, long(ldo));
+      }
+    }, p->stream);
+    if (rc) return rc;
+  }
+  return CWT_OK;
+}
+
+// ---- thresholded inverse (cwt_icwt_shrink; kernel: cwt_kernels_shrink.hpp): reduce_scales_impl's launch with the thresholds -----
+template <typename T>
+int icwt_shrink_impl(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols, int nrows, const double* weights,
+                     const void* lambda_dev, int mode, double coeff, void* out_dev) {
+  int rc = upload_reals<T>(p, weights, nrows);
+  if (rc) return rc;
+  const unsigned blocks = unsigned((ncols + ICWT_THREADS - 1) / ICWT_THREADS);
+  return timed_launch(p, KC_SHRINK, [&] {
+    hipLaunchKernelGGL((shrink_icwt<T>), dim3(blocks), dim3(ICWT_THREADS), 0, p->stream, static_cast<const cplx<T>*>(W_dev), long(ldw),
+                       long(ncols), nrows, static_cast<const T*>(p->weights_dev), static_cast<const T*>(lambda_dev), mode, T(coeff),
+                       static_cast<T*>(out_dev));
+  }, p->stream);
+}
+
 // Chirp-kernel spectra for length n0 on this plan (N = M >= 2 n0 - 1), cached per n0.
 template <typename T>
 int bluestein_prepare(cwt_plan* p, int64_t n0) {
@@ -1718,6 +1784,8 @@ int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g
   X int ssq_reassign_impl<T>(cwt_plan*, const void*, const void*, int64_t, int64_t, int, const double*, double, double, double,     \
                              int, void*, int64_t, int, void*, int64_t);                                                             \
   X int ssq_gather_impl<T>(cwt_plan*, const void*, int64_t, int, const void*, int64_t, const double*, int, int64_t, void*, int64_t); \
+  X int order_statistics_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int, const int64_t*, int, void*, int64_t);          \
+  X int icwt_shrink_impl<T>(cwt_plan*, const void*, int64_t, int64_t, int, const double*, const void*, int, double, void*);         \
   X int random_normal_impl<T>(cwt_plan*, uint64_t, uint64_t, int64_t, double, void*);                                             \
   X int ar1_filter_impl<T>(cwt_plan*, const void*, int64_t, int64_t, double, void*);                                               \
   X int forward_fft_n_impl<T>(cwt_plan*, const void*, int64_t, void*);                                                              \

@@ -18,7 +18,7 @@ const char* const kClassNames[KC_COUNT] = {"fwd_small", "fwd_pass_a",  "fwd_pass
                                            "narrow_many", "narrow_big", "pass_a",     "pass_b", "icwt",   "elementwise",
                                            "ols_fwd", "ols", "ols_small", "aols_pre", "aols", "poly_coef", "poly",
                                            "adjoint", "hop_fold", "hop_rows", "sgrad", "pool_poly", "pool_rows",
-                                           "ssq_deriv", "ssq_zero", "ssq_reassign", "ssq_gather"};
+                                           "ssq_deriv", "ssq_zero", "ssq_reassign", "ssq_gather", "select", "icwt_shrink"};
 
 int ilog2(int64_t v) {
   int l = 0;

@@ -507,6 +507,44 @@ class _DeviceResult:
         finally:
             out.free()
 
+    def _row_quantiles(self, is_complex, q, columns):
+        """Exact quantiles of every row of the matrix (a complex one: of the modulus, the root of v = fma(re, re, im im) of an
+        entry) over the columns [a, b): NumPy's method="lower" (the order statistic floor(q (n - 1))), except q = 0.5 on an even
+        count, which is the mean of the two middle order statistics -- np.median.  rows x len(q) float64; the selection runs
+        on the device (cwt_row_order_statistics), at most 8 ranks per call."""
+        rows, ncols = self.shape
+        a, b = (0, ncols) if columns is None else (int(columns[0]), int(columns[1]))
+        if not 0 <= a < b <= ncols:
+            raise ValueError(f"columns must be (a, b) with 0 <= a < b <= {ncols}; got {columns!r}")
+        q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+        if q.ndim != 1 or not np.all((q >= 0) & (q <= 1)):
+            raise ValueError("q must be a number or a 1-D sequence of numbers in [0, 1]")
+        n = b - a
+        lo = np.floor(q * (n - 1)).astype(np.int64)
+        hi = np.where((q == 0.5) & (n % 2 == 0), lo + 1, lo)
+        ranks = np.unique(np.concatenate([lo, hi]))
+        es = np.dtype(self._plan.real).itemsize
+        first = self._buf.ptr + a * es * (2 if is_complex else 1)
+        stats = np.empty((rows, ranks.size), dtype=np.float64)
+        out = _hip.DeviceBuffer(rows * 8 * es, self._plan.device)
+        try:
+            with self._plan.lock:
+                for i in range(0, ranks.size, 8):
+                    part = ranks[i:i + 8]
+                    self._plan.row_order_statistics(first, is_complex, ncols, n, rows, part, out.ptr, 8)
+                    stats[:, i:i + part.size] = out.download(self._plan, (rows, 8), self._plan.real)[:, :part.size]
+        finally:
+            out.free()
+        if is_complex:
+            stats = np.sqrt(stats)           # the order statistics of |W| are the roots of those of |W|^2
+        at = {int(r): i for i, r in enumerate(ranks)}
+        with np.errstate(invalid="ignore"):
+            return np.stack([0.5 * (stats[:, at[int(l)]] + stats[:, at[int(h)]]) if h != l else stats[:, at[int(l)]]
+                             for l, h in zip(lo, hi)], axis=1)
+
+
+SHRINK_MODES = ("hard", "soft", "garrote")
+
 
 class DeviceTransform(_DeviceResult):
     """A wavelet transform that stays on the GPU: W (rows x n0 complex) is device
@@ -533,6 +571,41 @@ class DeviceTransform(_DeviceResult):
         """TC98 eq. 11 without leaving the device (wavelet.py:169-170)."""
         rows, n0 = self.shape
         total = self._vector(n0, lambda p: self._plan.icwt_reduce(self._buf.ptr, n0, n0, self.sj, 1.0, p))
+        return dj * np.sqrt(self.dt) / (self.mother.cdelta * self.mother.psi(0)) * total
+
+    def row_quantiles(self, q, columns=None):
+        """Exact quantiles of |W| per scale, rows x len(q) float64: the square roots of the order statistics of v = fma(re, re,
+        im im) (the plan's precision), which the device selects exactly.  `q` in [0, 1] with NumPy's method="lower"; q = 0.5
+        on an even count is the mean of the two middle moduli: np.median of sqrt(v).  columns=(a, b): over the columns [a, b)."""
+        return self._row_quantiles(True, q, columns)
+
+    def noise_levels(self, columns=None):
+        """The noise level of every scale from the median of |W_j| over time (over `columns` = (a, b) if given): sigma_j =
+        median_n |W_j| / c.  Where W of a real signal is complex (Morlet, Paul), W_j of white Gaussian noise is a circular
+        Gaussian, its modulus is Rayleigh with median sqrt(ln 4) times the standard deviation of one component: c = sqrt(ln 4).
+        Where W is real (DOG, MexicanHat), c = 0.6744897501960817, the median of |N(0, 1)|.  Decided by the mother's class, not
+        by looking at the data."""
+        c = 0.6744897501960817 if isinstance(self.mother, DOG) else float(np.sqrt(np.log(4.0)))
+        return self.row_quantiles(0.5, columns)[:, 0] / c
+
+    def icwt_shrink(self, dj, lam, mode="soft"):
+        """`icwt` of the shrunk coefficients without leaving the device (cwt_icwt_shrink): `lam`, a number or one per scale
+        (>= 0), is the threshold on |W_j|; mode "hard" (keep |W| > lam), "soft" (W (1 - lam / |W|)+) or "garrote"
+        (W (1 - lam^2 / |W|^2)+).  The factor dj sqrt(dt) / (cdelta psi(0)) is `icwt`'s."""
+        rows, ncols = self.shape
+        if ncols != self.n0:
+            raise ValueError("icwt_shrink needs every column of W: this result is decimated (hop=)")
+        if mode not in SHRINK_MODES:
+            raise ValueError(f"mode must be one of {SHRINK_MODES}; got {mode!r}")
+        lam = np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=np.float64), (rows,)), dtype=self._plan.real)
+        lam_dev = _hip.DeviceBuffer(max(lam.nbytes, 16), self._plan.device)
+        try:
+            def fill(p):
+                lam_dev.upload(self._plan, lam)
+                self._plan.icwt_shrink(self._buf.ptr, ncols, ncols, self.sj, lam_dev.ptr, mode, 1.0, p)
+            total = self._vector(ncols, fill)
+        finally:
+            lam_dev.free()
         return dj * np.sqrt(self.dt) / (self.mother.cdelta * self.mother.psi(0)) * total
 
 
@@ -583,6 +656,48 @@ def cwt_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None,
         v.flags.writeable = False
         return v
     return DeviceTransform(plan, Wd, ro(sj), ro(freqs), ro(coi), None, ro(fftfreqs), mother, dt, n0, spectrum=xh, ncols=ncols)
+
+
+# ---- wavelet shrinkage ------------------------------------------------------------------------------------------------------------
+def denoise(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, mode="soft", threshold="universal", scale=1.0,
+            noise_columns=None, precision=None, device=0):
+    """Wavelet shrinkage denoising on the device: `cwt_device`, the noise level of every scale (`noise_levels`), the thresholded
+    reconstruction (`icwt_shrink`).  Returns ``(y, lam, sj, freqs, coi)``: the denoised series (the dtype of `icwt`'s result),
+    the thresholds used (one per scale, on |W_j|) and the grids of `cwt`.  The signal goes up; y, the per-scale medians and lam
+    (one number per scale each) are all that moves otherwise: W never leaves the GPU.
+
+    threshold="universal": lam_j = scale * sigma_j * sqrt(2 ln n0) with sigma_j = `noise_levels(noise_columns)` -- from the
+    columns noise_columns=(a, b) when given (a stretch known to hold noise only, the pre-event window of seismic practice), else
+    from all n0 columns.  A number or one number per scale: lam itself (`scale` does not apply, no selection runs).
+    mode: "soft" | "hard" | "garrote".
+
+    Built-in mothers, a real 1-D signal; the transform is zero padded to a power of two as in `cwt`.  The mean of the signal is
+    not restored: the CWT has no DC row, so y reconstructs the signal minus its mean.  Paul reconstructs with the amplitude
+    of the reference's `icwt`, whose psi(0) keeps the reference's (m - 2)! factor."""
+    mother = _check_parameter_wavelet(wavelet)
+    try:
+        _device_id(mother)
+    except NotImplementedError:
+        raise NotImplementedError(
+            "pycwt_amd.denoise needs a built-in mother (Morlet, Paul, DOG, MexicanHat from pycwt_amd); "
+            f"got {type(mother).__name__} without device_id()") from None
+    x = np.asarray(signal)
+    if x.ndim != 1 or np.iscomplexobj(x):
+        raise ValueError(f"pycwt_amd.denoise needs a real 1-D signal; got shape {x.shape}, dtype {x.dtype}")
+    if mode not in SHRINK_MODES:
+        raise ValueError(f"mode must be one of {SHRINK_MODES}; got {mode!r}")
+    if isinstance(threshold, str) and threshold != "universal":
+        raise ValueError(f'threshold must be "universal", a number or one number per scale; got {threshold!r}')
+    D = cwt_device(x, dt, dj, s0, J, mother, freqs, precision=precision, device=device)
+    try:
+        if isinstance(threshold, str):
+            lam = float(scale) * D.noise_levels(noise_columns) * np.sqrt(2.0 * np.log(x.size))
+        else:
+            lam = np.array(np.broadcast_to(np.asarray(threshold, dtype=np.float64), D.sj.shape))
+        y = D.icwt_shrink(dj, lam, mode)
+        return y, lam, np.array(D.sj), np.array(D.freqs), np.array(D.coi)
+    finally:
+        D.close()
 
 
 # ---- synchrosqueezed transform ---------------------------------------------------------------------------------------------------
@@ -970,6 +1085,12 @@ class DevicePower(_DeviceResult):
         w = np.where((self.sj >= s1) & (self.sj < s2), 1.0 / self.sj, 0.0)
         coeff = dj * self.dt / self.mother.cdelta
         return self._vector(n0, lambda p: self._plan.reduce_scales(self._buf.ptr, n0, n0, w, 2, coeff, p))
+
+    def row_quantiles(self, q, columns=None):
+        """Exact quantiles of the power per scale, rows x len(q) float64, selected on the device: `q` in [0, 1] with NumPy's
+        method="lower"; q = 0.5 on an even count is np.median (the mean of the two middle values).  columns=(a, b): over the
+        columns [a, b).  Median normalisation and percentile clipping of a scalogram start here."""
+        return self._row_quantiles(False, q, columns)
 
 
 def cwt_power_device(signal, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, precision=None, device=0, hop=None,
