@@ -617,6 +617,32 @@ int cwt_row_order_statistics(cwt_plan* plan, const void* A_dev, int is_complex, 
 int cwt_icwt_shrink(cwt_plan* plan, const void* W_dev, int64_t ldw, int64_t ncols, int nrows, const double* scales_host,
                     const void* lambda_dev, int mode, double coeff, void* out_dev);
 
+/* ---- gradient of the thresholded inverse ------------------------------------------------------------------------------------------
+ * cwt_icwt_shrink_adjoint: the vector-Jacobian product of cwt_icwt_shrink for the real cotangent gy_dev (ncols reals of T) of its
+ * output.  With W = a + ib, v = fma(a, a, b * b), l2 = lambda * lambda, r = sqrt(v) and t = (coeff / sqrt(scales[j])) * gy[n]:
+ *     G[j, n]    = dL/dRe W[j, n] + i dL/dIm W[j, n]   (the convention of cwt_adjoint_rows, whose input G is)
+ *     glambda[j] = sum_n dL/dlambda_j at entry (j, n)
+ *     mode 0 (hard)     kept when v > l2:              G = t,                                   dlambda = 0
+ *     mode 1 (soft)     kept when f = 1 - lambda/r > 0: G = t (f + lambda a^2/r^3 + i lambda a b/r^3),   dlambda = -t a/r
+ *     mode 2 (garrote)  kept when f = 1 - l2/v > 0:     G = t (f + 2 l2 a^2/v^2 + i 2 l2 a b/v^2),       dlambda = -2 t lambda a/v
+ * A dropped entry, and v = 0, give 0.  "Kept" is the predicate of cwt_icwt_shrink on the same rounded v, lambda/r and l2/v -- an
+ * entry exactly on its threshold is dropped --, so this is the gradient of what the forward computed; at the kink the one-sided
+ * value of the dropped side is taken.  An entry with a NaN component or a NaN lambda gives NaN in its G and its row's glambda; a NaN
+ * gy[n] gives NaN in column n of G and in every glambda; lambda = +inf gives zeros.  In mode 0 the imaginary part is +0.
+ * lambda_dev == NULL: the plain inverse, G = t + 0i, the adjoint of cwt_icwt_reduce (W is not read, mode is only range-checked).
+ * G_dev: nrows x ldg complex; it MAY be W_dev (ldg = ldw): an element is read and then written by the same thread, so the backward
+ * of a shrinkage layer needs one rows x ncols buffer.  Columns ncols .. ld - 1 of W and G are never read or written.
+ * glambda_dev: nrows DOUBLES on the device for either precision, or NULL (no reduction runs); accumulate != 0 adds to what is
+ * there (a batch: the signals in the order of the calls).  The sum of a row is formed in one fixed order -- a thread its 8 columns
+ * ascending, the 256 threads of a slice of 2048 columns in a binary tree, the slices ascending in double; no atomics --, so the
+ * bits of glambda[j] and of row j of G depend on ncols and the row's data alone, not on nrows or on how the rows are split over
+ * calls.  Work space (nrows x ceil(ncols / 2048) reals) from plan scratch; queued on the plan's stream without host
+ * synchronisation.  Refused with CWT_EINVAL before anything is queued: what cwt_icwt_shrink refuses (W_dev NULL included, also
+ * with lambda_dev NULL), a NULL gy_dev or G_dev, ldg < ncols, glambda_dev given with lambda_dev NULL.                              */
+int cwt_icwt_shrink_adjoint(cwt_plan* plan, const void* W_dev, int64_t ldw, int64_t ncols, int nrows, const double* scales_host,
+                            const void* lambda_dev, int mode, double coeff, const void* gy_dev, void* G_dev, int64_t ldg,
+                            double* glambda_dev, int accumulate);
+
 /* Weighted reduction over scales with explicit weights:
  *   out[n] = coeff * sum_j g(W[j, n]) * weights[j],  g = Re (power = 0) or |.|^2 (power = 1).
  * power = 1 with weights 1/s_j on the selected scales (0 elsewhere) and coeff = dj*dt/cdelta is the

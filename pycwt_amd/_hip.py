@@ -95,6 +95,8 @@ SYMBOLS = [
     ("cwt_ssq_gather", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, C.c_int64, C.POINTER(C.c_double), C.c_int, C.c_int64, _P, C.c_int64]),
     ("cwt_row_order_statistics", C.c_int, [_P, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.c_int, _P, C.c_int64]),
     ("cwt_icwt_shrink", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), _P, C.c_int, C.c_double, _P]),
+    ("cwt_icwt_shrink_adjoint", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double), _P, C.c_int, C.c_double, _P, _P,
+                                          C.c_int64, _P, C.c_int]),
     ("cwt_time_mean_power", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
     ("cwt_time_mean_real", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, _P]),
     ("cwt_coherence_histogram", C.c_int, [_P, _P, C.c_int64, C.c_int, _P, _P, C.c_int64, C.c_int, _P]),
@@ -672,6 +674,17 @@ class Plan:
         s = np.ascontiguousarray(scales, dtype=np.float64)
         self.lib.check(self.lib.cwt_icwt_shrink(self.h, _P(W_dev), ldw, ncols, s.size, _dptr(s), _P(lambda_dev),
                                                 int(self.SHRINK_MODES.get(mode, mode)), float(coeff), _P(out_dev)))
+
+    @_locked
+    def icwt_shrink_adjoint(self, W_dev: int, ldw: int, ncols: int, scales, lambda_dev, mode, coeff: float, gy_dev: int, G_dev: int,
+                            ldg: int, glambda_dev=None, accumulate: bool = False):
+        """G = the cotangent of W, glambda (+)= the cotangent of the thresholds for the cotangent gy of cwt_icwt_shrink's output
+        (cwt_icwt_shrink_adjoint); lambda_dev None: the adjoint of icwt_reduce; G_dev may be W_dev; glambda_dev: one DOUBLE per
+        row on the device, or None."""
+        s = np.ascontiguousarray(scales, dtype=np.float64)
+        self.lib.check(self.lib.cwt_icwt_shrink_adjoint(self.h, _P(W_dev), ldw, ncols, s.size, _dptr(s), _P(lambda_dev),
+                                                        int(self.SHRINK_MODES.get(mode, mode)), float(coeff), _P(gy_dev), _P(G_dev), ldg,
+                                                        _P(glambda_dev), int(bool(accumulate))))
 
     @_locked
     def time_mean_power(self, W_dev: int, ldw: int, ncols: int, nrows: int, out_dev: int):

@@ -3,7 +3,9 @@ its backward through the HIP adjoint of the rows (``cwt_adjoint_rows``): dL/dx =
 dense filter bank and no activation saved but the geometry of the call.  With ``hop=h`` forward and backward work on every
 h-th column only (``cwt_transform_hop``, ``cwt_adjoint_rows_hop``): nothing of rows x n0 elements exists in either.  With
 ``scales=`` (a torch tensor) and, for Morlet, ``f0=`` the transform is differentiable in those too (``cwt_adjoint_rows_scales``:
-one reduction over each row's band on the spectra the adjoint forms anyway)."""
+one reduction over each row's band on the spectra the adjoint forms anyway).  The way back out of the wavelet domain is
+``icwt_torch`` / ``icwt_shrink_torch`` / ``denoise_torch``: the (thresholded) inverse and its HIP adjoint
+(``cwt_icwt_shrink_adjoint``), differentiable in W, in the thresholds and, for ``denoise_torch``, in x without a saved W."""
 import threading
 
 import numpy as np
@@ -295,7 +297,131 @@ def _function(torch):
             del G
             return xbar, None, None, None, None, None, None, None
 
-    return CwtRows, CwtPower, CwtRowsScales, CwtPowerScales, SsqRows
+    def shrink_inverse(eng, Wb, sj, lam_b, mode, out_b):
+        """out_b = sum_j Re eta(W[j]; lam[j]) / sqrt(s_j) of one signal (lam_b None: the plain inverse), coeff = 1"""
+        n0 = Wb.shape[-1]
+        if lam_b is None:
+            eng.plan.icwt_reduce(Wb.data_ptr(), n0, n0, sj, 1.0, out_b.data_ptr())
+        else:
+            eng.plan.icwt_shrink(Wb.data_ptr(), n0, n0, sj, lam_b.data_ptr(), mode, 1.0, out_b.data_ptr())
+
+    class IcwtShrink(torch.autograd.Function):
+        """sum_j Re eta(W[j, n]; lam_j) / sqrt(s_j) of W (B, rows, n0) and lam (B, rows) of W's precision, or None (the plain
+        inverse), signal by signal.  Saves W and lam; the backward is cwt_icwt_shrink_adjoint."""
+        @staticmethod
+        def forward(ctx, W, lam, eng, sj, mode):
+            real_t = torch.float64 if W.dtype == torch.complex128 else torch.float32
+            out = torch.empty((W.shape[0], W.shape[-1]), dtype=real_t, device=W.device)
+            _on_current_stream(torch, eng, W.device)
+            for b in range(W.shape[0]):
+                shrink_inverse(eng, W[b], sj, None if lam is None else lam[b], mode, out[b])
+            if lam is None:
+                ctx.shape = (tuple(W.shape), W.dtype, W.device)
+            else:
+                ctx.save_for_backward(W, lam)
+            ctx.geometry = (eng, sj, mode)
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gy):
+            eng, sj, mode = ctx.geometry
+            if ctx.saved_tensors:
+                W, lam = ctx.saved_tensors
+                shape, dtype, device = tuple(W.shape), W.dtype, W.device
+            else:
+                W, lam = None, None
+                shape, dtype, device = ctx.shape
+            real_t = torch.float64 if dtype == torch.complex128 else torch.float32
+            g = gy.to(real_t).contiguous()
+            n0 = shape[-1]
+            G = torch.empty(shape, dtype=dtype, device=device)
+            glam = None if lam is None else torch.empty(lam.shape, dtype=torch.float64, device=device)
+            _on_current_stream(torch, eng, device)
+            for b in range(shape[0]):
+                if lam is None:                                  # (W is not read: G stands in for the pointer)
+                    eng.plan.icwt_shrink_adjoint(G[b].data_ptr(), n0, n0, sj, None, 0, 1.0, g[b].data_ptr(), G[b].data_ptr(), n0)
+                else:
+                    eng.plan.icwt_shrink_adjoint(W[b].data_ptr(), n0, n0, sj, lam[b].data_ptr(), mode, 1.0, g[b].data_ptr(),
+                                                 G[b].data_ptr(), n0, glam[b].data_ptr())
+            return G, None if lam is None else glam.to(lam.dtype), None, None, None
+
+    class DenoiseRows(torch.autograd.Function):
+        """transform -> (noise level per scale) -> thresholded inverse of x (B, n0), signal by signal, with ONE rows x n0 buffer.
+        p (B, rows) float64: the thresholds, or (universal) the factor `scale` of lam = (scale sigma) sqrt(2 ln n0).  Returns
+        (the sum with coeff = 1, sigma (B, rows) float64 -- not differentiable; zeros without `universal`).  Saved: x, the
+        thresholds used (B, rows) and d lam / d scale -- not W."""
+        @staticmethod
+        def forward(ctx, x, p, eng, kind, param, dt, sj, mode, universal, columns, c, finite):
+            nb, n0 = x.shape
+            rows = sj.size
+            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+            out = torch.empty((nb, n0), dtype=x.dtype, device=x.device)
+            sigma = torch.zeros((nb, rows), dtype=torch.float64, device=x.device)
+            lam = torch.empty((nb, rows), dtype=x.dtype, device=x.device)
+            tol = _tolerance()
+            _on_current_stream(torch, eng, x.device)
+            eng.plan.set_tolerance(tol)
+            W = torch.empty((rows, n0), dtype=cplx_t, device=x.device)
+            K = float(np.sqrt(2.0 * np.log(n0)))
+            if universal:                                        # the ranks of the median over the columns [a, b), as row_quantiles
+                a, b = columns
+                lo = (b - a - 1) // 2
+                ranks = [lo, lo + 1] if (b - a) % 2 == 0 else [lo]
+                stats = torch.empty((rows, 8), dtype=x.dtype, device=x.device)
+                first = a * (16 if x.dtype == torch.float64 else 8)
+            for i in range(nb):
+                if not finite[i]:                                # a non-finite sample: every element of W is NaN
+                    out[i].fill_(float("nan"))
+                    sigma[i].fill_(float("nan"))
+                    lam[i].fill_(float("nan"))
+                    continue
+                eng.transform(x[i], n0, None, kind, param, dt, sj, W, n0)          # W as CwtRows.forward computes it
+                if universal:
+                    eng.plan.row_order_statistics(W.data_ptr() + first, True, n0, b - a, rows, ranks, stats.data_ptr(), 8)
+                    # the roots, the mean of the two middle ones and the division as `noise_levels` does them, in NumPy on the
+                    # host (rows x 2 numbers; one synchronisation per signal): the same bits as `denoise`, which a square root
+                    # of torch's need not give
+                    st = np.sqrt(stats[:, :len(ranks)].cpu().numpy().astype(np.float64))
+                    med = 0.5 * (st[:, 0] + st[:, 1]) if len(ranks) == 2 else st[:, 0]
+                    sigma[i] = torch.as_tensor(med / c, dtype=torch.float64).to(x.device)
+                    lam[i] = ((p[i] * sigma[i]) * K).to(x.dtype)
+                else:
+                    lam[i] = p[i].to(x.dtype)
+                shrink_inverse(eng, W, sj, lam[i], mode, out[i])
+            del W
+            ctx.save_for_backward(x, lam, sigma * K if universal else sigma)
+            ctx.geometry = (eng, kind, param, dt, sj, tol, mode, universal, finite)
+            ctx.mark_non_differentiable(sigma)
+            return out, sigma
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gy, _gsigma):
+            x, lam, dlam = ctx.saved_tensors
+            eng, kind, param, dt, sj, tol, mode, universal, finite = ctx.geometry
+            nb, n0 = x.shape
+            rows = sj.size
+            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+            g = gy.to(x.dtype).contiguous()
+            xbar = torch.empty((nb, n0), dtype=x.dtype, device=x.device)
+            glam = torch.empty((nb, rows), dtype=torch.float64, device=x.device)
+            _on_current_stream(torch, eng, x.device)
+            eng.plan.set_tolerance(tol)
+            G = torch.empty((rows, n0), dtype=cplx_t, device=x.device)       # W recomputed, then its cotangent in place
+            for i in range(nb):
+                if not finite[i]:
+                    xbar[i].fill_(float("nan"))
+                    glam[i].fill_(float("nan"))
+                    continue
+                eng.transform(x[i], n0, None, kind, param, dt, sj, G, n0)
+                eng.plan.icwt_shrink_adjoint(G.data_ptr(), n0, n0, sj, lam[i].data_ptr(), mode, 1.0, g[i].data_ptr(), G.data_ptr(), n0,
+                                             glam[i].data_ptr())
+                eng.plan.adjoint_rows(G.data_ptr(), 1, rows * n0, n0, n0, kind, param, dt, sj, xbar[i].data_ptr(), n0)
+            del G
+            return (xbar, glam * dlam if universal else glam) + (None,) * 10
+
+    return CwtRows, CwtPower, CwtRowsScales, CwtPowerScales, SsqRows, IcwtShrink, DenoiseRows
 
 
 _fn = None
@@ -514,6 +640,141 @@ def issq_cwt_torch(Tx, dt, dj=1 / 12, wavelet="morlet", *, ssq_freqs=None, band=
     total = (Tx.real * w[:, None]).sum(dim=-2)
     coeff = complex(dj * np.sqrt(dt) / (mother.cdelta * mother.psi(0)))
     return total * (coeff.real if coeff.imag == 0 else coeff)
+
+
+def _icwt_coeff(mother, dt, dj):
+    """dj sqrt(dt) / (cdelta psi(0)): a float where psi(0) is real, else complex"""
+    coeff = complex(dj * np.sqrt(dt) / (mother.cdelta * mother.psi(0)))
+    return coeff.real if coeff.imag == 0 else coeff
+
+
+def _shrink_prepare(name, W, sj, wavelet):
+    """The checks and the engine of `icwt_torch` / `icwt_shrink_torch`: (torch, engine, mother, sj, W as (B, rows, n0))."""
+    import torch
+    mother = _check_parameter_wavelet(wavelet)
+    if not hasattr(mother, "device_id"):
+        raise NotImplementedError(f"{name} needs a built-in mother (Morlet, Paul, DOG, MexicanHat); got {type(mother).__name__} "
+                                  "without device_id()")
+    if not torch.is_tensor(W) or W.dtype not in (torch.complex128, torch.complex64) or W.dim() not in (2, 3) or W.shape[-1] < 1:
+        raise ValueError(f"{name}: W must be a complex torch tensor of shape (rows, n0) or (B, rows, n0)")
+    sj = np.ascontiguousarray(sj, dtype=np.float64)
+    if sj.shape != (W.shape[-2],) or not (np.isfinite(sj).all() and (sj > 0).all()):
+        raise ValueError(f"{name}: sj must hold one positive scale per row of W")
+    lib = _hip.load()
+    if W.device.type != "cuda" and lib.backend().startswith("hip"):
+        raise RuntimeError(f"{name} needs a tensor on a GPU (the HIP kernels cannot read host memory)")
+    precision = 64 if W.dtype == torch.complex128 else 32
+    eng = _engine(torch, _next_pow2(int(W.shape[-1])), precision, sj.size, W.device, lib)
+    return torch, eng, mother, sj, (W if W.dim() == 3 else W[None]).contiguous()
+
+
+def _check_mode(name, mode):
+    from .wavelet import SHRINK_MODES
+    if mode not in SHRINK_MODES:
+        raise ValueError(f"{name}: mode must be one of {SHRINK_MODES}; got {mode!r}")
+    return mode
+
+
+def _rows_parameter(name, what, torch, t, nb, rows, batched, device):
+    """`t` of shape (), (rows,) or (B, rows) -> a (B, rows) view of it on `device` (torch's expand: autograd sums)"""
+    if not torch.is_tensor(t) or t.is_complex() or not t.is_floating_point():
+        raise ValueError(f"{name}: {what} must be a real floating-point torch tensor")
+    ok = t.dim() == 0 or tuple(t.shape) == (rows,) or (batched and tuple(t.shape) == (nb, rows))
+    if not ok:
+        raise ValueError(f"{name}: {what} must have shape (), ({rows},)" + (f" or ({nb}, {rows})" if batched else "")
+                         + f"; got {tuple(t.shape)}")
+    return t.to(device).expand(nb, rows)
+
+
+def icwt_torch(W, sj, dt, dj=1 / 12, wavelet="morlet"):
+    """Inverse wavelet transform of a torch tensor, differentiable with respect to it: ``icwt``'s series
+    ``dj sqrt(dt) / (cdelta psi(0)) sum_j Re W[j, n] / sqrt(s_j)`` for W complex128 / complex64 of shape (rows, n0) or
+    (B, rows, n0) on the device; (n0,) or (B, n0), real where the mother's psi(0) is.  The sum is ``cwt_icwt_reduce`` on torch's
+    current stream, the factor a torch operation; the backward is ``cwt_icwt_shrink_adjoint`` without thresholds
+    (G[j, n] = gy[n] / sqrt(s_j)): nothing is saved.  Built-in mothers; once differentiable."""
+    global _fn
+    torch, eng, mother, sj, Wb = _shrink_prepare("icwt_torch", W, sj, wavelet)
+    if _fn is None:
+        _fn = _function(torch)
+    total = _fn[5].apply(Wb, None, eng, sj, 0)
+    return (total if W.dim() == 3 else total[0]) * _icwt_coeff(mother, dt, dj)
+
+
+def icwt_shrink_torch(W, sj, dt, lam, dj=1 / 12, wavelet="morlet", mode="soft"):
+    """``icwt_torch`` of the shrunk coefficients, differentiable with respect to W and to the thresholds: ``lam``, a real tensor
+    of shape (), (rows,) or (B, rows), is the threshold on |W_j|; mode "hard" (keep |W| > lam), "soft" (W (1 - lam / |W|)+) or
+    "garrote" (W (1 - lam^2 / |W|^2)+), the rules and roundings of ``cwt_icwt_shrink``.  The backward is
+    ``cwt_icwt_shrink_adjoint``: the gradient of what the forward computed -- an entry on its threshold counts as dropped, the
+    gradient with respect to lam is 0 in hard mode -- summed per row in one fixed order, in float64 across a row's slices.
+    W and lam are saved (time-frequency masking between ``cwt_torch`` and here keeps W anyway); ``denoise_torch`` is the
+    composition that does not.  Built-in mothers; once differentiable."""
+    global _fn
+    torch, eng, mother, sj, Wb = _shrink_prepare("icwt_shrink_torch", W, sj, wavelet)
+    mode = _check_mode("icwt_shrink_torch", mode)
+    real_t = torch.float64 if Wb.dtype == torch.complex128 else torch.float32
+    lam_b = _rows_parameter("icwt_shrink_torch", "lam", torch, lam, Wb.shape[0], sj.size, W.dim() == 3, Wb.device).to(real_t).contiguous()
+    if _fn is None:
+        _fn = _function(torch)
+    total = _fn[5].apply(Wb, lam_b, eng, sj, mode)
+    return (total if W.dim() == 3 else total[0]) * _icwt_coeff(mother, dt, dj)
+
+
+def denoise_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, mode="soft", threshold="universal", scale=1.0,
+                  noise_columns=None):
+    """Wavelet shrinkage of a torch tensor, differentiable with respect to it and to the thresholds: ``denoise`` as a layer.
+
+    x: (n0,) or (B, n0), float64 or float32, on a GPU (CPU tensors only under the CPU emulation of the library, as
+    ``cwt_torch``).  Returns ``(y, lam, sj, freqs, coi)``: y the denoised series on x's device, produced on torch's current
+    stream, with the values of ``denoise`` for the same arguments (the same kernels in the same order); lam the thresholds used,
+    a tensor (rows,) or (B, rows); sj, freqs, coi NumPy arrays as ``cwt`` returns them.
+
+    threshold="universal": lam_j = scale sigma_j sqrt(2 ln n0), sigma_j the noise level of ``DeviceTransform.noise_levels``
+    over ``noise_columns`` (all columns by default), selected on the device (``cwt_row_order_statistics``).  ``scale`` is a float
+    or a tensor of shape () or (rows,) -- learnable: its gradient is that of lam times sigma_j sqrt(2 ln n0).  THE NOISE LEVELS
+    ENTER AS CONSTANTS: the median is not differentiated, no gradient reaches x through sigma.  threshold=a tensor of shape (),
+    (rows,) or (B, rows): the thresholds themselves, learnable (``scale`` does not apply, no selection runs).
+
+    Between forward and backward the node holds x, the thresholds used (one per row and signal) and the geometry -- not W.  The
+    backward, signal by signal: W recomputed into one rows x n0 buffer, overwritten in place by its cotangent
+    (``cwt_icwt_shrink_adjoint``, which also sums the cotangent of the thresholds), ``cwt_adjoint_rows``, the buffer freed.  A
+    signal with a non-finite sample gives NaN in its y and in its gradients (one read-back of the flags per call).  Built-in
+    mothers, pad=True, no hop; the refusals of ``denoise``; once differentiable."""
+    global _fn
+    mode = _check_mode("denoise_torch", mode)
+    if isinstance(threshold, str) and threshold != "universal":
+        raise ValueError(f'denoise_torch: threshold must be "universal" or a tensor of thresholds; got {threshold!r}')
+    mother = _check_parameter_wavelet(wavelet)
+    if not hasattr(mother, "device_id"):
+        raise NotImplementedError("denoise_torch needs a built-in mother (Morlet, Paul, DOG, MexicanHat from pycwt_amd); "
+                                  f"got {type(mother).__name__} without device_id()")
+    torch, eng, kind, param, sj, freqs, coi, _ = _prepare("denoise_torch", x, dt, dj, s0, J, mother, freqs, True)
+    from .mothers import DOG
+    nb, n0, rows = (int(x.shape[0]) if x.dim() == 2 else 1), int(x.shape[-1]), sj.size
+    universal = isinstance(threshold, str)
+    columns = (0, n0)
+    if universal:
+        if noise_columns is not None:
+            columns = (int(noise_columns[0]), int(noise_columns[1]))
+            if not 0 <= columns[0] < columns[1] <= n0:
+                raise ValueError(f"columns must be (a, b) with 0 <= a < b <= {n0}; got {noise_columns!r}")
+        if not torch.is_tensor(scale):
+            scale = torch.tensor(float(scale), dtype=torch.float64)
+        if scale.dim() == 2:
+            raise ValueError("denoise_torch: scale must be a float or a tensor of shape () or (rows,)")
+        p = _rows_parameter("denoise_torch", "scale", torch, scale, nb, rows, False, x.device)
+    else:
+        p = _rows_parameter("denoise_torch", "threshold", torch, threshold, nb, rows, x.dim() == 2, x.device)
+    xs = x.reshape(nb, n0).contiguous()
+    finite = [bool(v) for v in torch.isfinite(xs.detach()).all(dim=1).cpu().numpy()]
+    c = 0.6744897501960817 if isinstance(mother, DOG) else float(np.sqrt(np.log(4.0)))
+    if _fn is None:
+        _fn = _function(torch)
+    total, sigma = _fn[6].apply(xs, p.to(torch.float64), eng, kind, param, float(dt), sj, mode, universal, columns, c, finite)
+    lam = (p.to(torch.float64) * sigma) * float(np.sqrt(2.0 * np.log(n0))) if universal else p
+    y = total * _icwt_coeff(mother, dt, dj)
+    if x.dim() == 1:
+        y, lam = y[0], lam[0]
+    return y, lam, sj, freqs, coi
 
 
 def _ssq_saved_bins(Tx):

@@ -366,7 +366,7 @@ int cwt_plan_destroy(cwt_plan* p) {
   for (auto& t : p->timed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
   for (auto e : p->free_events) (void)hipEventDestroy(e);
   void* bufs[] = {p->tw_all, p->twn_lo, p->weights_dev, p->Z, p->xs, p->xm, p->xsa, p->pcoef, p->pband, p->range_dev, p->hx, p->hxhat, p->hW,
-                  p->bs_khat[0], p->bs_khat[1], p->bs_a, p->bs_spec, p->bs_par, p->adj_spec, p->adj_acc, p->hop_z, p->sgrad_part, p->pool_s, p->sel};
+                  p->bs_khat[0], p->bs_khat[1], p->bs_a, p->bs_spec, p->bs_par, p->adj_spec, p->adj_acc, p->hop_z, p->sgrad_part, p->pool_s, p->sel, p->shgrad_part};
   for (void* b : bufs) if (b) (void)hipFree(b);
   for (auto& t : p->slots) {
     if (t.gt_dev) (void)hipFree(t.gt_dev);
@@ -1073,6 +1073,26 @@ int cwt_icwt_shrink(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols, 
   HIPCHECK(hipSetDevice(p->device));
   return by_precision(p, [&](auto t) {
     return icwt_shrink_impl<decltype(t)>(p, W_dev, ldw, ncols, nrows, w.data(), lambda_dev, mode, coeff, out_dev);
+  });
+}
+
+int cwt_icwt_shrink_adjoint(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols, int nrows, const double* scales,
+                            const void* lambda_dev, int mode, double coeff, const void* gy_dev, void* G_dev, int64_t ldg,
+                            double* glambda_dev, int accumulate) {
+  if (!p || !W_dev || !scales || !gy_dev || !G_dev) return fail(CWT_EINVAL, "NULL argument");
+  if (nrows < 1 || nrows > p->max_rows) return fail(CWT_EINVAL, "nrows must be in [1, max_rows]");
+  if (ncols < 1 || ldw < ncols || ldg < ncols) return fail(CWT_EINVAL, "need ncols >= 1, ldw >= ncols and ldg >= ncols");
+  if (mode < 0 || mode > 2) return fail(CWT_EINVAL, "mode must be 0 (hard), 1 (soft) or 2 (garrote)");
+  if (glambda_dev && !lambda_dev) return fail(CWT_EINVAL, "glambda_dev needs lambda_dev");
+  std::vector<double> w(nrows);
+  for (int j = 0; j < nrows; ++j) {
+    if (!(scales[j] > 0)) return fail(CWT_EINVAL, "scales must be positive");
+    w[j] = 1.0 / std::sqrt(scales[j]);
+  }
+  HIPCHECK(hipSetDevice(p->device));
+  return by_precision(p, [&](auto t) {
+    return icwt_shrink_adjoint_impl<decltype(t)>(p, W_dev, ldw, ncols, nrows, w.data(), lambda_dev, mode, coeff, gy_dev, G_dev, ldg,
+                                                 glambda_dev, accumulate);
   });
 }
 

@@ -861,3 +861,4 @@ k_pass_b_ct(const cplx<T>* __restrict__ Z, const RowDesc* __restrict__ rows,
 #include "cwt_kernels_ssq_grad.hpp"  // gradient of the synchrosqueezed transform: reassignment that records the bins, gather through them
 #include "cwt_kernels_select.hpp"    // exact order statistics of every row: radix select on the keys of the values
 #include "cwt_kernels_shrink.hpp"    // thresholded inverse transform: k_icwt over hard / soft / garrote shrunk coefficients
+#include "cwt_kernels_shrink_grad.hpp"  // its vector-Jacobian product: the cotangent of W and of the thresholds

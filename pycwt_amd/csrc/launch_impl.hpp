@@ -1631,6 +1631,60 @@ int icwt_shrink_impl(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols,
   }, p->stream);
 }
 
+// ---- adjoint of the thresholded inverse (cwt_icwt_shrink_adjoint; kernels: cwt_kernels_shrink_grad.hpp) --------------------------
+// One launch of shgrad_rows per slab of kMaxGridY rows; with glambda the slice sums go to plan scratch (nrows x slices reals) and
+// shgrad_sum adds them.  lambda_dev NULL: the plain inverse (mode -1, W is not read).
+template <typename T, int MODE>
+void launch_shgrad_rows(cwt_plan* p, const cplx<T>* W, int64_t ldw, int64_t ncols, int nrows, const T* lambda, T coeff, const T* gy,
+                        cplx<T>* G, int64_t ldg, long nslices, T* partial) {
+  for (int r0 = 0; r0 < nrows; r0 += kMaxGridY) {
+    const dim3 grid{unsigned(nslices), unsigned(std::min(kMaxGridY, nrows - r0))};
+    const cplx<T>* Wr = W ? W + size_t(r0) * size_t(ldw) : nullptr;
+    const T* lr = lambda ? lambda + r0 : nullptr;
+    const T* wr = static_cast<const T*>(p->weights_dev) + r0;
+    if constexpr (MODE >= 0) {
+      if (partial) {
+        hipLaunchKernelGGL((shgrad_rows<T, MODE, true>), grid, dim3(SHGRAD_THREADS), SHGRAD_THREADS * sizeof(T), p->stream, Wr, long(ldw),
+                           long(ncols), wr, lr, coeff, gy, G + size_t(r0) * size_t(ldg), long(ldg), nslices,
+                           partial + size_t(r0) * size_t(nslices));
+        continue;
+      }
+    }
+    hipLaunchKernelGGL((shgrad_rows<T, MODE, false>), grid, dim3(SHGRAD_THREADS), 0, p->stream, Wr, long(ldw), long(ncols), wr, lr, coeff,
+                       gy, G + size_t(r0) * size_t(ldg), long(ldg), nslices, static_cast<T*>(nullptr));
+  }
+}
+
+template <typename T>
+int icwt_shrink_adjoint_impl(cwt_plan* p, const void* W_dev, int64_t ldw, int64_t ncols, int nrows, const double* weights,
+                             const void* lambda_dev, int mode, double coeff, const void* gy_dev, void* G_dev, int64_t ldg,
+                             double* glambda_dev, int accumulate) {
+  int rc = upload_reals<T>(p, weights, nrows);
+  if (rc) return rc;
+  const long nslices = shgrad_slices(long(ncols));
+  T* partial = nullptr;
+  if (glambda_dev) {
+    rc = grow(&p->shgrad_part, &p->shgrad_part_bytes, size_t(nrows) * size_t(nslices) * sizeof(T), p->stream);
+    if (rc) return rc;
+    partial = static_cast<T*>(p->shgrad_part);
+  }
+  const cplx<T>* W = static_cast<const cplx<T>*>(W_dev);
+  const T* lambda = static_cast<const T*>(lambda_dev);
+  const T* gy = static_cast<const T*>(gy_dev);
+  cplx<T>* G = static_cast<cplx<T>*>(G_dev);
+  rc = timed_launch(p, KC_SHRINK_GRAD, [&] {
+    if (!lambda) launch_shgrad_rows<T, -1>(p, nullptr, ldw, ncols, nrows, nullptr, T(coeff), gy, G, ldg, nslices, nullptr);
+    else if (mode == 0) launch_shgrad_rows<T, 0>(p, W, ldw, ncols, nrows, lambda, T(coeff), gy, G, ldg, nslices, partial);
+    else if (mode == 1) launch_shgrad_rows<T, 1>(p, W, ldw, ncols, nrows, lambda, T(coeff), gy, G, ldg, nslices, partial);
+    else launch_shgrad_rows<T, 2>(p, W, ldw, ncols, nrows, lambda, T(coeff), gy, G, ldg, nslices, partial);
+  }, p->stream);
+  if (rc || !partial) return rc;
+  return timed_launch(p, KC_SHRINK_GRAD, [&] {
+    hipLaunchKernelGGL((shgrad_sum<T>), dim3(unsigned((nrows + SHGRAD_THREADS - 1) / SHGRAD_THREADS)), dim3(SHGRAD_THREADS), 0, p->stream,
+                       static_cast<const T*>(partial), nrows, nslices, accumulate, glambda_dev);
+  }, p->stream);
+}
+
 // Chirp-kernel spectra for length n0 on this plan (N = M >= 2 n0 - 1), cached per n0.
 template <typename T>
 int bluestein_prepare(cwt_plan* p, int64_t n0) {
@@ -1786,6 +1840,8 @@ int ar1_filter_impl(cwt_plan* p, const void* e, int64_t tau, int64_t n, double g
   X int ssq_gather_impl<T>(cwt_plan*, const void*, int64_t, int, const void*, int64_t, const double*, int, int64_t, void*, int64_t); \
   X int order_statistics_impl<T>(cwt_plan*, const void*, int, int64_t, int64_t, int, const int64_t*, int, void*, int64_t);          \
   X int icwt_shrink_impl<T>(cwt_plan*, const void*, int64_t, int64_t, int, const double*, const void*, int, double, void*);         \
+  X int icwt_shrink_adjoint_impl<T>(cwt_plan*, const void*, int64_t, int64_t, int, const double*, const void*, int, double,        \
+                                    const void*, void*, int64_t, double*, int);                                                     \
   X int random_normal_impl<T>(cwt_plan*, uint64_t, uint64_t, int64_t, double, void*);                                             \
   X int ar1_filter_impl<T>(cwt_plan*, const void*, int64_t, int64_t, double, void*);                                               \
   X int forward_fft_n_impl<T>(cwt_plan*, const void*, int64_t, void*);                                                              \

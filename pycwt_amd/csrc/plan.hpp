@@ -47,7 +47,7 @@ int fail(int code, const std::string& msg);
 enum KernelClass { KC_FWD_SMALL, KC_FWD_A, KC_FWD_B, KC_SMALL, KC_DIRECT, KC_NARROW, KC_NARROW_MANY, KC_NARROW_BIG,
                    KC_PASS_A, KC_PASS_B, KC_ICWT, KC_ELEMENTWISE, KC_OLS_FWD, KC_OLS, KC_OLS_SMALL, KC_AOLS_PRE, KC_AOLS,
                    KC_POLY_COEF, KC_POLY, KC_ADJOINT, KC_HOP_FOLD, KC_HOP_ROWS, KC_SGRAD, KC_POOL_POLY, KC_POOL_ROWS,
-                   KC_SSQ_DERIV, KC_SSQ_ZERO, KC_SSQ, KC_SSQ_GATHER, KC_SELECT, KC_SHRINK, KC_COUNT };
+                   KC_SSQ_DERIV, KC_SSQ_ZERO, KC_SSQ, KC_SSQ_GATHER, KC_SELECT, KC_SHRINK, KC_SHRINK_GRAD, KC_COUNT };
 extern const char* const kClassNames[KC_COUNT];
 
 int ilog2(int64_t v);
@@ -186,6 +186,8 @@ struct cwt_plan {
   size_t sgrad_part_bytes = 0;
   void* sel = nullptr;      // cwt_row_order_statistics: per (row, rank) of a slab of rows the state, the digit histogram and the candidate keys
   size_t sel_bytes = 0;
+  void* shgrad_part = nullptr;  // cwt_icwt_shrink_adjoint: the slice sums of shgrad_rows (rows x slices reals)
+  size_t shgrad_part_bytes = 0;
   void* xm = nullptr;       // band-passed complex signal x_M of the k_aols rows (N complex)
   size_t xm_bytes = 0;
   void* xsa = nullptr;      // its block spectra (nblocks x (P + 8) complex)

@@ -18,7 +18,8 @@ const char* const kClassNames[KC_COUNT] = {"fwd_small", "fwd_pass_a",  "fwd_pass
                                            "narrow_many", "narrow_big", "pass_a",     "pass_b", "icwt",   "elementwise",
                                            "ols_fwd", "ols", "ols_small", "aols_pre", "aols", "poly_coef", "poly",
                                            "adjoint", "hop_fold", "hop_rows", "sgrad", "pool_poly", "pool_rows",
-                                           "ssq_deriv", "ssq_zero", "ssq_reassign", "ssq_gather", "select", "icwt_shrink"};
+                                           "ssq_deriv", "ssq_zero", "ssq_reassign", "ssq_gather", "select", "icwt_shrink",
+                                           "icwt_shrink_adjoint"};
 
 int ilog2(int64_t v) {
   int l = 0;
