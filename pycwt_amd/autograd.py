@@ -6,11 +6,15 @@ h-th column only (``cwt_transform_hop``, ``cwt_adjoint_rows_hop``): nothing of r
 one reduction over each row's band on the spectra the adjoint forms anyway).  The way back out of the wavelet domain is
 ``icwt_torch`` / ``icwt_shrink_torch`` / ``denoise_torch``: the (thresholded) inverse and its HIP adjoint
 (``cwt_icwt_shrink_adjoint``), differentiable in W, in the thresholds and, for ``denoise_torch``, in x without a saved W."""
+import functools
 import threading
+from collections import namedtuple
+from types import SimpleNamespace
 
 import numpy as np
 
 from . import _hip
+from . import wavelet as _wavelet
 from .parallel import HipEngine
 from .wavelet import (_band_weights, _check_hop, _check_pool, _pool_coi, _check_parameter_wavelet, _coi, _device_id, _geometry, _nan_rows,
                       _next_pow2, _ssq_grid, _ssq_mother)
@@ -43,16 +47,59 @@ def _on_current_stream(torch, eng, device):
 def _tolerance():
     """The module's accuracy target (pycwt_amd.set_tolerance) as a fixed tolerance: a float applies as it is; "auto" and None
     run at the engine's round-off default, 0 (the automatic mode reads the spectrum's range back to the host per call)."""
-    from . import wavelet
-    t = wavelet._tolerance
+    t = _wavelet._tolerance
     return float(t) if isinstance(t, (int, float)) and not isinstance(t, bool) and t else 0.0
 
 
-def _function(torch):
-    from torch.autograd.function import once_differentiable
+def _begin(torch, eng, device, tol):
+    """What every forward and backward of a transform starts with: the plan on torch's current stream, at this tolerance."""
+    _on_current_stream(torch, eng, device)
+    eng.plan.set_tolerance(tol)
 
-    def pooled_columns(n0, hop, pool):
-        return n0 if hop is None and pool is None else -(-n0 // (pool if pool is not None else hop))
+
+def _real_of(torch, dtype):
+    return torch.float64 if dtype in (torch.complex128, torch.float64) else torch.float32
+
+
+def _complex_of(torch, dtype):
+    return torch.complex128 if dtype in (torch.complex128, torch.float64) else torch.complex64
+
+
+# what a node of CwtRows / CwtPower holds of its call: the backward is the transpose of exactly this forward
+_Geometry = namedtuple("_Geometry", "eng kind param dt sj tol hop pool n0 keep scales f0")
+
+
+@functools.lru_cache(maxsize=None)
+def _functions():
+    """The autograd Functions by name, built on first use (importing this module does not import torch)."""
+    import torch
+    from torch.autograd.function import once_differentiable
+    OUT_W, OUT_POWER, OUT_WEIGHTED = _hip.Plan.OUT_W, _hip.Plan.OUT_POWER, _hip.Plan.OUT_WEIGHTED
+
+    def output_columns(g):
+        return g.n0 if g.hop is None and g.pool is None else -(-g.n0 // (g.pool if g.pool is not None else g.hop))
+
+    def run_forward(g, x, out, output, Q=None, alpha=0.0):
+        """The one engine call that transforms x into `out` under the geometry g: W, |W|^2 (its window means with g.pool) or
+        (alpha Q) W.  With g.hop on the kept columns; the weighted output is at the full rate whatever g.pool."""
+        n0 = x.shape[-1]
+        if g.hop is not None:
+            g.eng.transform_hop(x, n0, g.hop, output, g.kind, g.param, g.dt, g.sj, out, Q, alpha)
+        elif output == OUT_W:
+            g.eng.transform(x, n0, None, g.kind, g.param, g.dt, g.sj, out, n0)
+        elif output == OUT_WEIGHTED:
+            g.eng.transform_weighted(x, n0, None, g.kind, g.param, g.dt, g.sj, Q, alpha, out, n0)
+        elif g.pool is not None:
+            g.eng.transform_pool(x, n0, g.pool, g.kind, g.param, g.dt, g.sj, out)
+        else:
+            g.eng.transform_power(x, n0, None, g.kind, g.param, g.dt, g.sj, out, n0)
+
+    def run_adjoint(g, G, xbar):
+        """xbar = Re A^H G for the cotangent G of W under the geometry g (on the kept columns with g.hop)"""
+        if g.hop is None:
+            g.eng.adjoint_rows(G, g.n0, g.kind, g.param, g.dt, g.sj, xbar)
+        else:
+            g.eng.adjoint_rows_hop(G, g.n0, g.hop, g.kind, g.param, g.dt, g.sj, xbar)
 
     def spread_over_windows(q, n0, pool):
         """gP (..., rows, ceil(n0 / pool)) -> (..., rows, n0): gP[j, n // pool] / c_m, c_m the columns of window m inside n0"""
@@ -61,178 +108,85 @@ def _function(torch):
         count[-1] = float(n0 - (ncols - 1) * pool)
         return (q / count).repeat_interleave(pool, dim=-1)[..., :n0].contiguous()
 
-    class CwtRows(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, x, eng, kind, param, dt, sj, hop):
-            n0 = x.shape[-1]
-            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
-            W = torch.empty(tuple(x.shape[:-1]) + (sj.size, n0 if hop is None else -(-n0 // hop)), dtype=cplx_t, device=x.device)
-            tol = _tolerance()
-            _on_current_stream(torch, eng, x.device)
-            eng.plan.set_tolerance(tol)
-            if hop is None:
-                eng.transform(x, n0, None, kind, param, dt, sj, W, n0)
-            else:
-                eng.transform_hop(x, n0, hop, eng.plan.OUT_W, kind, param, dt, sj, W)
-            ctx.geometry = (eng, kind, param, dt, sj, tol, hop, n0)   # the backward is the transpose of exactly this forward
-            return W
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, gW):
-            eng, kind, param, dt, sj, tol, hop, n0 = ctx.geometry
-            real_t = torch.float64 if gW.dtype in (torch.complex128, torch.float64) else torch.float32
-            cplx_t = torch.complex128 if real_t == torch.float64 else torch.complex64
-            g = gW.to(cplx_t).resolve_conj().contiguous()        # (a lazily conjugated cotangent keeps its bits unconjugated in memory)
-            rows = g.shape[-2]
-            nb = g.shape[0] if g.dim() == 3 else 1
-            xbar = torch.empty(tuple(g.shape[:-2]) + (n0,), dtype=real_t, device=g.device)
-            _on_current_stream(torch, eng, g.device)
-            eng.plan.set_tolerance(tol)
-            if hop is None:
-                eng.plan.adjoint_rows(g.data_ptr(), nb, rows * n0, n0, n0, kind, param, dt, sj, xbar.data_ptr(), n0)
-            else:
-                eng.adjoint_rows_hop(g, n0, hop, kind, param, dt, sj, xbar)
-            return xbar, None, None, None, None, None, None
-
-    class CwtPower(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, x, eng, kind, param, dt, sj, hop, pool):
-            n0 = x.shape[-1]
-            P = torch.empty(tuple(x.shape[:-1]) + (sj.size, pooled_columns(n0, hop, pool)), dtype=x.dtype, device=x.device)
-            tol = _tolerance()
-            _on_current_stream(torch, eng, x.device)
-            eng.plan.set_tolerance(tol)
-            if pool is not None:
-                eng.transform_pool(x, n0, pool, kind, param, dt, sj, P)
-            elif hop is None:
-                eng.transform_power(x, n0, None, kind, param, dt, sj, P, n0)
-            else:
-                eng.transform_hop(x, n0, hop, eng.plan.OUT_POWER, kind, param, dt, sj, P)
-            ctx.save_for_backward(x)                             # the signal and the geometry: nothing of rows x n0 elements
-            ctx.geometry = (eng, kind, param, dt, sj, tol, hop, pool)
-            return P
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, gP):
-            (x,) = ctx.saved_tensors
-            eng, kind, param, dt, sj, tol, hop, pool = ctx.geometry
-            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
-            q = gP.to(x.dtype).contiguous()
-            if pool is not None:                                 # the cotangent of |W|^2 at the full rate: gP / c_m on every column of window m
-                q = spread_over_windows(q, x.shape[-1], pool)
-            rows, n0 = q.shape[-2], x.shape[-1]
-            nb = q.shape[0] if q.dim() == 3 else 1
-            G = torch.empty(q.shape, dtype=cplx_t, device=q.device)
-            xbar = torch.empty(tuple(q.shape[:-2]) + (n0,), dtype=x.dtype, device=q.device)
-            _on_current_stream(torch, eng, q.device)
-            eng.plan.set_tolerance(tol)
-            # dL = sum gP 2 Re(conj(W) dW) = Re sum conj(2 gP W) dW: W recomputed from x, weighted in the row kernels' store
-            if hop is None:
-                eng.transform_weighted(x, n0, None, kind, param, dt, sj, q, 2.0, G, n0)
-                eng.plan.adjoint_rows(G.data_ptr(), nb, rows * n0, n0, n0, kind, param, dt, sj, xbar.data_ptr(), n0)
-            else:                                                # the same on the kept columns: G is rows x ceil(n0 / hop)
-                eng.transform_hop(x, n0, hop, eng.plan.OUT_WEIGHTED, kind, param, dt, sj, G, q, 2.0)
-                eng.adjoint_rows_hop(G, n0, hop, kind, param, dt, sj, xbar)
-            del G
-            return xbar, None, None, None, None, None, None, None
-
-    def scale_backward(ctx, x, G, needs):
-        """The backward of the two Functions below for the cotangent G of W (complex, contiguous): (xbar, grad_scales, grad_f0),
-        None where no gradient is asked.  Without a scale or f0 gradient it queues what CwtRows.backward queues."""
-        eng, kind, param, dt, sj, tol, hop, n0, keep, scales, f0 = ctx.geometry
-        real_t = x.dtype
-        need_x, need_s, need_f = needs
-        rows = G.shape[-2]
-        nb = G.shape[0] if G.dim() == 3 else 1
-        xbar = torch.empty(tuple(G.shape[:-2]) + (n0,), dtype=real_t, device=G.device) if need_x or not (need_s or need_f) else None
-        _on_current_stream(torch, eng, G.device)
-        eng.plan.set_tolerance(tol)
-        if not (need_s or need_f):
-            if hop is None:
-                eng.plan.adjoint_rows(G.data_ptr(), nb, rows * n0, n0, n0, kind, param, dt, sj, xbar.data_ptr(), n0)
-            else:
-                eng.adjoint_rows_hop(G, n0, hop, kind, param, dt, sj, xbar)
+    def rows_backward(ctx, G):
+        """What CwtRows and CwtPower do with the cotangent G of W (complex, contiguous), the plan set up by the caller:
+        (xbar, grad_scales, grad_f0), None where no gradient is asked.  Without a scale or f0 gradient that is the adjoint of the
+        rows alone, and the saved x is not looked at."""
+        g = ctx.geometry
+        need_x, need_s, need_f = ctx.needs_input_grad[:3]
+        learn = need_s or need_f
+        xbar = None
+        if need_x or not learn:
+            xbar = torch.empty(tuple(G.shape[:-2]) + (g.n0,), dtype=_real_of(torch, G.dtype), device=G.device)
+        if not learn:
+            run_adjoint(g, G, xbar)
             return xbar, None, None
+        (x,) = ctx.saved_tensors
         xs = x if x.dim() == 2 else x[None]
-        xhat = eng._spectra(xs, G)                              # the signals' spectra, recomputed: x alone was saved
-        eng.forward(xs, n0, xhat)
-        sgrad = torch.empty((rows, 2), dtype=torch.float64, device=G.device)
-        eng.adjoint_rows_scales(G, n0, hop, xhat, kind, param, dt, sj, xbar, sgrad)
+        xhat = g.eng._spectra(xs, G)                            # the signals' spectra, recomputed: x alone was saved
+        g.eng.forward(xs, g.n0, xhat)
+        sgrad = torch.empty((G.shape[-2], 2), dtype=torch.float64, device=G.device)
+        g.eng.adjoint_rows_scales(G, g.n0, g.hop, xhat, g.kind, g.param, g.dt, g.sj, xbar, sgrad)
         gs = gf = None
         if need_s:                                              # d/ds = (d/d ln s) / s; the rows Paul's NaN rule dropped get 0
-            part = sgrad[:, 0] / torch.as_tensor(sj, dtype=torch.float64, device=sgrad.device)
-            gs = torch.zeros(scales.shape, dtype=torch.float64, device=sgrad.device)
-            gs[torch.as_tensor(keep, device=sgrad.device)] = part
-            gs = gs.to(scales.device)
+            part = sgrad[:, 0] / torch.as_tensor(g.sj, dtype=torch.float64, device=sgrad.device)
+            gs = torch.zeros(g.scales.shape, dtype=torch.float64, device=sgrad.device)
+            gs[torch.as_tensor(g.keep, device=sgrad.device)] = part
+            gs = gs.to(g.scales.device)
         if need_f:
-            gf = sgrad[:, 1].sum().to(f0.device)
+            gf = sgrad[:, 1].sum().to(g.f0.device)
         return xbar, gs, gf
 
-    class CwtRowsScales(torch.autograd.Function):
-        """CwtRows with `scales` (and `f0`) as differentiable inputs; their values reach the kernels through `sj` and `param`."""
+    class CwtRows(torch.autograd.Function):
+        """W of x.  `scales` and `f0` (None where the caller gave none) are differentiable inputs whose values reach the kernels
+        through `sj` and `param`; only with one of them is x saved."""
         @staticmethod
         def forward(ctx, x, scales, f0, eng, kind, param, dt, sj, hop, keep):
-            n0 = x.shape[-1]
-            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
-            W = torch.empty(tuple(x.shape[:-1]) + (sj.size, n0 if hop is None else -(-n0 // hop)), dtype=cplx_t, device=x.device)
-            tol = _tolerance()
-            _on_current_stream(torch, eng, x.device)
-            eng.plan.set_tolerance(tol)
-            if hop is None:
-                eng.transform(x, n0, None, kind, param, dt, sj, W, n0)
-            else:
-                eng.transform_hop(x, n0, hop, eng.plan.OUT_W, kind, param, dt, sj, W)
-            ctx.save_for_backward(x)
-            ctx.geometry = (eng, kind, param, dt, sj, tol, hop, n0, keep, scales, f0)
+            g = _Geometry(eng, kind, param, dt, sj, _tolerance(), hop, None, x.shape[-1], keep, scales, f0)
+            W = torch.empty(tuple(x.shape[:-1]) + (sj.size, output_columns(g)), dtype=_complex_of(torch, x.dtype), device=x.device)
+            _begin(torch, eng, x.device, g.tol)
+            run_forward(g, x, W, OUT_W)
+            if scales is not None or f0 is not None:
+                ctx.save_for_backward(x)
+            ctx.geometry = g
             return W
 
         @staticmethod
         @once_differentiable
         def backward(ctx, gW):
-            (x,) = ctx.saved_tensors
-            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
-            g = gW.to(cplx_t).resolve_conj().contiguous()
-            return scale_backward(ctx, x, g, ctx.needs_input_grad[:3]) + (None,) * 7
+            g = ctx.geometry
+            # (a lazily conjugated cotangent keeps its bits unconjugated in memory)
+            G = gW.to(_complex_of(torch, gW.dtype)).resolve_conj().contiguous()
+            _begin(torch, g.eng, G.device, g.tol)
+            return rows_backward(ctx, G) + (None,) * 7
 
-    class CwtPowerScales(torch.autograd.Function):
-        """CwtPower with `scales` (and `f0`) as differentiable inputs."""
+    class CwtPower(torch.autograd.Function):
+        """|W|^2 of x (its window means with `pool`), `scales` and `f0` as in CwtRows.  Saved: the signal and the geometry,
+        nothing of rows x n0 elements."""
         @staticmethod
         def forward(ctx, x, scales, f0, eng, kind, param, dt, sj, hop, keep, pool):
-            n0 = x.shape[-1]
-            P = torch.empty(tuple(x.shape[:-1]) + (sj.size, pooled_columns(n0, hop, pool)), dtype=x.dtype, device=x.device)
-            tol = _tolerance()
-            _on_current_stream(torch, eng, x.device)
-            eng.plan.set_tolerance(tol)
-            if pool is not None:
-                eng.transform_pool(x, n0, pool, kind, param, dt, sj, P)
-            elif hop is None:
-                eng.transform_power(x, n0, None, kind, param, dt, sj, P, n0)
-            else:
-                eng.transform_hop(x, n0, hop, eng.plan.OUT_POWER, kind, param, dt, sj, P)
+            g = _Geometry(eng, kind, param, dt, sj, _tolerance(), hop, pool, x.shape[-1], keep, scales, f0)
+            P = torch.empty(tuple(x.shape[:-1]) + (sj.size, output_columns(g)), dtype=x.dtype, device=x.device)
+            _begin(torch, eng, x.device, g.tol)
+            run_forward(g, x, P, OUT_POWER)
             ctx.save_for_backward(x)
-            ctx.geometry = (eng, kind, param, dt, sj, tol, hop, n0, keep, scales, f0)
-            ctx.pool = pool
+            ctx.geometry = g
             return P
 
         @staticmethod
         @once_differentiable
         def backward(ctx, gP):
             (x,) = ctx.saved_tensors
-            eng, kind, param, dt, sj, tol, hop, n0 = ctx.geometry[:8]
-            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+            g = ctx.geometry
             q = gP.to(x.dtype).contiguous()
-            if ctx.pool is not None:                             # (hop is None then: the undecimated backward on gP / c_m spread over the windows)
-                q = spread_over_windows(q, n0, ctx.pool)
-            G = torch.empty(q.shape, dtype=cplx_t, device=q.device)
-            _on_current_stream(torch, eng, q.device)
-            eng.plan.set_tolerance(tol)
-            if hop is None:                                      # G = 2 gP W, as in CwtPower.backward
-                eng.transform_weighted(x, n0, None, kind, param, dt, sj, q, 2.0, G, n0)
-            else:
-                eng.transform_hop(x, n0, hop, eng.plan.OUT_WEIGHTED, kind, param, dt, sj, G, q, 2.0)
-            out = scale_backward(ctx, x, G, ctx.needs_input_grad[:3])
+            if g.pool is not None:                               # the cotangent of |W|^2 at the full rate: gP / c_m on every column of window m
+                q = spread_over_windows(q, g.n0, g.pool)
+            G = torch.empty(q.shape, dtype=_complex_of(torch, x.dtype), device=q.device)
+            _begin(torch, g.eng, q.device, g.tol)
+            # dL = sum gP 2 Re(conj(W) dW) = Re sum conj(2 gP W) dW: W recomputed from x, weighted in the row kernels' store
+            # (with hop on the kept columns: G is rows x ceil(n0 / hop))
+            run_forward(g, x, G, OUT_WEIGHTED, q, 2.0)
+            out = rows_backward(ctx, G)
             del G
             return out + (None,) * 8
 
@@ -241,17 +195,15 @@ def _function(torch):
         bins (int16, ... x rows x n0) and the geometry are held: neither x, W nor dW."""
         @staticmethod
         def forward(ctx, x, eng, kind, param, dt, sj, grid, gammas):
-            from . import wavelet
             f_lo, dv, nf = grid
             n0, rows = x.shape[-1], sj.size
-            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
+            cplx_t = _complex_of(torch, x.dtype)
             Tx = torch.empty(tuple(x.shape[:-1]) + (nf, n0), dtype=cplx_t, device=x.device)
             bins = torch.empty(tuple(x.shape[:-1]) + (rows, n0), dtype=torch.int16, device=x.device)
             tol = _tolerance()
-            _on_current_stream(torch, eng, x.device)
-            eng.plan.set_tolerance(tol)
+            _begin(torch, eng, x.device, tol)
             es = 8 if x.dtype == torch.float64 else 4
-            chunk = wavelet.SSQ_CHUNK_ROWS or max(1, wavelet._pool_limit(eng.plan.lib, x.device.index or 0) // (n0 * 2 * es))
+            chunk = _wavelet.SSQ_CHUNK_ROWS or max(1, _wavelet._pool_limit(eng.plan.lib, x.device.index or 0) // (n0 * 2 * es))
             chunk = int(min(rows, chunk))
             w = 1.0 / np.sqrt(sj)
             W = torch.empty((rows, n0), dtype=cplx_t, device=x.device)
@@ -279,13 +231,11 @@ def _function(torch):
         def backward(ctx, gT):
             (bins,) = ctx.saved_tensors
             eng, kind, param, dt, sj, tol, nf, n0, finite = ctx.geometry
-            real_t = torch.float64 if gT.dtype in (torch.complex128, torch.float64) else torch.float32
-            cplx_t = torch.complex128 if real_t == torch.float64 else torch.complex64
+            cplx_t = _complex_of(torch, gT.dtype)
             g = gT.to(cplx_t).resolve_conj().contiguous()        # (a lazily conjugated cotangent keeps its bits unconjugated in memory)
             rows = sj.size
-            xbar = torch.empty(tuple(g.shape[:-2]) + (n0,), dtype=real_t, device=g.device)
-            _on_current_stream(torch, eng, g.device)
-            eng.plan.set_tolerance(tol)
+            xbar = torch.empty(tuple(g.shape[:-2]) + (n0,), dtype=_real_of(torch, gT.dtype), device=g.device)
+            _begin(torch, eng, g.device, tol)
             w = 1.0 / np.sqrt(sj)
             G = torch.empty((rows, n0), dtype=cplx_t, device=g.device)      # one signal's rows x n0, whatever the batch
             for gb, bb, xb, ok in zip(g.reshape(-1, nf, n0), bins.reshape(-1, rows, n0), xbar.reshape(-1, n0), finite):
@@ -293,7 +243,7 @@ def _function(torch):
                     xb.fill_(float("nan"))
                     continue
                 eng.ssq_gather(gb, bb, w, G)
-                eng.plan.adjoint_rows(G.data_ptr(), 1, rows * n0, n0, n0, kind, param, dt, sj, xb.data_ptr(), n0)
+                eng.adjoint_rows(G, n0, kind, param, dt, sj, xb)
             del G
             return xbar, None, None, None, None, None, None, None
 
@@ -310,8 +260,7 @@ def _function(torch):
         inverse), signal by signal.  Saves W and lam; the backward is cwt_icwt_shrink_adjoint."""
         @staticmethod
         def forward(ctx, W, lam, eng, sj, mode):
-            real_t = torch.float64 if W.dtype == torch.complex128 else torch.float32
-            out = torch.empty((W.shape[0], W.shape[-1]), dtype=real_t, device=W.device)
+            out = torch.empty((W.shape[0], W.shape[-1]), dtype=_real_of(torch, W.dtype), device=W.device)
             _on_current_stream(torch, eng, W.device)
             for b in range(W.shape[0]):
                 shrink_inverse(eng, W[b], sj, None if lam is None else lam[b], mode, out[b])
@@ -332,8 +281,7 @@ def _function(torch):
             else:
                 W, lam = None, None
                 shape, dtype, device = ctx.shape
-            real_t = torch.float64 if dtype == torch.complex128 else torch.float32
-            g = gy.to(real_t).contiguous()
+            g = gy.to(_real_of(torch, dtype)).contiguous()
             n0 = shape[-1]
             G = torch.empty(shape, dtype=dtype, device=device)
             glam = None if lam is None else torch.empty(lam.shape, dtype=torch.float64, device=device)
@@ -355,14 +303,12 @@ def _function(torch):
         def forward(ctx, x, p, eng, kind, param, dt, sj, mode, universal, columns, c, finite):
             nb, n0 = x.shape
             rows = sj.size
-            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
             out = torch.empty((nb, n0), dtype=x.dtype, device=x.device)
             sigma = torch.zeros((nb, rows), dtype=torch.float64, device=x.device)
             lam = torch.empty((nb, rows), dtype=x.dtype, device=x.device)
             tol = _tolerance()
-            _on_current_stream(torch, eng, x.device)
-            eng.plan.set_tolerance(tol)
-            W = torch.empty((rows, n0), dtype=cplx_t, device=x.device)
+            _begin(torch, eng, x.device, tol)
+            W = torch.empty((rows, n0), dtype=_complex_of(torch, x.dtype), device=x.device)
             K = float(np.sqrt(2.0 * np.log(n0)))
             if universal:                                        # the ranks of the median over the columns [a, b), as row_quantiles
                 a, b = columns
@@ -402,13 +348,11 @@ def _function(torch):
             eng, kind, param, dt, sj, tol, mode, universal, finite = ctx.geometry
             nb, n0 = x.shape
             rows = sj.size
-            cplx_t = torch.complex128 if x.dtype == torch.float64 else torch.complex64
             g = gy.to(x.dtype).contiguous()
             xbar = torch.empty((nb, n0), dtype=x.dtype, device=x.device)
             glam = torch.empty((nb, rows), dtype=torch.float64, device=x.device)
-            _on_current_stream(torch, eng, x.device)
-            eng.plan.set_tolerance(tol)
-            G = torch.empty((rows, n0), dtype=cplx_t, device=x.device)       # W recomputed, then its cotangent in place
+            _begin(torch, eng, x.device, tol)
+            G = torch.empty((rows, n0), dtype=_complex_of(torch, x.dtype), device=x.device)     # W recomputed, then its cotangent in place
             for i in range(nb):
                 if not finite[i]:
                     xbar[i].fill_(float("nan"))
@@ -417,14 +361,11 @@ def _function(torch):
                 eng.transform(x[i], n0, None, kind, param, dt, sj, G, n0)
                 eng.plan.icwt_shrink_adjoint(G.data_ptr(), n0, n0, sj, lam[i].data_ptr(), mode, 1.0, g[i].data_ptr(), G.data_ptr(), n0,
                                              glam[i].data_ptr())
-                eng.plan.adjoint_rows(G.data_ptr(), 1, rows * n0, n0, n0, kind, param, dt, sj, xbar[i].data_ptr(), n0)
+                eng.adjoint_rows(G, n0, kind, param, dt, sj, xbar[i])
             del G
             return (xbar, glam * dlam if universal else glam) + (None,) * 10
 
-    return CwtRows, CwtPower, CwtRowsScales, CwtPowerScales, SsqRows, IcwtShrink, DenoiseRows
-
-
-_fn = None
+    return SimpleNamespace(CwtRows=CwtRows, CwtPower=CwtPower, SsqRows=SsqRows, IcwtShrink=IcwtShrink, DenoiseRows=DenoiseRows)
 
 
 def _learnable(name, torch, x, dj, s0, J, freqs, mother, scales, f0):
@@ -453,9 +394,12 @@ def _learnable(name, torch, x, dj, s0, J, freqs, mother, scales, f0):
     return mother, sj
 
 
+_Call = namedtuple("_Call", "torch eng kind param sj freqs coi hop keep")
+
+
 def _prepare(name, x, dt, dj, s0, J, wavelet, freqs, pad, hop=None, scales=None, f0=None):
-    """The checks, grid and engine of one call of `name` (cwt_torch, cwt_power_torch).  With scales= or f0= a ninth value: the
-    mask of the scales that W keeps (Paul's NaN-row rule), for the gradient's way back."""
+    """The checks, grid and engine of one call of `name` (cwt_torch, cwt_power_torch, ...).  `keep` is the mask of the scales
+    that W keeps (Paul's NaN-row rule), for the way back of a gradient with respect to `scales`."""
     import torch
     if not pad:
         raise ValueError(f"{name}: pad=False (Bluestein transforms of any length) has no adjoint; use pad=True")
@@ -470,9 +414,8 @@ def _prepare(name, x, dt, dj, s0, J, wavelet, freqs, pad, hop=None, scales=None,
     if x.device.type != "cuda" and lib.backend().startswith("hip"):
         raise RuntimeError(f"{name} needs a tensor on a GPU (the HIP kernels cannot read host memory)")
     n0 = int(x.shape[-1])
-    learn = scales is not None or f0 is not None
     given = None
-    if learn:
+    if scales is not None or f0 is not None:
         mother, given = _learnable(name, torch, x, dj, s0, J, freqs, mother, scales, f0)
     if given is None:
         N, sj, freqs, coi, _, bad = _geometry(mother, n0, dt, dj, s0, J, freqs, True)
@@ -492,9 +435,7 @@ def _prepare(name, x, dt, dj, s0, J, wavelet, freqs, pad, hop=None, scales=None,
     nb = int(x.shape[0]) if x.dim() == 2 else 1
     precision = 64 if x.dtype == torch.float64 else 32
     eng = _engine(torch, N, precision, nb * sj.size, x.device, lib)
-    if learn:
-        return torch, eng, kind, float(param), sj, freqs, coi, hop, keep
-    return torch, eng, kind, float(param), sj, freqs, coi, hop
+    return _Call(torch, eng, kind, float(param), sj, freqs, coi, hop, keep)
 
 
 def cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=True, hop=None, *, scales=None, f0=None):
@@ -525,18 +466,9 @@ def cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=T
     the grid there each time -- 1.9 ms for 256 scales at 2^20 points on the build machine (EXPERIMENTS.md); a whole step
     measured 8.2 ms against 6.0 with fixed scales (profiles/scale_grad_bench.txt) -- and a plan caches four row tables, so at
     most four distinct grids alternate for free."""
-    global _fn
-    if scales is not None or f0 is not None:
-        torch, eng, kind, param, sj, freqs, coi, hop, keep = _prepare("cwt_torch", x, dt, dj, s0, J, wavelet, freqs, pad, hop, scales, f0)
-        if _fn is None:
-            _fn = _function(torch)
-        W = _fn[2].apply(x.contiguous(), scales, f0, eng, kind, param, float(dt), sj, hop, keep)
-        return W, sj, freqs, coi
-    torch, eng, kind, param, sj, freqs, coi, hop = _prepare("cwt_torch", x, dt, dj, s0, J, wavelet, freqs, pad, hop)
-    if _fn is None:
-        _fn = _function(torch)
-    W = _fn[0].apply(x.contiguous(), eng, kind, param, float(dt), sj, hop)
-    return W, sj, freqs, coi
+    call = _prepare("cwt_torch", x, dt, dj, s0, J, wavelet, freqs, pad, hop, scales, f0)
+    W = _functions().CwtRows.apply(x.contiguous(), scales, f0, call.eng, call.kind, call.param, float(dt), call.sj, call.hop, call.keep)
+    return W, call.sj, call.freqs, call.coi
 
 
 def cwt_power_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, pad=True, hop=None, *, scales=None, f0=None,
@@ -565,25 +497,15 @@ def cwt_power_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None,
     per element in float64), ``cwt_transform_weighted`` with alpha = 2 (G, rows x n0 complex: 16 B per element), then
     ``cwt_adjoint_rows`` (with scales= / f0=: ``cwt_adjoint_rows_scales``) -- so it holds rows x n0 elements of Q and of G
     transiently, 24 B per element in float64, freed when it returns.  Once differentiable, like its siblings."""
-    global _fn
     if pool is not None and hop is not None:
         _check_pool(pool, 2, hop=hop)
-    if scales is not None or f0 is not None:
-        torch, eng, kind, param, sj, freqs, coi, hop, keep = _prepare("cwt_power_torch", x, dt, dj, s0, J, wavelet, freqs, pad, hop, scales,
-                                                                      f0)
-        if pool is not None:
-            pool, coi = _check_pool(pool, eng.plan.nfft), _pool_coi(coi, pool)
-        if _fn is None:
-            _fn = _function(torch)
-        P = _fn[3].apply(x.contiguous(), scales, f0, eng, kind, param, float(dt), sj, hop, keep, pool)
-        return P, sj, freqs, coi
-    torch, eng, kind, param, sj, freqs, coi, hop = _prepare("cwt_power_torch", x, dt, dj, s0, J, wavelet, freqs, pad, hop)
+    call = _prepare("cwt_power_torch", x, dt, dj, s0, J, wavelet, freqs, pad, hop, scales, f0)
+    coi = call.coi
     if pool is not None:
-        pool, coi = _check_pool(pool, eng.plan.nfft), _pool_coi(coi, pool)
-    if _fn is None:
-        _fn = _function(torch)
-    P = _fn[1].apply(x.contiguous(), eng, kind, param, float(dt), sj, hop, pool)
-    return P, sj, freqs, coi
+        pool, coi = _check_pool(pool, call.eng.plan.nfft), _pool_coi(coi, pool)
+    P = _functions().CwtPower.apply(x.contiguous(), scales, f0, call.eng, call.kind, call.param, float(dt), call.sj, call.hop, call.keep,
+                                    pool)
+    return P, call.sj, call.freqs, coi
 
 
 def ssq_cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *, gamma=None, ssq_freqs=None):
@@ -604,11 +526,11 @@ def ssq_cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *
     the values of W alone.  Saved for the backward: the bins (int16, 2 B per entry of W) and the geometry -- not x, W or dW.
     Backward, signal by signal: ``cwt_ssq_gather`` of the cotangent through the bins into G (one signal's rows x n0), then
     ``cwt_adjoint_rows`` of G.  Once differentiable; no gradient with respect to the scales, gamma or the grid."""
-    global _fn
     mother = _ssq_mother(wavelet)
     user_freqs = freqs is not None
-    torch, eng, kind, param, sj, freqs, coi, _ = _prepare("ssq_cwt_torch", x, dt, dj, s0, J, mother, freqs, True)
-    f_lo, dv, nf = _ssq_grid(freqs, dj, ssq_freqs, user_freqs)
+    call = _prepare("ssq_cwt_torch", x, dt, dj, s0, J, mother, freqs, True)
+    torch = call.torch
+    f_lo, dv, nf = _ssq_grid(call.freqs, dj, ssq_freqs, user_freqs)
     if nf > 32767:
         raise ValueError("ssq_cwt_torch: at most 32767 bins (the map saved for the backward is int16)")
     xs = x.detach().reshape(-1, x.shape[-1])
@@ -622,10 +544,14 @@ def ssq_cwt_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *
         if not (np.isfinite(gamma) and gamma >= 0):
             raise ValueError("ssq_cwt: gamma must be finite and >= 0")
         gammas = [gamma if ok else None for ok in finite.cpu().numpy()]
-    if _fn is None:
-        _fn = _function(torch)
-    Tx = _fn[4].apply(x.contiguous(), eng, kind, param, float(dt), sj, (f_lo, dv, nf), gammas)
-    return Tx, f_lo * 2.0 ** (dv * np.arange(nf)), sj, freqs, coi
+    Tx = _functions().SsqRows.apply(x.contiguous(), call.eng, call.kind, call.param, float(dt), call.sj, (f_lo, dv, nf), gammas)
+    return Tx, f_lo * 2.0 ** (dv * np.arange(nf)), call.sj, call.freqs, call.coi
+
+
+def _icwt_coeff(mother, dt, dj):
+    """dj sqrt(dt) / (cdelta psi(0)): a float where psi(0) is real, else complex"""
+    coeff = complex(dj * np.sqrt(dt) / (mother.cdelta * mother.psi(0)))
+    return coeff.real if coeff.imag == 0 else coeff
 
 
 def issq_cwt_torch(Tx, dt, dj=1 / 12, wavelet="morlet", *, ssq_freqs=None, band=None):
@@ -638,14 +564,7 @@ def issq_cwt_torch(Tx, dt, dj=1 / 12, wavelet="morlet", *, ssq_freqs=None, band=
         raise ValueError("issq_cwt_torch: Tx must be a complex tensor (bins x samples) or (B x bins x samples)")
     w = torch.as_tensor(_band_weights(ssq_freqs, Tx.shape[-2], band), dtype=Tx.real.dtype, device=Tx.device)
     total = (Tx.real * w[:, None]).sum(dim=-2)
-    coeff = complex(dj * np.sqrt(dt) / (mother.cdelta * mother.psi(0)))
-    return total * (coeff.real if coeff.imag == 0 else coeff)
-
-
-def _icwt_coeff(mother, dt, dj):
-    """dj sqrt(dt) / (cdelta psi(0)): a float where psi(0) is real, else complex"""
-    coeff = complex(dj * np.sqrt(dt) / (mother.cdelta * mother.psi(0)))
-    return coeff.real if coeff.imag == 0 else coeff
+    return total * _icwt_coeff(mother, dt, dj)
 
 
 def _shrink_prepare(name, W, sj, wavelet):
@@ -669,9 +588,8 @@ def _shrink_prepare(name, W, sj, wavelet):
 
 
 def _check_mode(name, mode):
-    from .wavelet import SHRINK_MODES
-    if mode not in SHRINK_MODES:
-        raise ValueError(f"{name}: mode must be one of {SHRINK_MODES}; got {mode!r}")
+    if mode not in _wavelet.SHRINK_MODES:
+        raise ValueError(f"{name}: mode must be one of {_wavelet.SHRINK_MODES}; got {mode!r}")
     return mode
 
 
@@ -692,11 +610,8 @@ def icwt_torch(W, sj, dt, dj=1 / 12, wavelet="morlet"):
     (B, rows, n0) on the device; (n0,) or (B, n0), real where the mother's psi(0) is.  The sum is ``cwt_icwt_reduce`` on torch's
     current stream, the factor a torch operation; the backward is ``cwt_icwt_shrink_adjoint`` without thresholds
     (G[j, n] = gy[n] / sqrt(s_j)): nothing is saved.  Built-in mothers; once differentiable."""
-    global _fn
     torch, eng, mother, sj, Wb = _shrink_prepare("icwt_torch", W, sj, wavelet)
-    if _fn is None:
-        _fn = _function(torch)
-    total = _fn[5].apply(Wb, None, eng, sj, 0)
+    total = _functions().IcwtShrink.apply(Wb, None, eng, sj, 0)
     return (total if W.dim() == 3 else total[0]) * _icwt_coeff(mother, dt, dj)
 
 
@@ -708,14 +623,10 @@ def icwt_shrink_torch(W, sj, dt, lam, dj=1 / 12, wavelet="morlet", mode="soft"):
     gradient with respect to lam is 0 in hard mode -- summed per row in one fixed order, in float64 across a row's slices.
     W and lam are saved (time-frequency masking between ``cwt_torch`` and here keeps W anyway); ``denoise_torch`` is the
     composition that does not.  Built-in mothers; once differentiable."""
-    global _fn
     torch, eng, mother, sj, Wb = _shrink_prepare("icwt_shrink_torch", W, sj, wavelet)
     mode = _check_mode("icwt_shrink_torch", mode)
-    real_t = torch.float64 if Wb.dtype == torch.complex128 else torch.float32
-    lam_b = _rows_parameter("icwt_shrink_torch", "lam", torch, lam, Wb.shape[0], sj.size, W.dim() == 3, Wb.device).to(real_t).contiguous()
-    if _fn is None:
-        _fn = _function(torch)
-    total = _fn[5].apply(Wb, lam_b, eng, sj, mode)
+    lam_b = _rows_parameter("icwt_shrink_torch", "lam", torch, lam, Wb.shape[0], sj.size, W.dim() == 3, Wb.device)
+    total = _functions().IcwtShrink.apply(Wb, lam_b.to(_real_of(torch, Wb.dtype)).contiguous(), eng, sj, mode)
     return (total if W.dim() == 3 else total[0]) * _icwt_coeff(mother, dt, dj)
 
 
@@ -739,7 +650,6 @@ def denoise_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *
     (``cwt_icwt_shrink_adjoint``, which also sums the cotangent of the thresholds), ``cwt_adjoint_rows``, the buffer freed.  A
     signal with a non-finite sample gives NaN in its y and in its gradients (one read-back of the flags per call).  Built-in
     mothers, pad=True, no hop; the refusals of ``denoise``; once differentiable."""
-    global _fn
     mode = _check_mode("denoise_torch", mode)
     if isinstance(threshold, str) and threshold != "universal":
         raise ValueError(f'denoise_torch: threshold must be "universal" or a tensor of thresholds; got {threshold!r}')
@@ -747,7 +657,8 @@ def denoise_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *
     if not hasattr(mother, "device_id"):
         raise NotImplementedError("denoise_torch needs a built-in mother (Morlet, Paul, DOG, MexicanHat from pycwt_amd); "
                                   f"got {type(mother).__name__} without device_id()")
-    torch, eng, kind, param, sj, freqs, coi, _ = _prepare("denoise_torch", x, dt, dj, s0, J, mother, freqs, True)
+    call = _prepare("denoise_torch", x, dt, dj, s0, J, mother, freqs, True)
+    torch, sj = call.torch, call.sj
     from .mothers import DOG
     nb, n0, rows = (int(x.shape[0]) if x.dim() == 2 else 1), int(x.shape[-1]), sj.size
     universal = isinstance(threshold, str)
@@ -767,14 +678,13 @@ def denoise_torch(x, dt, dj=1 / 12, s0=-1, J=-1, wavelet="morlet", freqs=None, *
     xs = x.reshape(nb, n0).contiguous()
     finite = [bool(v) for v in torch.isfinite(xs.detach()).all(dim=1).cpu().numpy()]
     c = 0.6744897501960817 if isinstance(mother, DOG) else float(np.sqrt(np.log(4.0)))
-    if _fn is None:
-        _fn = _function(torch)
-    total, sigma = _fn[6].apply(xs, p.to(torch.float64), eng, kind, param, float(dt), sj, mode, universal, columns, c, finite)
+    total, sigma = _functions().DenoiseRows.apply(xs, p.to(torch.float64), call.eng, call.kind, call.param, float(dt), sj, mode, universal,
+                                                  columns, c, finite)
     lam = (p.to(torch.float64) * sigma) * float(np.sqrt(2.0 * np.log(n0))) if universal else p
     y = total * _icwt_coeff(mother, dt, dj)
     if x.dim() == 1:
         y, lam = y[0], lam[0]
-    return y, lam, sj, freqs, coi
+    return y, lam, sj, call.freqs, call.coi
 
 
 def _ssq_saved_bins(Tx):

@@ -165,6 +165,12 @@ class HipEngine:
         nb = 1 if x.dim() == 1 else x.shape[0]
         self.plan.transform_pool(x.data_ptr(), nb, x.shape[-1], n0, kind, param, dt, sj, pool, None, P.data_ptr(), P.shape[-1])
 
+    def adjoint_rows(self, G, n0, kind, param, dt, sj, xbar, accumulate=False):
+        """xbar (+)= Re A^H G (cwt_adjoint_rows): G (rows, ld) or (batch, rows, ld) complex, xbar (n0,) or (batch, ld_x)."""
+        nb = 1 if G.dim() == 2 else G.shape[0]
+        self.plan.adjoint_rows(G.data_ptr(), nb, G.shape[-2] * G.shape[-1], G.shape[-1], n0, kind, param, dt, sj,
+                               xbar.data_ptr(), xbar.shape[-1], accumulate)
+
     def adjoint_rows_hop(self, G, n0, hop, kind, param, dt, sj, xbar, accumulate=False):
         """xbar (+)= Re A_h^H G (cwt_adjoint_rows_hop): G (rows, ld) or (batch, rows, ld) complex, xbar (n0,) or (batch, ld_x)."""
         nb = 1 if G.dim() == 2 else G.shape[0]
